@@ -12,7 +12,16 @@ InferenceCore.step with the frame already resident in HBM; the FPS definition mi
 cutie/eval_vos.py:126-145,165-167 (time around processor.step only).  With N GPUs each rank runs its own clip
 (clip sharding: weak scaling, no collective on the data path; the final gather of per-rank times is RCCL).
 
-One JSON line is printed by rank 0.  Extra objects:
+A plain run sets up, warms up, times exactly --steps steps once and prints one JSON line (rank 0): value = frames/s of that region,
+ms_per_step = its milliseconds per step.  --dump-outputs DIR also writes what the last timed step returned to its caller
+(DIR/prob.npy, float32: InferenceCore.step's probabilities, rank 0's clip); the inputs are seeded, so the same arguments give the
+same inputs in every run.
+
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+
+--full adds every other leg: five timed regions ("value" = the median one, spread in "repeats"), the clip without look-ahead
+hints and under the reference's FPS protocol, the bank at its steady-state size, the clips-in-flight / lock-step legs and the
+objects below.  Extra objects (--full):
   roofline           dominant kernel family (implicit-GEMM conv on MFMA): algorithmic flops of the conv launches
                      of the timed frames / their device time, measured live with hipEvents on the launch stream
   roofline_affinity  the fused affinity read-out (similarity + top-k + softmax + V read-out) credited with the
@@ -48,12 +57,12 @@ def parse():
     ap.add_argument('--no-long-term', action='store_true')
     ap.add_argument('--preroll', type=int, default=300,
                     help='untimed frames run before the warm-up so the memory bank is in its steady-state size')
-    ap.add_argument('--cpu-frames', type=int, default=12, help='frames of the CPU baseline sample (0 = skip)')
+    ap.add_argument('--cpu-frames', type=int, default=12, help='(--full) frames of the CPU baseline sample (0 = skip)')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-breakdown', action='store_true')
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--full-bank-preroll', type=int, default=2000,
-                    help='also report frames/s with the memory bank at its steady-state size: an extra clip run this many frames '
+                    help='(--full) also report frames/s with the memory bank at its steady-state size: an extra clip run this many frames '
                          'before its timed steps (SURVEY C2: 18-26k tokens, pruning fires near frame 1995); 0 = skip')
     ap.add_argument('--no-lookahead', action='store_true',
                     help='do not pass next_image to step (no overlap of the next frame\'s image encoder on a side stream)')
@@ -61,10 +70,15 @@ def parse():
                     help='frames per batched look-ahead encoder plan (step(next_images=...), InferenceCore.prefetch_window); '
                          '<= 1: one frame ahead (step(next_image=...))')
     ap.add_argument('--repeats', type=int, default=5,
-                    help='the timed region of --steps frames is repeated this many times; "value" is the FIRST one (the protocol-conform '
-                         'measurement), the spread goes to "repeats"')
+                    help='(--full) the timed region of --steps frames is repeated this many times; "value" is the MEDIAN one, the first one '
+                         'goes to "value_first_region", the spread to "repeats"')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every leg beyond the headline region: repeated regions, the un-hinted clip and the reference\'s FPS protocol, '
+                         'the full bank, clips in flight, roofline / per-kernel figures and the CPU baseline (off: the headline region only)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (the probabilities, float32) to DIR/prob.npy')
     ap.add_argument('--clips-in-flight', type=int, default=4,
-                    help='also measure the aggregate frames/s with this many independent clips in flight per GPU '
+                    help='(--full) also measure the aggregate frames/s with this many independent clips in flight per GPU '
                          '(one HIP stream + CUTIE.fork() each, see --multi-mode; reported as "multi_clip"; 0 = skip)')
     ap.add_argument('--multi-hw-queues', type=int, default=0,
                     help='> 0 (one GPU): the clips-in-flight leg runs in a child process started with GPU_MAX_HW_QUEUES set to this (HIP maps '
@@ -426,6 +440,22 @@ def conv_flops(arr):
     return f
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as d/<name>.npy in float32.  An array above DUMP_BYTES is written as a fixed sample instead: the flat
+    entries at the sorted indices numpy.random.default_rng(0).choice(size, DUMP_BYTES // 4, replace=False), the same for every run of
+    the same arguments."""
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_BYTES:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_BYTES // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` (N > 1) outside a launcher: start the N ranks ourselves -- the driver's own command line, one process per GPU
     (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>`) -- and hand its
@@ -456,6 +486,10 @@ def main():
     dist = None
     pinned = None
     on_cpu = args.cpu_interpreter
+    if not args.full and not args.multi_only:                # a plain run: the headline region and nothing else
+        args.no_roofline = True
+        args.clips_in_flight = args.cpu_frames = args.full_bank_preroll = 0
+        args.repeats = 1
     if on_cpu:                                               # (tests: protocol only -- every leg that measures the device is off)
         args.no_roofline = args.no_graph = True
         args.clips_in_flight = args.cpu_frames = args.full_bank_preroll = 0
@@ -536,8 +570,13 @@ def main():
         from cutie_amd.parallel import timed_steps
         base = t_idx
 
+        kept = {}                                          # --dump-outputs: what the last timed step returned to its caller
+        keep_at = [args.warmup + args.steps - 1 if args.dump_outputs else -1]
+
         def one_step(i):
-            proc.step(frames[(base + i) % 128], **la(base + i))
+            p = proc.step(frames[(base + i) % 128], **la(base + i))
+            if i == keep_at[0]:
+                kept['prob'] = p
 
         # W warm-up steps, then exactly K timed steps between barrier + synchronize, MAX over the ranks (cutie_amd/parallel.py)
         rank_secs = []
@@ -550,8 +589,12 @@ def main():
         for _ in range(max(0, args.repeats - 1)):
             base = t_idx
             rs = []
+            keep_at[0] = args.steps - 1 if args.dump_outputs else -1
             regions.append((timed_steps(one_step, args.steps, 0, dev, per_rank=rs), rs))
             t_idx = base + args.steps
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, kept)
+        kept.clear()
         rep_vals = [round(world * args.steps / r[0], 2) for r in regions]
         med = sorted(range(len(regions)), key=lambda j: regions[j][0])[len(regions) // 2]
         first_elapsed, (elapsed, rank_secs) = elapsed, regions[med]
@@ -559,7 +602,7 @@ def main():
         # ---- the same clip WITHOUT the next_image hint: what an unchanged scripting_demo.py / eval loop of the reference gets ----
         no_la = None
         hinted_protocol = None
-        if not args.no_lookahead and not on_cpu:
+        if args.full and not args.no_lookahead and not on_cpu:
             # the reference's own FPS protocol (cutie/eval_vos.py:126-145) for the HINTED caller as well
             ev_ms, t0p = 0.0, time.perf_counter()
             for i in range(args.steps):
@@ -577,7 +620,7 @@ def main():
                                        'the event intervals ON THE CALLER\'S STREAM -- the look-ahead lanes (window encoder, stacked read-outs) run on other streams and are '
                                        'only caught by the synchronize behind the second event, so for this multi-stream caller wall_fps (the two host synchronisations per '
                                        'frame included) is the honest one of the two'}
-        if not args.no_lookahead and not on_cpu:
+        if args.full and not args.no_lookahead and not on_cpu:
             base2 = t_idx
             # un-timed steps first, enough of them to use up every frame the hinted steps before have already encoded ahead (a look-ahead
             # window and its lead): with 2 of them a 20-step region still ran on left-over window entries (1023 frames/s instead of ~820)

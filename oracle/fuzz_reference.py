@@ -5,6 +5,10 @@ the same weights; per-frame probabilities and memory-bank sizes must agree.  Com
 (tests/golden): those travel to the GPU box, this runs only where /root/reference exists (the build container).
 
     python oracle/fuzz_reference.py --seeds 0 1 2 [--frames 14] [--model small]
+    python oracle/fuzz_reference.py --seeds 5 8 20 --record tests/golden/fuzz_reference_seeds_5_8_20.npz
+
+--record also stores the reference's per-frame probabilities (whole frames, on a grid of 1/PROB_LEVELS: pack_probs) and memory
+sizes of every seed it could run, for tests/test_fuzz_cpu.py to hold the oracle to without the reference checkout.
 
 TEST INFRASTRUCTURE (see oracle/__init__.py)."""
 import argparse
@@ -17,6 +21,24 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, '..'))
 from oracle.make_golden import _wrap, import_reference, memory_sizes, reference_cfg      # noqa: E402
+
+PROB_LEVELS = 1023                     # --record: probabilities p in [0, 1] stored as round(p * PROB_LEVELS)
+
+
+def pack_probs(p):
+    """(planes, H, W) probabilities -> uint8 (2, planes, H, W): round(p * PROB_LEVELS), differenced along W and then H, zigzag-coded,
+    low and high byte.  Compressed, the differences take less than half the room of the plain levels."""
+    x = np.round(np.asarray(p, dtype=np.float64) * PROB_LEVELS).astype(np.int32)
+    d = np.diff(np.diff(x, axis=-1, prepend=0), axis=-2, prepend=0)
+    z = (d << 1) ^ (d >> 31)
+    return np.stack([z & 255, z >> 8]).astype(np.uint8)
+
+
+def unpack_probs(b):
+    """pack_probs(p) -> p on the grid of 1/PROB_LEVELS (float64; within 0.5 / PROB_LEVELS of p)."""
+    z = b[0].astype(np.int32) | (b[1].astype(np.int32) << 8)
+    d = (z >> 1) ^ -(z & 1)
+    return np.cumsum(np.cumsum(d, axis=-2), axis=-1) / PROB_LEVELS
 
 
 def random_scenario(seed, frames):
@@ -98,6 +120,7 @@ def main():
     ap.add_argument('--frames', type=int, default=14)
     ap.add_argument('--tol', type=float, default=5e-3)
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
+    ap.add_argument('--record', default=None, help='.npz: the reference\'s probabilities and memory sizes of every seed it ran')
     args = ap.parse_args()
     torch.set_num_threads(min(8, os.cpu_count() or 1))
     CUTIE, InferenceCore = import_reference()
@@ -112,6 +135,7 @@ def main():
     onet = OracleNet(sd, mcfg)
     wrap = lambda over: reference_cfg(args.model, **{k: (_wrap(v) if isinstance(v, dict) else v) for k, v in over.items()})
     bad = 0
+    rec = {'frames': np.int64(args.frames), 'model': np.array(args.model), 'seeds': []}
     for seed in args.seeds:
         sc = random_scenario(seed, args.frames)
         S.SCENARIOS['_fuzz'] = sc
@@ -122,6 +146,10 @@ def main():
         except Exception as e:                                     # the script trips a bug of the reference itself: not comparable
             print(f'seed {seed}: skipped, the reference raised {type(e).__name__}: {e}')
             continue
+        rec['seeds'].append(seed)
+        rec[f'sizes_{seed}'] = np.array(rs, dtype=np.int64)
+        for t, p in enumerate(routs):
+            rec[f'prob_{seed}_{t}'] = pack_probs(p.numpy())
 
         def osizes(p):
             w = sum(p.work.size(b) for b in p.work.buckets)
@@ -141,6 +169,9 @@ def main():
             print('   per-frame errors', [f'{e:.1e}' for e in errs])
             print('   ref sizes   ', rs)
             print('   oracle sizes', os_)
+    if args.record:
+        rec['seeds'] = np.array(rec['seeds'], dtype=np.int64)
+        np.savez_compressed(args.record, **rec)
     sys.exit(1 if bad else 0)
 
 

@@ -162,3 +162,17 @@ def test_bench_gpus_flag_starts_that_many_ranks():
     assert r.returncode == 0 and line['n_gpus'] == 1 and len(line['per_rank_fps']) == 1, r.stderr[-2000:]
     r, line = _run_bench(['--gpus', '2'], env={'WORLD_SIZE': '3', 'RANK': '0', 'LOCAL_RANK': '0'})
     assert r.returncode != 0 and line is None and '--gpus 2' in r.stderr and 'WORLD_SIZE=3' in r.stderr
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`--dump-outputs DIR` writes what the last of exactly --steps timed steps returned to its caller -- InferenceCore.step's
+    probabilities, float32 -- to DIR/prob.npy; the line's ms_per_step is the time of one of those steps."""
+    import numpy as np
+    d = tmp_path / 'out'
+    r, line = _run_bench(['--gpus', '1', '--dump-outputs', str(d)])
+    assert r.returncode == 0 and line['steps'] == 3, r.stderr[-2000:]
+    assert abs(line['value'] - 1e3 / line['ms_per_step']) < 0.01 * line['value']
+    assert sorted(os.listdir(d)) == ['prob.npy']
+    a = np.load(d / 'prob.npy')
+    assert a.dtype == np.float32 and a.shape == (3, 48, 80) and np.isfinite(a).all()
+    assert np.abs(a.sum(0) - 1).max() < 1e-4                      # background + 2 objects

@@ -11,7 +11,7 @@ O=gpurun_out/ab_$name
 mkdir -p $O
 for r in $(seq 1 $reps); do
   for i in "${!variants[@]}"; do
-    env ${variants[$i]} timeout 300 python bench.py --steps 400 --cpu-frames 0 --clips-in-flight 0 --full-bank-preroll 0 --no-breakdown "$@" > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err
+    env ${variants[$i]} timeout 300 python bench.py --full --steps 400 --cpu-frames 0 --clips-in-flight 0 --full-bank-preroll 0 --no-breakdown "$@" > $O/v${i}_r$r.json 2> $O/v${i}_r$r.err
     python - <<PY
 import json
 try:

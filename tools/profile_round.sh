@@ -5,10 +5,10 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 export OMP_NUM_THREADS=16
 export CUTIE_AMD_TILE_CACHE=/tmp/cutie_tiles.json
 R=${1:-r01}
-BENCH="python bench.py --steps 60 --warmup 10 --preroll 60 --cpu-frames 0 --no-roofline --clips-in-flight 0"
+BENCH="python bench.py --full --steps 60 --warmup 10 --preroll 60 --cpu-frames 0 --no-roofline --clips-in-flight 0"
 OUT=/tmp/prof_$R
 rm -rf $OUT; mkdir -p $OUT gpurun_out
-python bench.py --steps 20 --warmup 5 --preroll 30 --cpu-frames 0 --no-roofline --clips-in-flight 0 > $OUT/tune.log 2>&1
+python bench.py --full --steps 20 --warmup 5 --preroll 30 --cpu-frames 0 --no-roofline --clips-in-flight 0 > $OUT/tune.log 2>&1
 timeout 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $BENCH > $OUT/stats.log 2>&1
 i=0
 for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_BF16" "FETCH_SIZE" "WRITE_SIZE" ${EXTRA_PMC:+"$EXTRA_PMC"}; do

@@ -24,22 +24,16 @@ from .object_manager import ObjectManager
 
 log = logging.getLogger()
 F32 = torch.float32
-AHEAD_AFFINITY = os.environ.get('CUTIE_AMD_AHEAD_AFFINITY', '1') not in ('', '0')     # look-ahead of the affinity read-out (see prefetch)
 # memorising on the side stream when no look-ahead hint is given (step / _join_pending): opt-in -- measured neutral on the MI355X (726 against
 # 730 fps without hints, profiles/r03_host.md: by the time the host has issued the next frame's encoder the side stream is almost done)
 DEFER_MEM = os.environ.get('CUTIE_AMD_DEFER_MEM', '0') not in ('', '0')
 # look-ahead WINDOW of the image encoder (step(next_images=...)): frames per batched encoder plan (<= 1: one frame at a time, as with
 # next_image), and how many already-encoded frames may be left ahead when the next batch is started
-# memory frames in two parts when the next frame is encoded already: its affinity read-out overlaps the summarizer (A/B switch)
-MEM_SPLIT = os.environ.get('CUTIE_AMD_MEM_SPLIT', '1') not in ('', '0')
 WAIT_TRACE = None                                          # a list: step() brackets its wait for the look-ahead with timing events (diagnostic)
 # one affinity read-out per BANK VERSION: the look-ahead read-out covers up to this many announced frames at once -- all frames up to and
 # including the next memory frame that sit in one encoder batch of the window (MemoryManager.prefetch_affinity_batch; <= 1: frame by frame)
 AFF_BATCH = int(os.environ.get('CUTIE_AMD_AFF_BATCH', '8'))
 AFF_FIRST_ALONE = os.environ.get('CUTIE_AMD_AFF_FIRST_ALONE', '1') not in ('', '0')     # (A/B switch: a memory frame's successor read on its own, see _ahead_affinity)
-# with AFF_FIRST_ALONE: the stacked pass for the rest of the memory cycle is not queued behind the successor's read-out at the memory frame, but by
-# the NEXT step's look-ahead (it then starts behind the memory frame's own tail -- sensory deep update, summarizer -- instead of next to it); A/B switch
-AFF_REST_LATER = os.environ.get('CUTIE_AMD_AFF_REST_LATER', '0') not in ('', '0')
 WINDOW = int(os.environ.get('CUTIE_AMD_WINDOW', '12'))
 WINDOW_LEAD = int(os.environ.get('CUTIE_AMD_WINDOW_LEAD', '3'))
 
@@ -108,7 +102,7 @@ class InferenceCore:
         drive the same network one after the other (clip after clip, a flip lane) then order their look-ahead work on the shared plan
         buffers by stream order.  (CUTIE.fork() gives a concurrent clip its own engine, hence its own streams.)"""
         eng = self.network.engine()
-        if plans.ONE_LANE or eng.one_lane:
+        if eng.one_lane:
             # several clips in flight on one GPU (cutie_amd/parallel.py): the look-ahead lanes of a clip keep their batching (one
             # encoder plan per 12 frames, one read-out per bank version) but run on the clip's own stream -- the other clips are what
             # fills the device next to it, and a clip that brings four streams of its own only competes for the hardware queues
@@ -462,7 +456,7 @@ class InferenceCore:
         g = frame_context.recall('geometry', image)            # (h0, w0, H, W, pad_left, pad_top) of the un-padded frame
         raw = (image, g[0], g[1], g[4], g[5]) if g is not None else None
         pre = self._prefetched
-        if (MEM_SPLIT and AHEAD_AFFINITY and pre is not None and self._prefetched_rec is not None and self._flip is None
+        if (pre is not None and self._prefetched_rec is not None and self._flip is None
                 and self._lane_of_other is None):
             # The next frame is encoded already (window hints): memorise in two parts.  The mask VALUES go into the bank first; then that
             # frame's affinity read-out -- which a memory frame cannot run ahead of its own insertion -- starts on the side stream against
@@ -473,8 +467,7 @@ class InferenceCore:
                 need_weights=self.save_aux, _raw=raw, _split=True)
             self.memory.add_memory(key, shrinkage, msk_value, None, ids, selection=selection, as_permanent=as_permanent)
             feats = pre[2]
-            ev = self._ahead_affinity(feats[2], feats[4], pre[3], self._prefetched_rec, next_mem_ti=self.curr_ti + self.mem_every, first_alone=AFF_FIRST_ALONE,
-                                      part='first' if (AFF_FIRST_ALONE and AFF_REST_LATER) else None)
+            ev = self._ahead_affinity(feats[2], feats[4], pre[3], self._prefetched_rec, next_mem_ti=self.curr_ti + self.mem_every, first_alone=AFF_FIRST_ALONE)
             self._prefetched = pre[:3] + (ev,) + pre[4:]
             sensory, obj_value = finish()
             self.memory.add_object_values(obj_value, ids)
@@ -584,7 +577,7 @@ class InferenceCore:
             key_f, shr_f, sel_f = fl.image_feature_store.get_key(self.curr_ti, image_f)
         elif (next_image is not None or (next_images is not None and len(next_images) > 0)) and not end:
             # (the next frame's read-out may run ahead only if this frame leaves the bank alone)
-            aff = AHEAD_AFFINITY and not (is_mem_frame or force_permanent) and self.memory.engaged
+            aff = not (is_mem_frame or force_permanent) and self.memory.engaged
             if next_images is not None and len(next_images) > 0:
                 self.prefetch_window(next_images, affinity=aff)
             else:

@@ -78,7 +78,7 @@ class LockstepCores:
         c0 = self.cores[0]
         if c0._flip is not None or (c0.chunk_size is not None and c0.chunk_size >= 1) or c0.save_aux:
             return False
-        if plans.UNFUSED or not plans.QCHAIN or not plans.SEG_MD or not plans.STEM or IC.DEFER_MEM:     # (A/B switches of the one-clip path that the lock-step plans do not carry)
+        if IC.DEFER_MEM:                                  # (deferred memorising of the one-clip path: the lock-step plans do not carry it)
             return False
         shape = tuple(images[0].shape)
         if c0.max_internal_size > 0 and min(shape[-2:]) > c0.max_internal_size:
@@ -372,7 +372,7 @@ class LockstepCores:
         K = cores[0].object_manager.num_obj
         sf, sb, ov = self._stack_state(K)
         if next_images is not None and len(next_images) == G:
-            self._prefetch(next_images, affinity=IC.AHEAD_AFFINITY and not is_mem_frame)
+            self._prefetch(next_images, affinity=not is_mem_frame)
         # ---- affinity read-out: per clip (its own bank), taken over from the look-ahead lane where that ran against this bank version
         h, w = recs[0]['h'], recs[0]['w']
         readouts = []
@@ -426,7 +426,7 @@ class LockstepCores:
         sf, sb, _ = self._state
         ws = recs[0]['_wstride']
         KT = G * K
-        md = self._md_valid and plans.SUM_FUSED
+        md = self._md_valid
         P = eng.plan(('ls_emask', G, K, h0, w0, H, W, pl, pt, md, ws), plans.build_encode_mask, K, h0, w0, H, W, pl, pt, True, md, G, ws)
         o = eng.pool.get(('ls_emask', G, K, h, w, eng.devstr),
                          dict(value=((KT, h, w, m['value_dim']), BF16, False),
@@ -441,7 +441,7 @@ class LockstepCores:
             _, _, key, shrinkage, selection = feats[c]
             with frame_context.context(self._ctx[c]):
                 core.memory.add_memory(key, shrinkage, group_logical(value[c * K:(c + 1) * K]), None, ids, selection=selection, as_permanent='first')
-        if next_images is not None and IC.AHEAD_AFFINITY and IC.MEM_SPLIT:
+        if next_images is not None:
             # every clip's next frame first (the next step waits for them), the stacked passes for the rest of the memory cycle behind them
             nxt = []
             for c, core in enumerate(cores):

@@ -24,13 +24,8 @@ from .object_manager import ObjectManager
 log = logging.getLogger()
 BF16, F32 = torch.bfloat16, torch.float32
 CAND_CAP = 1024          # candidate slots per query column (typical fill ~35; see csrc/affinity.hip)
-_UNFUSED = os.environ.get('CUTIE_AMD_UNFUSED', '0') not in ('', '0')      # diagnostic A/B switch, see model/plans.py
 _VALIDATE = os.environ.get('CUTIE_AMD_VALIDATE', '0') not in ('', '0')
-BANK_WRITE = os.environ.get('CUTIE_AMD_BANK_WRITE', '1') not in ('', '0')      # the copies / fills of an insertion in one launch (A/B switch)
-BATCH_FORMS = os.environ.get('CUTIE_AMD_AFF_BATCH_FORMS', '1') not in ('', '0')   # stacked read-outs pick their score kernels by frame count (A/B switch)
-JOINT_DMA = int(os.environ.get('CUTIE_AMD_JOINT_DMA', '0'))      # clips in lock step: the joint read-out stages its memory tiles by LDS-DMA in the score pass (1) / the candidate pass (2) (A/B switch)
 PATCH_PLANS = os.environ.get('CUTIE_AMD_PATCH_PLANS', '1') not in ('', '0')    # sizes that a memory frame changes are patched into the cached affinity / commit plans (off: rebuilt; A/B + test switch)
-COMMIT_ON_SIDE = os.environ.get('CUTIE_AMD_COMMIT_SIDE', '1') not in ('', '0')  # bookkeeping of a consumed look-ahead read-out on the look-ahead stream (A/B switch)
 # bank versions are drawn from one process-wide counter: a look-ahead read-out tagged with the version of one manager can never pass
 # the check of another (InferenceCore.clear_memory replaces the manager; per-manager counters would restart at 0 and collide)
 _VERSIONS = itertools.count(1)
@@ -211,7 +206,7 @@ class MemoryManager:
         vals = (tuple(flat), G, bucket.n_work, bucket.n_long)
         plans_ = bucket.__dict__.setdefault('_aff_plans', {})
         cached = plans_.get(ahead)
-        if cached is not None and cached[0] == key and (cached[1] == vals or (PATCH_PLANS and not _UNFUSED)):
+        if cached is not None and cached[0] == key and (cached[1] == vals or PATCH_PLANS):
             if cached[1] != vals:
                 ol, ops_ = cached[2], cached[3]
                 for op in (ops_['score0'], ops_['score1']):
@@ -241,11 +236,6 @@ class MemoryManager:
                 ticks.append((D('life'), bucket.n_long))
             if ahead and self.use_long_term:
                 ops_['select'] = ol.aff_select(D('gmax'), D('tau'), HW=HW, HWp=HWp, G=G, top_k=self.top_k, clear_count=D('count'), zero=(D('usage'), 2 * nslots), prio=True)
-            elif _UNFUSED:
-                ol.memset32(D('count'), HW * O.OpList.AFF_CSTRIDE, 0)
-                ops_['select'] = ol.aff_select(D('gmax'), D('tau'), HW=HW, HWp=HWp, G=G, top_k=self.top_k)
-                for life, n in ticks:
-                    ol.usage_tick(life, n)
             else:
                 ops_['select'] = ol.aff_select(D('gmax'), D('tau'), HW=HW, HWp=HWp, G=G, top_k=self.top_k, clear_count=D('count'), ticks=ticks, prio=True)
             ops_['score1'] = ol.aff_score(D('Ahi'), D('Alo'), D('scale'), D('Bhi'), D('Blo'), D('cq'), D('tau'), D('cval'), D('cidx'), D('count'),
@@ -305,7 +295,7 @@ class MemoryManager:
         nslots = int(bucket.use.shape[0]) if self.use_long_term else 0
         clear_long = self.use_long_term and bucket.n_long > 0 and not self.count_long_term_usage
         flat = [v for r in ranges for v in r] + [0] * (6 - 2 * len(ranges))
-        key = (len(ranges), K, HW, HWp, self.top_k, self.use_long_term, clear_long, nslots, F, BATCH_FORMS)     # (see _affinity: launches / sizes)
+        key = (len(ranges), K, HW, HWp, self.top_k, self.use_long_term, clear_long, nslots, F)     # (see _affinity: launches / sizes)
         vals = (tuple(flat), G, bucket.n_long)
         plans_ = bucket.__dict__.setdefault('_aff_plans', {})
         cached = plans_.get(('batch', F))
@@ -327,7 +317,7 @@ class MemoryManager:
             # times at 12.2 k tokens, tools/aff_batch_ab.py, profiles/r05_affinity.md): from three frames on the score pass runs 64 queries
             # per wave on the LDS-DMA kernel (its longer prologue is amortised: 70.6 against 80.0 us at F = 5, MFMA utilisation 0.44
             # against 0.39) and the candidate pass stages its memory tiles by LDS-DMA (94 against 103 us)
-            big = F >= 3 and BATCH_FORMS
+            big = F >= 3
             nq0, dma1 = (4, True) if big else (None, None)
             ops_['score0'] = ol.aff_score(D('Ahi'), D('Alo'), D('scale'), D('Bhi'), D('Blo'), D('cq'), D('gmax'), None, None, None, mode=0, nq=nq0, **common)
             ops_['select'] = ol.aff_select(D('gmax'), D('tau'), HW=HW, HWp=HWp, G=G, top_k=self.top_k, clear_count=D('count'), frames=F,
@@ -381,7 +371,7 @@ class MemoryManager:
                 return self._commit_ahead(bucket, udelta, network)
         ol = cached[1]
         side = None
-        if COMMIT_ON_SIDE and network is not None and udelta.is_cuda:
+        if network is not None and udelta.is_cuda:
             eng = network.engine()
             side = None if eng.one_lane else eng.__dict__.get('_streams', {}).get('side')
         if side is None:
@@ -503,11 +493,11 @@ class MemoryManager:
             ol = O.OpList()
             ops_ = dict(clear=[])
             common = dict(HW=HW, HWp=HWp, ranges=ranges, cap=CAND_CAP, frames=E, nq=2, banks=(D('table'), C), prio=prio)
-            ops_['score0'] = ol.aff_score(None, None, None, D('Bhi'), D('Blo'), D('cq'), D('gmax'), None, None, None, mode=0, dma=bool(JOINT_DMA & 1), **common)
+            ops_['score0'] = ol.aff_score(None, None, None, D('Bhi'), D('Blo'), D('cq'), D('gmax'), None, None, None, mode=0, **common)
             ops_['select'] = ol.aff_select(D('gmax'), D('tau'), HW=HW, HWp=HWp, G=G, top_k=m0.top_k, clear_count=D('count'), frames=E,
                                            zero=(D('usage'), 2 * E * nslots) if m0.use_long_term else None, prio=prio)
             ops_['score1'] = ol.aff_score(None, None, None, D('Bhi'), D('Blo'), D('cq'), D('tau'), D('cval'), D('cidx'), D('count'),
-                                          mode=1, gmax_precedes_tau=True, dma=bool(JOINT_DMA & 2), **common)
+                                          mode=1, gmax_precedes_tau=True, **common)
             ol.aff_readout(D('cval'), D('cidx'), D('count'), D('vptrs'), D('usage') if m0.use_long_term else None, D('readout'),
                            D('ovf'), HW=HW, cap=CAND_CAP, top_k=m0.top_k, K=K, CV=m0.CV, frames=E, HWp=HWp, usage_stride=nslots, banks=C, prio=prio, usage_fx=True)
             if clear_long:
@@ -583,7 +573,7 @@ class MemoryManager:
                 pixel_readout = network.pixel_fusion(pix_feat, visual_readout, this_sensory, this_last_mask)
                 a, b = self._rows(objects, self._objv_ids)
                 this_obj_mem = self._objv[a:b].unsqueeze(0).unsqueeze(2)                # [1,K,1,Q,C+1]
-                readout_memory, aux_features = network.readout_query(pixel_readout, this_obj_mem, _last_aux=self.save_aux or _UNFUSED,
+                readout_memory, aux_features = network.readout_query(pixel_readout, this_obj_mem, _last_aux=self.save_aux,
                                                                      _summary_token=(self._objv_token, a, b))
                 for i, obj in enumerate(objects):
                     all_readout[obj] = readout_memory[:, i]
@@ -718,7 +708,7 @@ class MemoryManager:
             region_end = (b.perm_start + b.P) if to_perm else (b.work_start + b.Wc)
             assert slot + HW <= region_end, ('memory bank overrun', slot, HW, region_end)
             ol.key_prep(kphys, sphys, b.Ahi[slot:], b.Alo[slot:], b.scale[slot:], n=HW, query=False)
-            copies, fills = [], []                                      # every tensor of the insertion in one launch (BANK_WRITE)
+            copies, fills = [], []                                      # every tensor of the insertion in one launch
             if self.use_long_term:
                 copies.append((kphys, b.rawkey[slot:], 4 * self.CK * HW))
                 copies.append((sphys, b.rawshr[slot:], 4 * HW))
@@ -729,13 +719,7 @@ class MemoryManager:
             for o in b.objects:
                 if o in objects:
                     copies.append((vphys[objects.index(o)], b.values[o][slot:], 2 * HW * self.CV))
-            if BANK_WRITE:
-                ol.bank_write(copies, fills)
-            else:                                                       # (A/B switch: one launch per tensor, as before)
-                for src, dst, nbytes in copies:
-                    ol.copy2d(src, dst, rows=1, rowbytes=nbytes, src_stride=nbytes, dst_stride=nbytes)
-                for dst, words, pattern in fills:
-                    ol.memset32(dst, words, pattern)
+            ol.bank_write(copies, fills)
         if len(ol):
             ol.run()
 
@@ -822,7 +806,7 @@ class MemoryManager:
         # -- the move is issued as stream-ordered chunks of at most n rows, ascending, so that every chunk's destination ends where its
         # source begins.
         keep = self.min_work_tokens
-        if keep <= n and BANK_WRITE:
+        if keep <= n:
             ol.bank_write([(t[ws + n:], t[ws:], rowbytes * keep) for t, rowbytes in b.arrays()] if keep > 0 else [], fills)
         else:
             ol.bank_write([], fills)

@@ -19,7 +19,7 @@ import torch.nn as nn
 from .. import _lib, frame_context
 from . import plans
 from .param_spec import build_spec
-from .weights import fold_bn, pack_conv, pack_linear, linear_as_conv, out_proj_blob
+from .weights import fold_bn, pack_conv, pack_linear, linear_as_conv
 
 log = logging.getLogger()
 BF16, F32 = torch.bfloat16, torch.float32
@@ -76,7 +76,7 @@ class Engine:
         self._rep = {}
         sd = {k: v.detach().float().cpu() for k, v in sd.items() if v.is_floating_point()}
         self.sd = sd
-        self._pe_w = {}
+        self._pe_wb = {}
         W, dev = self.w, device
         CS, CV = m['sensory_dim'], m['value_dim']
         up = m['mask_decoder']['up_dims']
@@ -135,14 +135,11 @@ class Engine:
             # pixel-side merged projection [k (read_from_pixel) | v (read_from_pixel) | q (read_from_query)]
             wm = torch.cat([Wp[C:2 * C], Wp[2 * C:], Wq[:C]], 0)
             bm = torch.cat([bp[C:2 * C], bp[2 * C:], bq[:C]], 0)
-            W[q + '.pixel_proj'] = linear_as_conv(wm, bm, dev)
             # the same projections applied to the (block-invariant) pixel positional term; v gets none
             wpe = torch.cat([Wp[C:2 * C], torch.zeros(C, C), Wq[:C]], 0)
-            self._pe_w[b] = wpe
-            self._pe_wb = getattr(self, '_pe_wb', {})
             self._pe_wb[b] = wpe.float()
-            # ... or inside the block's own projection (round 4): kvq_b = Wm_b pixel_b + Wpe_b (We x + be + PE) as ONE conv over the virtual
-            # concat [pixel_b | x] with the composed weights [Wm_b | Wpe_b We]; only the PE term is left as a per-pixel residual (pe_rb).
+            # ... composed into the block's own projection (round 4): kvq_b = Wm_b pixel_b + Wpe_b (We x + be + PE) as ONE conv over the
+            # virtual concat [pixel_b | x] with the composed weights [Wm_b | Wpe_b We]; only the PE term is left as a per-pixel residual (pe_rb).
             # Same flops as one conv x -> [R_0 | R_1 | R_2] in front, without writing and re-reading 3 x 768 channels per pixel and object.
             we_ = sd[t + '.pixel_emb_proj.weight'].float().reshape(C, -1)
             W[q + '.pixel_proj_x'] = pack_conv(torch.cat([wm.float(), wpe.float() @ we_], 1).reshape(3 * C, 2 * C, 1, 1),
@@ -153,26 +150,12 @@ class Engine:
             W[q + '.self_attn.out'] = pack_linear(sd[sa + '.out_proj.weight'], sd[sa + '.out_proj.bias'], dev)
             W[q + '.read_from_query.kv'] = pack_linear(Wq[C:], bq[C:], dev)        # [k | v]; the query PE feeds k only
             W[q + '.read_from_query.out'] = linear_as_conv(sd[rq + '.out_proj.weight'], sd[rq + '.out_proj.bias'], dev)
-            if C == 256:
-                W[q + '.read_from_query.out_blob'] = out_proj_blob(W[q + '.read_from_query.out'])       # ATTN_P2Q applies it itself (plans.P2Q_OUT)
             for ln in ('.read_from_pixel.norm', '.self_attn.norm', '.ffn.norm'):
                 W[q + ln + '.weight'] = sd[q + ln + '.weight'].to(dev).contiguous()
                 W[q + ln + '.bias'] = sd[q + ln + '.bias'].to(dev).contiguous()
             W[q + '.ffn.linear1'] = pack_linear(sd[q + '.ffn.linear1.weight'], sd[q + '.ffn.linear1.bias'], dev)
             W[q + '.ffn.linear2'] = pack_linear(sd[q + '.ffn.linear2.weight'], sd[q + '.ffn.linear2.bias'], dev)
-        # the positional term R_b = [Wk_b pe | 0 | Wq2_b pe] of every block depends only on pixel_pe: one conv for all blocks
-        wpe_all = torch.cat([self._pe_w.pop(b) for b in range(ot['num_blocks'])], 0).float()        # [3C*nb, C]
-        self._wpe_all = wpe_all
-        W[t + '.pe_proj_all'] = linear_as_conv(wpe_all, None, dev)
-        # ... and since pixel_pe = pixel_emb_proj(x) + PE is consumed by nothing else, the two 1x1 maps are composed (in fp32, once):
-        # R_all = (Wpe We) x + Wpe be + Wpe PE.  One conv x -> [pixel | R_all]; the PE term is a per-pixel residual (Engine.pe_r)
-        we = sd[t + '.pixel_emb_proj.weight'].float().reshape(C, -1)
-        W[t + '.pixel_init_R'] = pack_conv(torch.cat([sd[t + '.pixel_init_proj.weight'].float(), (wpe_all @ we).reshape(-1, we.shape[1], 1, 1)], 0),
-                                           torch.cat([sd[t + '.pixel_init_proj.bias'].float(), wpe_all @ sd[t + '.pixel_emb_proj.bias'].float()], 0), dev)
         conv(t + '.pixel_init_proj')
-        # pixel_init_proj | pixel_emb_proj read the same input: one conv with 2C output channels
-        W[t + '.pixel_init_emb'] = pack_conv(torch.cat([sd[t + '.pixel_init_proj.weight'], sd[t + '.pixel_emb_proj.weight']], 0),
-                                             torch.cat([sd[t + '.pixel_init_proj.bias'], sd[t + '.pixel_emb_proj.bias']], 0), dev)
         for b in range(ot['num_blocks'] + 1):
             conv(f'{t}.mask_pred.{b}.1')
         for name in ca_blocks:
@@ -182,8 +165,6 @@ class Engine:
         W[t + '.summary_to_query_init'] = pack_linear(sd[t + '.summary_to_query_init.weight'], sd[t + '.summary_to_query_init.bias'], dev)
         W[t + '.summary_to_query_emb'] = pack_linear(sd[t + '.summary_to_query_emb.weight'], sd[t + '.summary_to_query_emb.bias'], dev)
         u = 'object_summarizer'
-        for name in ('.input_proj', '.feature_pred.0', '.feature_pred.2', '.weights_pred.0', '.weights_pred.2'):
-            W[u + name] = linear_as_conv(sd[u + name + '.weight'], sd[u + name + '.bias'], dev)
         # The summarizer's five per-pixel linears as TWO launches (round 5; object_summarizer.py:55-89).  input_proj feeds nothing but the
         # first layers of the two MLPs (feature_pred.0, weights_pred.0), and the positional encoding is added in between, so the maps are
         # composed in fp32: [f1 | w1] = relu(W0 W_in value + W0 (b_in + PE) + b0), W0 = [Wf0 ; Ww0] -- one conv value -> 2C channels with the
@@ -200,31 +181,6 @@ class Engine:
         w2[:wf2.shape[0], :cf] = wf2
         w2[wf2.shape[0]:, cf:] = ww2
         W[u + '.fw2'] = linear_as_conv(w2, torch.cat([sd[u + '.feature_pred.2.bias'].float(), sd[u + '.weights_pred.2.bias'].float()], 0), dev)
-
-    def pe(self, h, w):
-        """bf16 [h*w, C] positional encoding (both PositionalEncoding instances use the same formula)."""
-        if (h, w) not in self._pe:
-            e = plans.positional_encoding(h, w, self.m['embed_dim'], self.m['pixel_pe_scale'], self.m['pixel_pe_temperature'])
-            self._pe[(h, w)] = e.reshape(h * w, -1).to(BF16).to(self.device).contiguous()
-        return self._pe[(h, w)]
-
-    def pe0(self, h, w):
-        """bf16 [h*w, 2C]: [0 | positional encoding] -- the broadcast residual of the merged pixel_init | pixel_emb conv."""
-        key = ('pe0', h, w)
-        if key not in self._pe:
-            e = self.pe(h, w)
-            self._pe[key] = torch.cat([torch.zeros_like(e), e], 1).contiguous()
-        return self._pe[key]
-
-    def pe_r(self, h, w):
-        """bf16 [h*w, C + 3C*blocks]: [0 | Wpe PE] -- the broadcast residual of the composed pixel_init | R_all conv."""
-        key = ('pe_r', h, w)
-        if key not in self._pe:
-            e = plans.positional_encoding(h, w, self.m['embed_dim'], self.m['pixel_pe_scale'], self.m['pixel_pe_temperature'])
-            e = e.reshape(h * w, -1).float()
-            r = e @ self._wpe_all.t()
-            self._pe[key] = torch.cat([torch.zeros_like(e), r], 1).to(BF16).to(self.device).contiguous()
-        return self._pe[key]
 
     def pe_rb(self, h, w, b):
         """bf16 [h*w, 3C]: Wpe_b PE -- the broadcast residual of block b's composed pixel projection (Engine: '.pixel_proj_x')."""
@@ -288,13 +244,12 @@ class Engine:
         if p is None:
             p = builder(self, *args)
             p.ol.finalize()
-            if plans.ARENA:
-                # the image encoder (+ key projection) may run on the look-ahead stream next to everything else: its own arena
-                kind = 'side' if key[0] in ('enc', 'key') else ('win' if key[0] == 'encw' else 'main')     # (the window encoder: a third stream)
-                arenas = self.__dict__.setdefault('_arenas', {})
-                if kind not in arenas:
-                    arenas[kind] = plans.Arena(self.device)
-                p.pack_into(arenas[kind])
+            # the image encoder (+ key projection) may run on the look-ahead stream next to everything else: its own arena
+            kind = 'side' if key[0] in ('enc', 'key') else ('win' if key[0] == 'encw' else 'main')     # (the window encoder: a third stream)
+            arenas = self.__dict__.setdefault('_arenas', {})
+            if kind not in arenas:
+                arenas[kind] = plans.Arena(self.device)
+            p.pack_into(arenas[kind])
             self._plans[key] = p
         return p
 
@@ -601,7 +556,7 @@ class CUTIE(nn.Module):
         # MASK_DOWN(masks) is already there when these masks are the probabilities the last segment() returned (every memory frame of a
         # propagation): its up-sampling launch left them for the next frame's pixel fusion (see segment / pixel_fusion)
         md = frame_context.recall('mask_down', mk)
-        md = md is not None and md == (K, h, w, eng.__dict__.get('_md_gen')) and plans.SUM_FUSED and not plans.UNFUSED
+        md = md is not None and md == (K, h, w, eng.__dict__.get('_md_gen'))
         P = eng.plan(('emask', K, h0, w0, H, W, pl, pt, bool(deep_update), md), plans.build_encode_mask, K, h0, w0, H, W, pl, pt,
                      bool(deep_update), md)
         o = eng.pool.get(('emask', K, h, w, eng.devstr),
@@ -633,7 +588,7 @@ class CUTIE(nn.Module):
         K, h, w = px.shape[:3]
         _, sb = self._sensory_pair(sensory)
         lm = f32c(last_mask[0])
-        xt = None if plans.UNFUSED else frame_context.recall('fuse_xt', pf)             # x_transform(pix_feat), computed with the encoder (None: a caller's own features)
+        xt = frame_context.recall('fuse_xt', pf)             # x_transform(pix_feat), computed with the encoder (None: a caller's own features)
         md = frame_context.recall('mask_down', lm)          # MASK_DOWN(last_mask), left by the segment() that produced this very tensor ...
         md = md is not None and md == (K, h, w, eng.__dict__.get('_md_gen'))      # ... if no later segment() has overwritten it
         P = eng.plan(('fuse', K, h, w, xt is not None, md), plans.build_pixel_fusion, K, h, w, xt is not None, md)
@@ -680,12 +635,12 @@ class CUTIE(nn.Module):
         K, h, w = p16.shape[:3]
         f8, f4 = nhwc_of(ms_image_feat[1]), nhwc_of(ms_image_feat[2])
         sf, sb = self._sensory_pair(sensory)
-        pre = None if plans.UNFUSED else frame_context.recall('decoder_feats', f8)     # decoder_feat_proc(f8, f4), computed with the encoder
+        pre = frame_context.recall('decoder_feats', f8)     # decoder_feat_proc(f8, f4), computed with the encoder
         if pre is not None and pre[2].data_ptr() != f4.data_ptr():
             pre = None                                         # (f8 of one frame with f4 of another: a caller's own mix)
         # (only on the caller's announcement: its contract -- do not modify handed-out tensors between steps -- is what makes the
         # MASK_DOWN computed here valid for the next frame; inference tensors carry no version counter to check it with)
-        md = bool(_fork) and plans.SEG_MD and not plans.UNFUSED and K + 1 <= 8 and dev.type == 'cuda'
+        md = bool(_fork) and K + 1 <= 8 and dev.type == 'cuda'
         P = eng.plan(('seg', K, h, w, bool(update_sensory), pre is not None, md), plans.build_segment, K, h, w, bool(update_sensory), pre is not None, md)
         sp = dict(prob=((K + 1, 16 * h, 16 * w), F32, False))
         if _need_logits:
@@ -695,12 +650,12 @@ class CUTIE(nn.Module):
         feats = dict(f8=f8, f4=f4) if pre is None else dict(f8p=pre[0], f4p=pre[1])
         dyn = dict(p16=p16, sensory_f32=sf, sensory_bf16=sb, prob=prob, logits_up=lup, **feats)
         n_ops, cut = len(P.ol.recs), P.meta.get('logits_done', 0)
-        if _fork and plans.SEG_FORK and not (plans.ONE_LANE or eng.one_lane) and update_sensory and dev.type == 'cuda' and not plans.GRAPHS and 0 < cut < n_ops - 1 and not plans.UNFUSED and K + 1 <= 16:
+        if _fork and not eng.one_lane and update_sensory and dev.type == 'cuda' and not plans.GRAPHS and 0 < cut < n_ops - 1 and K + 1 <= 16:
             # Behind the logits the plan forks: [area pooling, two convs, GRU] update the sensory state, the LAST launch up-samples the
             # logits and takes the softmax.  Neither branch reads what the other writes, and every launch is a serial step of the
             # frame's critical path (~3.4 us of launch boundary on top of its run time): the softmax launch goes to an auxiliary
             # stream of the engine, the caller's stream takes it back in behind the sensory update.  Same launches, same inputs.
-            # Measured in one box (tools/r4_call18.sh): +1.1 % with look-ahead hints, -4 % without them (there the frame is one
+            # Measured in one box (round 4): +1.1 % with look-ahead hints, -4 % without them (there the frame is one
             # stream and the host's extra calls cost more than the overlap returns) -- hence only on the caller's request.
             main = torch.cuda.current_stream(dev)
             st = eng.__dict__.setdefault('_streams', {})

@@ -53,49 +53,14 @@ TUNE_REPS, TUNE_ITERS = (int(v) for v in os.environ.get('CUTIE_AMD_TUNE', '3x8')
 # Timing-based tile selection for conv geometries that are NOT in the tuned table is opt-in ($CUTIE_AMD_AUTOTUNE=1, or
 # Engine.autotune = True): timing is noisy, and a different (tile, split-K) changes the fp32 summation order, so by default such
 # geometries take the deterministic static choice of ops.pick_tile and results are bit-reproducible across processes.
-# diagnostic: $CUTIE_AMD_UNFUSED=1 restores the unfused launch sequences of round 1 for in-box A/B timing (tools/r2_call*.sh)
-UNFUSED = os.environ.get('CUTIE_AMD_UNFUSED', '0') not in ('', '0')
-QCHAIN = os.environ.get('CUTIE_AMD_QCHAIN', '1') not in ('', '0')     # query side of a transformer block in 4 launches (0: the round-2 seven)
 # Plans replayed as HIP graphs once their pointer signature repeats (_lib.HipExecutor.run_cached): opt-in.  Measured on the MI355X
 # (profiles/r03_host.md): 94 % of the plan runs replay, the frame rate does not move (995.8 against 1003.3 fps) -- the look-ahead frame
 # is bound by the two streams sharing the compute units, not by the host's ~650 us of launches.
 GRAPHS = os.environ.get('CUTIE_AMD_GRAPHS', '0') not in ('', '0')
 GRAPH_MIN_OPS = 8
-QFFN_SLICE = int(os.environ.get('CUTIE_AMD_QFFN_SLICE', '64'))       # hidden columns per QFFN block (64 | 128)
-# the decoder's last launch (up-sampling + softmax of the logits) on an auxiliary stream next to the sensory update (4 launches that
-# depend on the logits as well, not on each other's branch): A/B switch
-# positional terms of the transformer's pixel projections composed INTO each block's projection conv ([pixel_b | x] -> k | v | q2) instead
-# of one conv x -> [pixel | R_0 | R_1 | R_2] in front of the blocks (A/B switch)
-PROJ_X = os.environ.get('CUTIE_AMD_PROJ_X', '1') not in ('', '0')
-SEG_FORK = os.environ.get('CUTIE_AMD_SEG_FORK', '1') not in ('', '0')
-# the object summarizer's five per-pixel linears as two composed launches (A/B switch; Engine '.in_fw0' / '.fw2')
-SUM_FUSED = os.environ.get('CUTIE_AMD_SUM_FUSED', '1') not in ('', '0')
-# MASK_DOWN of the next frame's pixel fusion inside the up-sampling launch of the current one (A/B switch)
-SEG_MD = os.environ.get('CUTIE_AMD_SEG_MD', '1') not in ('', '0')
-# read_from_query's output projection + residual inside the ATTN_P2Q launch (csrc/qchain.hip: p2q_out_kernel).  Bit-identical and OFF: the
-# fused launch needs every head of a pixel in one workgroup, i.e. all of Wkv + Wo (384 KB) through ONE compute unit -- 21.6 us against
-# 7.0 + 4.8 us + a boundary for the two launches (frame: -1.8 %; profiles/r04_frame_chain.md section 6)
-P2Q_OUT = os.environ.get('CUTIE_AMD_P2Q_OUT', '0') not in ('', '0')       # (honoured only by the diagnostic library, see build_readout_query)
 QINIT_SKIP = os.environ.get('CUTIE_AMD_QINIT_SKIP', '1') not in ('', '0')   # query initialisation only when the object summaries changed (A/B switch)
-ONE_LANE = os.environ.get('CUTIE_AMD_ONE_LANE', '0') not in ('', '0')   # every look-ahead lane of a clip on the caller's own stream (several clips in flight: see cutie_amd/parallel.py)
-ECA_HEAD = os.environ.get('CUTIE_AMD_ECA_HEAD', '1') not in ('', '0')   # mask_pred of a transformer block inside the ECA launch (A/B switch)
-QNEXT = os.environ.get('CUTIE_AMD_QNEXT', '1') not in ('', '0')       # ATTN_P2Q also projects the next block's ATTN_Q2P queries
 AUTOTUNE = os.environ.get('CUTIE_AMD_AUTOTUNE', '0') not in ('', '0')
-TOUCH_REWIRE = os.environ.get('CUTIE_AMD_WPF_REWIRE', '1') not in ('', '0')       # A/B switch: next-weights ranges recomputed after the tile table
 PACKAGED_TILES = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tiles_gfx950.json')
-
-
-_p2q_warned = []
-
-
-def _p2q_out_available():
-    ex = _lib.get_executor()
-    ok = ex.is_mock or _lib.has_diag_kernels()
-    if not ok and not _p2q_warned:
-        _p2q_warned.append(1)
-        import warnings
-        warnings.warn('CUTIE_AMD_P2Q_OUT=1 needs the diagnostic kernel library (make -C cutie_amd/csrc DIAG=1); ignored')
-    return ok
 
 
 def load_tile_cache():
@@ -134,8 +99,7 @@ def save_tile_cache(cache):
 # layer's output) in HBM.  After a plan is built, its buffers are packed into an arena by live range (first / last launch that touches
 # them, read off the descriptors), and the plans that run one after the other on a stream share ONE arena: the frame then cycles through
 # ~150 MB of addresses and the memory-side cache keeps them (tools/cold_probe.py: a conv whose operands come from HBM costs 2-7 us
-# more than the same launch served from the Infinity Cache).  $CUTIE_AMD_ARENA=0 restores one allocation per buffer.
-ARENA = os.environ.get('CUTIE_AMD_ARENA', '1') not in ('', '0')
+# more than the same launch served from the Infinity Cache).
 ARENA_POISON = os.environ.get('CUTIE_AMD_ARENA_POISON', '0') not in ('', '0')      # tests: garbage in the arena before every run
 ARENA_ALIGN = 256
 
@@ -263,7 +227,7 @@ def weights_go_cold(px16, K=None):
     stride-16 pixels and K objects moves ~0.18 MB x px16 x (1 + K) through HBM (1.2 GB at 480p / 3 objects against 256 MB of Infinity
     Cache).  Small frames: the weights stay warm between two uses and the touch only lengthens every launch.  Large frames: they are
     cold, but a launch runs for 50-300 us and its first K steps are noise against the tail the touch adds.  In between the launches are
-    short AND cold.  Measured in one box each (tools/r3_call44.sh, 47, 48, 49; frames/s without the look-ahead hint, touch on / off):
+    short AND cold.  Measured in one box each (round 3; frames/s without the look-ahead hint, touch on / off):
     240p x 1 object 1270 / 1291, 240p x 3 1185 / 1197, 360p x 2 1025 / 1034, 480p x 1 945 / 943, 480p x 3 771 / 754,
     1080p x 5 191.5 / 193.1.  Plans that do not know K (the image encoder) decide on the pixels alone."""
     return 1400 <= px16 < 4500 if K is None else 4800 <= px16 * (1 + K) < 18000
@@ -448,8 +412,7 @@ class Plan:
                 #  whatever path was taken above -- table entry, static choice kept, a skipped assignment --, the tile this
                 # conv RUNS must sum over K like the one-frame plan's: that is what keeps a frame of the batch bit-identical to it
                 assert O.korder_class(int(arr['i'][n, 17]), int(arr['i'][n, 19])) == want, (key, int(arr['i'][n, 17]), int(arr['i'][n, 19]), want)
-        if TOUCH_REWIRE:
-            ol.wire_next_weights()                           # the touch ranges follow the tiles the table has just put in place
+        ol.wire_next_weights()                               # the touch ranges follow the tiles the table has just put in place
         self.tuned = True
         if tuned_any:
             save_tile_cache(cache)
@@ -485,7 +448,7 @@ class Plan:
         w = self.eng.w[prefix + '.conv2']
         gap = self.buf(name + '.gap', (x.B, x.C), F32)
         HW = x.H * x.W
-        if not UNFUSED and O.conv_side_jobs_ok(cin=x.C, cout=w.cout, kh=w.kh):
+        if O.conv_side_jobs_ok(cin=x.C, cout=w.cout, kh=w.kh):
             # ECA's global average pool rides on the convs: conv1 clears the accumulator, conv2 adds the per-object channel sums of
             # what it stores (fixed point, integer atomics: order-independent), ECA_APPLY turns them into means -- no GAP launch
             sums = self.buf(name + '.gapsum', (x.B, x.C), torch.int64)
@@ -536,13 +499,9 @@ class Plan:
 
 
 # ---------------------------------------------------------------------------------------------------
-STEM = os.environ.get('CUTIE_AMD_STEM', '1') not in ('', '0')
-STEM_BATCH = os.environ.get('CUTIE_AMD_STEM_BATCH', '1') not in ('', '0')     # the frames of an encoder window / the clips of a lock-step group in one STEM launch (A/B switch)
-
-
 def stem_ok(eng, name):
     w = eng.w.get(name)
-    return STEM and not UNFUSED and w is not None and w.cout == 64 and w.kh == 7 and w.kw == 7 and w.cin_padded == 8 and w.bias is not None
+    return w is not None and w.cout == 64 and w.kh == 7 and w.kw == 7 and w.cin_padded == 8 and w.bias is not None
 
 
 def build_encode(eng, h0, w0, H, W, pad_left, pad_top, B=1, qrows=64):
@@ -561,7 +520,7 @@ def build_encode(eng, h0, w0, H, W, pad_left, pad_top, B=1, qrows=64):
     img = (lambda b: Dyn('image')) if B == 1 else (lambda b: Dyn('image%d' % b))
     if stem_ok(eng, 'pixel_encoder.conv1'):                 # IMG_PREP + 7x7 conv + max pool in one launch (csrc/stem.hip)
         pool = P.buf('pool', (B, H // 4, W // 4, 64))
-        SM = O.OpList.STEM_MAX_IMAGES if STEM_BATCH else 1
+        SM = O.OpList.STEM_MAX_IMAGES
         for b0 in range(0, B, SM):                          # the frames of a window in launches of up to 12 (one frame is a partial round of blocks)
             P.ol.stem(img(b0), None, eng.w['pixel_encoder.conv1'], pool[b0:], h0=h0, w0=w0, H=H, W=W, pad_left=pad_left, pad_top=pad_top, K=1,
                       mean=m['pixel_mean'], std=m['pixel_std'], relu=True, more_images=[img(b) for b in range(b0 + 1, min(B, b0 + SM))])
@@ -678,12 +637,12 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
     t = 'object_transformer'
     f = lambda name, shape: P.buf(name, shape, F32)
     query, query_emb = eng.query_bufs(K)                  # (engine-level: the variant with fresh=False reads what the other one wrote)
-    use_chain = QCHAIN and not UNFUSED and C == 256 and Q == 16 and heads == 8 and HW <= 24576 and ot['ff_dim'] % QFFN_SLICE == 0
+    use_chain = C == 256 and Q == 16 and heads == 8 and HW <= 24576 and ot['ff_dim'] % 64 == 0
     assert G == 1 or use_chain, 'clips in lock step need the chain form of the query side'
     # fixed-point accumulators of the query chain (three per block), cleared by the first launch of the plan
     qacc = P.buf('qacc', (3 * nb, M, C), torch.int64) if use_chain else None
     zero_on_conv = None
-    if C == 256 and Q == 16 and not UNFUSED:
+    if C == 256 and Q == 16:
         if fresh or not use_chain:
             ol.query_init2(Dyn('obj_mem'), query, query_emb, rows=M, w_init=W[t + '.summary_to_query_init'], res_init=eng.rep_embedding('query_init', K),
                            w_emb=W[t + '.summary_to_query_emb'], res_emb=eng.rep_embedding('query_emb', K), zero=qacc)
@@ -700,26 +659,10 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
         ol.linear(vals, W[t + '.summary_to_query_init'], query, M=M, res=eng.rep_embedding('query_init', K))
         ol.linear(vals, W[t + '.summary_to_query_emb'], query_emb, M=M, res=eng.rep_embedding('query_emb', K))
     pix_in = Act(Dyn('pixel'), K, h, w, C)
-    if UNFUSED:
-        # pixel = pixel_init_proj(x), pixel_pe = pixel_emb_proj(x) + PE: one conv, two channel slices of its output
-        both = P.conv(t + '.pixel_init_emb', pix_in, name='pixel_init_emb', res=Act(eng.pe0(h, w), 1, h, w, 2 * C), res_bcast=True)
-        pixel = Act(both.t, K, h, w, C, 2 * C)
-        pixel_pe = Act(both.t.view(-1)[C:], K, h, w, C, 2 * C)
-        R_all = P.conv(t + '.pe_proj_all', pixel_pe, name='R_all')               # [Wk.pe | 0 | Wq2.pe] of every block
-        R_of = lambda b: Act(R_all.t.view(-1)[b * 3 * C:], K, h, w, 3 * C, nb * 3 * C)
-    elif PROJ_X:
-        # the positional terms live inside each block's projection (Engine: '.pixel_proj_x'): only pixel = pixel_init_proj(x) here
-        pixel = P.conv(t + '.pixel_init_proj', pix_in, name='pixel_init', zero=zero_on_conv)
-        R_of = None
-    else:
-        # pixel_pe feeds nothing but the positional terms R_b, so its projection is composed with theirs at load time
-        # (Engine: '.pixel_init_R'): ONE conv x -> [pixel | R_0 | R_1 | ...], the PE part of R as a per-pixel broadcast residual
-        CR = C + nb * 3 * C
-        both = P.conv(t + '.pixel_init_R', pix_in, name='pixel_init_R', res=Act(eng.pe_r(h, w), 1, h, w, CR), res_bcast=True, zero=zero_on_conv)
-        pixel = Act(both.t, K, h, w, C, CR)
-        R_of = lambda b: Act(both.t.view(-1)[C + b * 3 * C:], K, h, w, 3 * C, CR)
+    # the positional terms live inside each block's projection (Engine: '.pixel_proj_x'): only pixel = pixel_init_proj(x) here
+    pixel = P.conv(t + '.pixel_init_proj', pix_in, name='pixel_init', zero=zero_on_conv)
     aux = P.buf('aux_logits', (nb + 1, K, HW), F32, persistent=True)      # read by the caller after the run
-    fused_mask = HW <= 24576 and not UNFUSED                      # ATTN_Q2P derives the foreground mask from the logits itself (flags in LDS)
+    fused_mask = HW <= 24576                      # ATTN_Q2P derives the foreground mask from the logits itself (flags in LDS)
     fg = None if fused_mask else P.buf('fg', (K, HW), torch.uint8)
     nfg = None if fused_mask else P.buf('nfg', (K,), torch.int32)
     P.conv(t + '.mask_pred.0.1', pixel, relu_in=True, out_f32=True, out=Act(aux[0], K, h, w, 1))
@@ -730,16 +673,14 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
     for b in range(nb):
         q = f'{t}.blocks.{b}'
         n = f'b{b}.'
-        if R_of is None:                                         # k | v | q2 of the pixels, positional terms included: [pixel_b | x] -> 3C
-            kvq = P.conv(q + '.pixel_proj_x', pixel, x2=pix_in, name=n + 'kvq', res=Act(eng.pe_rb(h, w, b), 1, h, w, 3 * C), res_bcast=True)
-        else:
-            kvq = P.conv(q + '.pixel_proj', pixel, name=n + 'kvq', res=R_of(b))    # k | v | q2 of the pixels
+        # k | v | q2 of the pixels, positional terms included: [pixel_b | x] -> 3C
+        kvq = P.conv(q + '.pixel_proj_x', pixel, x2=pix_in, name=n + 'kvq', res=Act(eng.pe_rb(h, w, b), 1, h, w, 3 * C), res_bcast=True)
         # read_from_pixel (CrossAttention, transformer_layers.py:75-98): residual is the normed x.  Every LayerNorm of the
         # block is fused into the linear that consumes it (the normalised rows are kept where the reference reuses them).
         ln = lambda name: (W[q + name + '.weight'], W[q + name + '.bias'])
         xn = xn_next if xn_next is not None else f(n + 'xn', (M, C))
         xn_next = None
-        fuse_proj = fused_mask and C == 256 and not UNFUSED      # the small projections run inside the attention launches
+        fuse_proj = fused_mask and C == 256      # the small projections run inside the attention launches
         chain = fuse_proj and use_chain
         if chain:
             # The query side of a block in FOUR launches (was seven): each attention launch also applies its output projection, per
@@ -760,27 +701,21 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
                          proj=dict(x=xn, W=W[q + '.self_attn.qkv'], emb=query_emb, ln=ln('.self_attn.norm'), ln_out=y),
                          acc_in=(a1, Wo1.bias), out_proj=(Wo2, a2))
             x2 = f(n + 'x2', (M, C))
-            ol.qffn(y, x2, a3, rows=M, ln=ln('.ffn.norm'), W1=W1, W2=W2, acc_in=(a2, Wo2.bias), hid_slice=QFFN_SLICE)
+            ol.qffn(y, x2, a3, rows=M, ln=ln('.ffn.norm'), W1=W1, W2=W2, acc_in=(a2, Wo2.bias), hid_slice=64)
             x = x2                                                 # + b2 + a3 / 2^32: added by whoever reads x
             prev_acc = (a3, W2.bias)
             next_q = None
-            if b + 1 < nb and QNEXT:
+            if b + 1 < nb:
                 qn = f'{t}.blocks.{b + 1}'
                 q_pre, xn_next = f(f'b{b + 1}.q', (M, C)), f(f'b{b + 1}.xn', (M, C))
                 next_q = dict(ln=(W[qn + '.read_from_pixel.norm.weight'], W[qn + '.read_from_pixel.norm.bias']), W=W[qn + '.read_from_pixel.q'],
                               q_out=q_pre, xn_out=xn_next)
             else:
                 q_pre = None
-            # pixel + out_proj(attention) by the same launch: no 1x1 conv behind it.  The kernel exists in the diagnostic library only (make DIAG=1):
-            # with the product library the switch is ignored, with a warning (it used to fail at launch time in the middle of a frame)
-            fuse_out = P2Q_OUT and pixel.ld == C and pixel.B == K and _p2q_out_available()
-            pf = Act(P.buf(n + 'pf', (K, h, w, C)), K, h, w, C) if fuse_out else None
-            pa = None if fuse_out else P.buf(n + 'pa', (K, h, w, C))
-            ol.attn_p2q(kvq.t.view(-1)[2 * C:], None, None, pf.t if fuse_out else pa, K=K, Q=Q, HW=HW, C=C, heads=heads, ldq=3 * C,
-                        proj=dict(x=x, W=W[q + '.read_from_query.kv'], emb=query_emb), acc_in=prev_acc, next_q=next_q,
-                        out=dict(Wo=W[q + '.read_from_query.out_blob'], res=pixel.t) if fuse_out else None)
+            pa = P.buf(n + 'pa', (K, h, w, C))
+            ol.attn_p2q(kvq.t.view(-1)[2 * C:], None, None, pa, K=K, Q=Q, HW=HW, C=C, heads=heads, ldq=3 * C,
+                        proj=dict(x=x, W=W[q + '.read_from_query.kv'], emb=query_emb), acc_in=prev_acc, next_q=next_q)
         else:
-            pf = None
             att = f(n + 'att', (M, C))
             if fuse_proj:
                 ol.attn_q2p(None, kvq.t, None, None, att, K=K, Q=Q, HW=HW, C=C, heads=heads, ldkv=3 * C, voff=C, logits=aux[b],
@@ -818,12 +753,11 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
                 kv2 = f(n + 'kv2', (M, 2 * C))
                 ol.linear(x, W[q + '.read_from_query.kv'], kv2, M=M, x_add=query_emb, add_rows=M, add_cols=C)
                 ol.attn_p2q(kvq.t.view(-1)[2 * C:], kv2, kv2.view(-1)[C:], pa, K=K, Q=Q, HW=HW, C=C, heads=heads, ldq=3 * C, ldkv=2 * C)
-        if pf is None:
-            pf = P.conv(q + '.read_from_query.out', Act(pa, K, h, w, C), name=n + 'pf', res=pixel)
+        pf = P.conv(q + '.read_from_query.out', Act(pa, K, h, w, C), name=n + 'pf', res=pixel)
         # PixelFFN (transformer_layers.py:121-136)
         last = b == nb - 1
         want_aux = not last or last_aux
-        fuse_head = want_aux and ECA_HEAD and C == 256 and not UNFUSED        # the mask_pred head rides on the block's ECA launch
+        fuse_head = want_aux and C == 256        # the mask_pred head rides on the block's ECA launch
         pixel = P.ca_block(q + '.pixel_ffn.conv', pf, n + 'ffn', out=Act(Dyn('out'), K, h, w, C) if last else None,
                            head=(f'{t}.mask_pred.{b + 1}.1', aux[b + 1]) if fuse_head else None)
         if want_aux and not fuse_head:
@@ -843,7 +777,7 @@ def build_segment(eng, K, h, w, update_sensory, pre=False, md=False, clips=1, ws
     encoder window's output, `wstride` frames apart; dyn out prob f32 [clips, K+1, 16h, 16w]."""
     G, Kc = clips, K
     K = G * Kc
-    assert G == 1 or (pre and Kc + 1 <= 8 and not UNFUSED), 'clips in lock step: image-only decoder convs from the encoder plan, <= 7 objects per clip'
+    assert G == 1 or (pre and Kc + 1 <= 8), 'clips in lock step: image-only decoder convs from the encoder plan, <= 7 objects per clip'
     P = Plan(eng, touch=weights_go_cold(h * w, K))
     if G > 1:
         P.korder_ref = G
@@ -884,7 +818,7 @@ def build_segment(eng, K, h, w, update_sensory, pre=False, md=False, clips=1, ws
         vals = P.conv('mask_decoder.sensory_update.transform', g3, x2=Act(Dyn('sensory_bf16'), K, h, w, CS),
                       out_f32=True, name='gru_vals')
         ol.gru(vals.t, Dyn('sensory_f32'), Dyn('sensory_bf16'), n=K * h * w, C=CS)
-    if Kc + 1 <= 16 and not UNFUSED:              # aggregation recomputed per bilinear tap inside the up-sampling launch
+    if Kc + 1 <= 16:              # aggregation recomputed per bilinear tap inside the up-sampling launch
         # md: the launch also derives what the NEXT frame's pixel fusion needs from these probabilities (MASK_DOWN: the stride-16 means
         # of the object planes and the (mask, others) pairs), into buffers both plans know (Engine.mask_down_bufs)
         ol.up4_softmax(logits, Dyn('prob'), Dyn('logits_up'), P=Kc + 1, h=h4, w=w4, from_logits=True, clips=G,
@@ -918,7 +852,7 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
         pool = P.buf('pool', (K, H // 4, W // 4, 64))
         # ("others" = the other objects of the same clip, one frame per clip: the clips are the FRAMES of one launch -- or a launch per clip)
         iname = lambda c: Dyn('image' if G == 1 else 'image%d' % c)
-        SM = O.OpList.STEM_MAX_IMAGES if STEM_BATCH else 1
+        SM = O.OpList.STEM_MAX_IMAGES
         for c0 in range(0, G, SM):
             ol.stem(iname(c0), masks_of(c0), eng.w['mask_encoder.conv1'], pool[c0 * Kc:], h0=h0, w0=w0, H=H, W=W, pad_left=pad_left, pad_top=pad_top,
                     K=Kc, mean=m['pixel_mean'], std=m['pixel_std'], relu=True, more_images=[iname(c) for c in range(c0 + 1, min(G, c0 + SM))],
@@ -954,20 +888,11 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
         m16 = P.buf('m16', (K, h, w), F32)
         for c in range(G):
             ol.mask_down(masks_of(c), pair[c * Kc:], m16[c * Kc:], K=Kc, H=H, W=W)
-    if SUM_FUSED and not UNFUSED:
-        # two launches instead of five (Engine: '.in_fw0', '.fw2'): value -> [f1 | w1] with the composed weights, then the block-diagonal
-        # second layers -> fp32 [feature | weight logits]
-        fw1 = P.conv('object_summarizer.in_fw0', value, res=Act(eng.pe_sum(h, w), 1, h, w, 2 * CE), res_bcast=True, act=O.ACT_RELU, name='sum.fw1')
-        fw2 = P.conv('object_summarizer.fw2', fw1, out_f32=True, name='sum.fw2')
-        ol.summarize(fw2.t, fw2.t.view(-1)[CE:], m16, Dyn('summ'), K=K, HW=h * w, C=CE, Q=Q, feat_f32=True, ldf=CE + Q, ldw=CE + Q)
-        return P
-    pe = Act(eng.pe(h, w), 1, h, w, CE)
-    v1 = P.conv('object_summarizer.input_proj', value, res=pe, res_bcast=True, name='sum.v1')
-    f1 = P.conv('object_summarizer.feature_pred.0', v1, act=O.ACT_RELU, name='sum.f1')
-    feat = P.conv('object_summarizer.feature_pred.2', f1, name='sum.feat')
-    w1 = P.conv('object_summarizer.weights_pred.0', v1, act=O.ACT_RELU, name='sum.w1')
-    wl = P.conv('object_summarizer.weights_pred.2', w1, out_f32=True, name='sum.wl')
-    ol.summarize(feat.t, wl.t, m16, Dyn('summ'), K=K, HW=h * w, C=CE, Q=Q)
+    # two launches instead of five (Engine: '.in_fw0', '.fw2'): value -> [f1 | w1] with the composed weights, then the block-diagonal
+    # second layers -> fp32 [feature | weight logits]
+    fw1 = P.conv('object_summarizer.in_fw0', value, res=Act(eng.pe_sum(h, w), 1, h, w, 2 * CE), res_bcast=True, act=O.ACT_RELU, name='sum.fw1')
+    fw2 = P.conv('object_summarizer.fw2', fw1, out_f32=True, name='sum.fw2')
+    ol.summarize(fw2.t, fw2.t.view(-1)[CE:], m16, Dyn('summ'), K=K, HW=h * w, C=CE, Q=Q, feat_f32=True, ldf=CE + Q, ldw=CE + Q)
     return P
 
 

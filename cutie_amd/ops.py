@@ -29,14 +29,11 @@ for _n in ('CONV MAXPOOL IMG_PREP UPSAMPLE2X_ADD AREA_DOWN MASK_DOWN GAP ECA_APP
     KIND_NAMES[globals()[_n]] = _n
 
 F_RELU_IN, F_OUT_F32, F_RES_BCAST = 1, 2, 4
-# launches of the frame's critical path raise their waves' issue priority (include/cutie_hip.h CUTIE_F_PRIO; A/B switch)
-PRIO = os.environ.get('CUTIE_AMD_PRIO', '1') not in ('', '0')
+# launches of the frame's critical path raise their waves' issue priority (include/cutie_hip.h CUTIE_F_PRIO)
 F_PRIO, F_AFF_PRIO = 256, 64
-F_PLAIN = 8 if os.environ.get('CUTIE_AMD_COUT1_ROWS', '1') in ('', '0') else 0      # A/B switch of conv_cout1_rows_kernel
 F_TILE_OFF = 128 if os.environ.get('CUTIE_AMD_COUT1_TILE', '1') in ('', '0') else 0  # A/B switch of conv_cout1_tile_kernel
 ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_SQ1 = 0, 1, 2, 3
 ACT_SHIFT = 4
-UP4_SCALAR = 2 if os.environ.get('CUTIE_AMD_UP4_VEC', '1') in ('', '0') else 0       # UP4_SOFTMAX flags&2: one pixel per thread (A/B switch)
 AREA_RT = 8 if os.environ.get('CUTIE_AMD_AREA_R', '1') in ('', '0') else 0          # AREA_DOWN3 flags&8: bodies with a run-time pooling ratio (A/B switch)
 GRU_SCALAR = 1 if os.environ.get('CUTIE_AMD_GRU4', '1') in ('', '0') else 0            # GRU flags&1: one channel per thread (A/B switch)
 KEYPREP_LOOP = 2 if os.environ.get('CUTIE_AMD_KEYPREP_LOOP', '0') not in ('', '0') else 0   # KEY_PREP flags&2: c_j by one lane per row (A/B switch)
@@ -137,7 +134,6 @@ def conv_side_jobs_ok(*, cin, cout, kh, c2=0):
 NUM_CU = 256
 # bytes of the next conv's weights a conv_pc launch touches on its way out (0: off); CUTIE_AMD_WPF overrides
 WEIGHT_PREFETCH = int(os.environ.get('CUTIE_AMD_WPF', str(8 << 20)))
-WEIGHT_PREFETCH_2 = int(os.environ.get('CUTIE_AMD_WPF2', '1'))
 WEIGHT_PREFETCH_BLOCK = int(os.environ.get('CUTIE_AMD_WPF_BLOCK', str(48 << 10)))      # bytes per block (see OpList.finalize)
 
 
@@ -260,7 +256,7 @@ class OpList:
     PRIO_KINDS = frozenset((UPSAMPLE2X_ADD, AREA_DOWN3, ECA_APPLY, GRU, UP4_SOFTMAX, ATTN_Q2P, ATTN_SELF, ATTN_P2Q, QFFN))
 
     def __init__(self, scratch_owner=None, touch_next_weights=True, prio=True):
-        self.prio = prio                     # the launches of this list belong to the frame's critical path (plans.Plan.prio; $CUTIE_AMD_PRIO=0: nobody's do)
+        self.prio = prio                     # the launches of this list belong to the frame's critical path (plans.Plan.prio)
         self.scratch_owner = scratch_owner   # see splitk_scratch
         self.touch_next_weights = touch_next_weights   # see finalize (plans switch it off where weights stay warm between two uses)
         self.recs = []          # (kind, flags, ints, floats, ptrs)
@@ -273,7 +269,7 @@ class OpList:
     # ---- generic ------------------------------------------------------------------
     def add(self, kind, flags=0, ints=(), floats=(), ptrs=()):
         idx = len(self.recs)
-        if kind in self.PRIO_KINDS and self.prio and PRIO:
+        if kind in self.PRIO_KINDS and self.prio:
             flags |= F_PRIO
         pl = []
         for slot, t in enumerate(ptrs):
@@ -322,7 +318,7 @@ class OpList:
                 budget = WEIGHT_PREFETCH_BLOCK * -(-pc_blocks(int(i[17]), int(i[0]), int(i[7]), int(i[8]), int(i[9])) // 8)
                 n1 = min(nxt[1], WEIGHT_PREFETCH, budget)
                 arr['p'][n, 9], arr['i'][n, 22] = nxt[0], n1
-                n2 = min(nxt2[1], WEIGHT_PREFETCH, budget - n1) if (nxt2 is not None and not nxt[2] and WEIGHT_PREFETCH_2) else 0
+                n2 = min(nxt2[1], WEIGHT_PREFETCH, budget - n1) if (nxt2 is not None and not nxt[2]) else 0
                 if n2 > 0:                                   # the next conv cannot do it for its successor
                     arr['p'][n, 10], arr['i'][n, 23] = nxt2[0], n2
             nxt, nxt2 = (int(arr['p'][n, 2]), self.wbytes[n], pc), nxt
@@ -390,8 +386,8 @@ class OpList:
         (include/cutie_hip.h CONV, ABI 4) -- the B objects come in groups, every group adds its own broadcast residual.  gap_acc: int64 [B, Cout] -- the conv adds the per-(object, channel) sums of its stored output
         (fixed point x 2^24) to it (ECA's global average pool without a launch of its own); zero: an int64 tensor cleared by this
         launch (the accumulator of the NEXT conv).  Both need an LDS-DMA tile (the tile choice is restricted accordingly)."""
-        flags = (F_RELU_IN if relu_in else 0) | (F_OUT_F32 if out_f32 else 0) | (F_RES_BCAST if res_bcast else 0) | (act << ACT_SHIFT) | F_PLAIN | F_TILE_OFF | \
-            (F_PRIO if (prio and PRIO) else 0)
+        flags = (F_RELU_IN if relu_in else 0) | (F_OUT_F32 if out_f32 else 0) | (F_RES_BCAST if res_bcast else 0) | (act << ACT_SHIFT) | F_TILE_OFF | \
+            (F_PRIO if prio else 0)
         assert C1 + C2 == w.cin_padded, (C1, C2, w.cin_padded)
         M = B * OH * OW
         side = gap_acc is not None or zero is not None
@@ -492,11 +488,11 @@ class OpList:
         mask_down = (m16 f32 [K, hw16], pair bf16 [K, h16, w16, pitch], pitch): the launch also writes MASK_DOWN(prob[1:], r = 16).
         clips > 1 (clips in lock step, ABI 4; the four-pixel forms): every array holds that many clips, P planes out / P - 1 in each."""
         if mask_down is not None:
-            assert from_logits and not UP4_SCALAR and P <= 8 and h % 4 == 0 and w % 4 == 0
+            assert from_logits and P <= 8 and h % 4 == 0 and w % 4 == 0
             m16, pair, pitch = mask_down
             return self.add(UP4_SOFTMAX, 1 | 4 | UP4_RTK | UP4_LANES, [P, h, w, pitch, clips], [], [agg, prob, logits_up, m16, pair])
-        assert clips == 1 or (from_logits and not UP4_SCALAR and P <= 8)
-        return self.add(UP4_SOFTMAX, (1 | UP4_SCALAR | UP4_RTK) if from_logits else 0, [P, h, w, 0, clips], [], [agg, prob, logits_up])
+        assert clips == 1 or (from_logits and P <= 8)
+        return self.add(UP4_SOFTMAX, (1 | UP4_RTK) if from_logits else 0, [P, h, w, 0, clips], [], [agg, prob, logits_up])
 
     def mask_merge(self, inmask, pred, src, planes, *, h0, w0, H, W, pad_left, pad_top, Knew, Kold, nfloat, float_mode):
         return self.add(MASK_MERGE, 1 if float_mode else 0, [h0, w0, H, W, pad_left, pad_top, Knew, Kold, nfloat], [],
@@ -655,14 +651,11 @@ class OpList:
 
     AFF_CSTRIDE = 32          # ints between the candidate counters of consecutive queries (one cache line each)
 
-    AFF_DMA = int(os.environ.get('CUTIE_AMD_AFF_DMA', '0'))    # 1: the LDS-DMA kernel (aff_score4_kernel) also for 2 sets per wave
-    AFF_NQ = int(os.environ.get('CUTIE_AMD_AFF_NQ', '2'))      # 16-query column sets per wave of AFF_SCORE (1, 2: aff_score_kernel; 4: aff_score4_kernel)
-
     def aff_score(self, Ahi, Alo, scale, Bhi, Blo, c, out, cand_val, cand_idx, count, *, HW, HWp, ranges, cap, mode, gmax_precedes_tau=False, nq=None, dma=None,
                   frames=1, extra_lds_kb=0, prio=False, banks=None):
         """gmax_precedes_tau (mode 1): `out` (= tau) sits right behind the [HWp, Gld] maxima of pass 0 in memory; the kernel then
-        skips every (tile, 16-query set) that cannot hold a candidate.  nq: query column sets per wave (default AFF_NQ; every
-        choice computes the same bits).  frames > 1: the query operands of that many frames, HWp rows each (HW real ones), stacked -- every
+        skips every (tile, 16-query set) that cannot hold a candidate.  nq: 16-query column sets per wave (1, 2 -- the default: aff_score_kernel;
+        4: aff_score4_kernel; every choice computes the same bits); dma: the LDS-DMA kernel (aff_score4_kernel) also for 2 sets per wave.  frames > 1: the query operands of that many frames, HWp rows each (HW real ones), stacked -- every
         per-query array (c, maxima, tau, candidate lists, counters) is then indexed by the stacked row.
         banks = (table, n) (clips in lock step, ABI 4): stacked frame e reads bank e % n -- table: u64 [n, 3] = the (A_hi, A_lo, scale) bases of the
         banks, which share the token ranges (Ahi / Alo / scale are then ignored); needs nq = 2 and HWp % 128 == 0."""
@@ -672,12 +665,12 @@ class OpList:
         ints = [HW, HWp, len(ranges)]
         for r in range(3):
             ints += list(ranges[r]) if r < len(ranges) else [0, 0]
-        ints += [G, cap, mode, self.AFF_NQ if nq is None else nq, 0, int(extra_lds_kb), self.AFF_DMA if dma is None else int(dma)]
+        ints += [G, cap, mode, 2 if nq is None else nq, 0, int(extra_lds_kb), int(bool(dma))]
         if frames > 1:
             ints[1] = frames * HWp
             ints += [HWp]
         ptrs = [Ahi, Alo, scale, Bhi, Blo, c, out, cand_val, cand_idx, count]
-        flags = (1 if (gmax_precedes_tau and mode == 1) else 0) | (F_AFF_PRIO if (prio and PRIO) else 0)
+        flags = (1 if (gmax_precedes_tau and mode == 1) else 0) | (F_AFF_PRIO if prio else 0)
         if banks is not None:
             assert frames > 1 and frames % banks[1] == 0 and ints[12] == 2 and HWp % 128 == 0
             ints += [banks[1]]
@@ -691,17 +684,17 @@ class OpList:
         frames > 1: stacked queries, see aff_score."""
         if zero is not None:
             assert not ticks
-            return self.add(AFF_SELECT, 1 | SELECT_COARSE | (F_AFF_PRIO if (prio and PRIO) else 0), [HW, HWp, G, top_k, zero[1], 0, frames], [], [gmax, tau, clear_count, zero[0], None])
+            return self.add(AFF_SELECT, 1 | SELECT_COARSE | (F_AFF_PRIO if prio else 0), [HW, HWp, G, top_k, zero[1], 0, frames], [], [gmax, tau, clear_count, zero[0], None])
         ticks = list(ticks) + [(None, 0)] * (2 - len(ticks))
         assert len(ticks) == 2
-        return self.add(AFF_SELECT, SELECT_COARSE | (F_AFF_PRIO if (prio and PRIO) else 0), [HW, HWp, G, top_k, ticks[0][1], ticks[1][1], frames], [], [gmax, tau, clear_count, ticks[0][0], ticks[1][0]])
+        return self.add(AFF_SELECT, SELECT_COARSE | (F_AFF_PRIO if prio else 0), [HW, HWp, G, top_k, ticks[0][1], ticks[1][1], frames], [], [gmax, tau, clear_count, ticks[0][0], ticks[1][0]])
 
     def aff_readout(self, cand_val, cand_idx, count, vptrs, usage, y, overflow, *, HW, cap, top_k, K, CV, frames=1, HWp=0, usage_stride=0, prio=False, banks=1, usage_fx=False):
         """frames > 1: stacked queries (HWp rows per frame, see aff_score); frame f's read-out goes to y[f] ([frames, K, HW, CV]) and its
         usage to usage + f * usage_stride counters.  banks > 1: frame f gathers from bank f % banks -- vptrs: u64 [banks, K].
         usage_fx: the usage counters are unsigned 64-bit fixed point (2^-40) instead of f32 -- integer atomics, sums independent of the order of arrival."""
         assert banks == 1 or frames % banks == 0
-        return self.add(AFF_READOUT, (F_AFF_PRIO if (prio and PRIO) else 0) | (1 if usage_fx else 0), [HW, cap, top_k, K, CV, frames, HWp, usage_stride, banks], [], [cand_val, cand_idx, count, vptrs, usage, y, overflow])
+        return self.add(AFF_READOUT, (F_AFF_PRIO if prio else 0) | (1 if usage_fx else 0), [HW, cap, top_k, K, CV, frames, HWp, usage_stride, banks], [], [cand_val, cand_idx, count, vptrs, usage, y, overflow])
 
     def memset32(self, dst, n, value=0):
         return self.add(MEMSET32, 0, [n, value], [], [dst])

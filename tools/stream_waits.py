@@ -8,7 +8,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--window', type=int, default=8)
 ap.add_argument('--lead', type=int, default=2)
 ap.add_argument('--frames', type=int, default=300)
-ap.add_argument('--no-affinity-ahead', action='store_true')
 args = ap.parse_args()
 from cutie_amd.config import default_config
 from cutie_amd.inference import inference_core as IC
@@ -16,8 +15,6 @@ from cutie_amd.model.cutie import CUTIE
 from cutie_amd.utils.synth import SyntheticClip
 from cutie_amd.utils.synth_weights import make_state_dict
 IC.WINDOW, IC.WINDOW_LEAD = args.window, args.lead
-if args.no_affinity_ahead:
-    IC.AHEAD_AFFINITY = False
 cfg = default_config(use_long_term=True)
 net = CUTIE(cfg).cuda().eval(); net.load_weights(make_state_dict(0))
 clip = SyntheticClip(480, 854, 3, 128, seed=1)
@@ -44,7 +41,7 @@ with torch.inference_mode(), torch.cuda.stream(torch.cuda.Stream()):
 frame_ms = np.array([a.elapsed_time(b) for a, b in zip(marks[:-1], marks[1:])])
 waits = {ti: a.elapsed_time(b) for ti, a, b in IC.WAIT_TRACE}
 w = np.array(list(waits.values()))
-print(f'window {args.window} lead {args.lead} affinity ahead {IC.AHEAD_AFFINITY}: {args.frames} frames, wall {wall / args.frames * 1e3:.3f} ms per frame '
+print(f'window {args.window} lead {args.lead}: {args.frames} frames, wall {wall / args.frames * 1e3:.3f} ms per frame '
       f'({args.frames / wall:.1f} fps), host issue {host / args.frames * 1e3:.3f} ms per frame')
 print(f'  frame on the caller\'s stream (event to event): mean {frame_ms.mean():.3f} ms, median {np.median(frame_ms):.3f}, p90 {np.percentile(frame_ms, 90):.3f}')
 print(f'  wait for the look-ahead at the start of a frame: mean {w.mean() * 1e3:.1f} us, median {np.median(w) * 1e3:.1f}, p90 {np.percentile(w, 90) * 1e3:.1f}, max {w.max() * 1e3:.1f} '

@@ -21,14 +21,23 @@ struct ConvParams {
     int res_grp_rows, res_grp_stride;
 };
 #define GAP_FIXED_SCALE 16777216.f
-// GAP side job of the LDS-DMA / producer-consumer convs: every stored VALUE goes to fixed point (2^-20: exact for a bf16 of magnitude 2^-13 .. 2^11,
-// saturating beyond) BEFORE anything is summed -- integer sums depend neither on how a tile groups the rows into fragments and waves nor on the
+// GAP side job of the LDS-DMA / producer-consumer convs: every stored VALUE goes to fixed point (2^-20, to nearest even) BEFORE anything is summed -- integer sums depend neither on how a tile groups the rows into fragments and waves nor on the
 // order in which the blocks' atomics arrive.  (Rounds 3-6 summed a wave's values in fp32 and converted the partial sums: exact almost always -- but
 // one bf16 ulp of a fusion output differed between the 128 x 64 tile of clips in lock step and the 96 x 64 tile of one clip about once per 35 M
 // elements, and the transformer carried it into every pixel of the clip: tools/lockstep_soak.py, tools/lockstep_diverge.py.)  One multiply and one
 // conversion per value (the two-part 2^-24 form cost the pooled convs 6.6 us of 33: profiles/r06_lockstep.md); the accumulator keeps its 2^-24 unit.
+// Range: exact for |v| <= 2^20 -- an object's 8160 pixels of 1080p then sum to at most 2^53 units, 2^57 after the shift
+// into the accumulator; larger magnitudes (infinities included) saturate at +-2^20, NaN counts 0.  |v| < 2^11, the common case, is one
+// multiply and one 32-bit conversion as before (round 6 stopped there: its conversion saturated silently at 2048); the rest splits exactly
+// into the integer part (2^20 units) and a fraction of at most 12 bits, so no 64-bit float conversion is needed.
 #define GAP_ELEM_SHIFT 4                                  // accumulator unit 2^-24 = element unit 2^-20 >> 4
-__device__ __forceinline__ long long conv_gapfx(float v) { return (long long)__float2int_rn(v * 1048576.f); }
+__device__ __forceinline__ long long conv_gapfx(float v) {
+    if (__builtin_expect(fabsf(v) < 2048.f, 1)) return (long long)__float2int_rn(v * 1048576.f);
+    if (v != v) return 0;
+    const float c = fminf(fmaxf(v, -1048576.f), 1048576.f);
+    const float hi = truncf(c);
+    return (long long)(int)hi * 1048576LL + (long long)__float2int_rn((c - hi) * 1048576.f);
+}
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 // 16-B load that is a global_load for sure.  Pointers that went through a select, an array of pointers or pointer

@@ -131,9 +131,11 @@ class MockExecutor:
         out.copy_(y)
         if len(p) > 8 and p[8]:                                         # side job: clear the next conv's GAP accumulator
             view(p[8], I64, (i[21],)).zero_()
-        if len(p) > 7 and p[7]:                                         # GAP accumulation: fixed-point sums of the STORED values
-            stored = out.float().reshape(B, OH * OW, Cout)
-            view(p[7], I64, (B, Cout)).add_(torch.round(stored.double().sum(1) * 16777216.0).to(torch.int64))
+        if len(p) > 7 and p[7]:                                         # GAP accumulation: fixed point of every STORED value, then sums
+            stored = out.float().reshape(B, OH * OW, Cout).double()      # (conv_common.h conv_gapfx: 2^-20 to nearest even, +-2^20 saturate, NaN = 0)
+            q = torch.round(stored.clamp(-1048576.0, 1048576.0) * 1048576.0)
+            q = torch.where(torch.isnan(stored), torch.zeros_like(q), q).to(torch.int64)
+            view(p[7], I64, (B, Cout)).add_(q.sum(1) * 16)
 
     # ---- MAXPOOL --------------------------------------------------------------------
     def _op_2(self, flags, i, f, p):

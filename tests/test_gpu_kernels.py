@@ -11,6 +11,7 @@ import torch
 from cutie_amd import _lib, ops as O
 from cutie_amd.model.weights import pack_conv, pack_linear
 from mock_exec import MockExecutor
+import ref64 as R
 
 pytestmark = pytest.mark.gpu
 BF16, F32 = torch.bfloat16, torch.float32
@@ -78,6 +79,7 @@ CONV_CASES = [
 
 
 def _conv_build(c, tile, splitk=1):
+    """build(dev, g) of a conv case; build.cpu = the host-side operands of its last CPU build (for the float64 reference)."""
     def build(dev, g):
         B, H, W, C1, Cout, k = c['B'], c['H'], c['W'], c['C1'], c['Cout'], c['k']
         C2 = c.get('C2', 0)
@@ -94,14 +96,37 @@ def _conv_build(c, tile, splitk=1):
         ol.conv(x1, pc, y, B=B, H=H, W=W, C1=C1, ldx1=C1, OH=OH, OW=OW, ldy=Cout, stride=stride, pad=pad, x2=x2, C2=C2,
                 ldx2=C2, res=res, ldr=Cout, res_bcast=c.get('res_bcast', False), relu_in=c.get('relu_in', False),
                 act=c.get('act', O.ACT_NONE), out_f32=c.get('out_f32', False), tile=tile, splitk=splitk)
+        if dev == 'cpu':
+            geo = R.ConvGeom(B=B, H=H, W=W, C1=C1, C2=C2, OH=OH, OW=OW, Cout=Cout, KH=k, KW=k, Kpad=pc.kpad, stride=stride, pad=pad,
+                             relu_in=c.get('relu_in', False), out_f32=c.get('out_f32', False), res_bcast=c.get('res_bcast', False),
+                             act=c.get('act', O.ACT_NONE))
+            build.cpu = (geo, x1, x2, pc, res)
         return ol, {'y': y}
     return build
 
 
+_REF64 = {}
+
+
+def check_ref64(build, hip_y, name):
+    """The HIP output against the float64 reference of the same host-side operands, element by element (tests/ref64.py bound).  The
+    reference of a (case, seed) is computed once (on the device's float64 units) and shared by every tile that runs it."""
+    geo, x1, x2, pc, res = build.cpu
+    key = (tuple(getattr(geo, k) for k in geo.__slots__),) + tuple(None if t is None else float(t.double().sum()) for t in (x1, x2, pc.weight, pc.bias, res))
+    if key not in _REF64:
+        cu = lambda t: None if t is None else t.cuda()
+        y64, bound = R.conv_ref64(geo, x1.cuda(), pc.weight.cuda(), x2=cu(x2), bias=cu(pc.bias), res=cu(res))
+        _REF64[key] = (y64.cpu(), bound.cpu())
+    y64, bound = _REF64[key]
+    R.check_bound(hip_y.reshape(geo.M, geo.Cout), y64, bound, name + ' vs float64')
+
+
 @pytest.mark.parametrize('ci', range(len(CONV_CASES)))
 def test_conv_auto_tile(ci):
-    hip, ref = run_both(_conv_build(CONV_CASES[ci], None), seed=ci)
+    b = _conv_build(CONV_CASES[ci], None)
+    hip, ref = run_both(b, seed=ci)
     check(hip, ref, f'conv[{ci}]')
+    check_ref64(b, hip['y'], f'conv[{ci}]')
 
 
 def _k_tiles(c, tile):
@@ -117,8 +142,10 @@ def test_conv_every_tile(ci, tile):
         pytest.skip('BK > 32 needs Cin >= 32')
     if _k_tiles(c, tile) % O.TILE_WK.get(tile, 1):
         pytest.skip('the K groups of this tile do not divide the K tiles')
-    hip, ref = run_both(_conv_build(c, tile), seed=100 + ci)
+    b = _conv_build(c, tile)
+    hip, ref = run_both(b, seed=100 + ci)
     check(hip, ref, f'conv[{ci}] tile{tile}')
+    check_ref64(b, hip['y'], f'conv[{ci}] tile{tile}')
 
 
 LAYER_CASES = [
@@ -156,8 +183,10 @@ def test_conv_dma_tiles(ci, tile):
     if not O.dma_tile_ok(tile, cin=c['C1'] + c.get('C2', 0), kh=c['k'], c2=c.get('C2', 0)):
         assert O.DMA_TILES[tile][2] == 128
         pytest.skip('128-channel K tile: sources are not multiples of 128')
-    hip, ref = run_both(_conv_build(c, tile), seed=400 + ci)
+    b = _conv_build(c, tile)
+    hip, ref = run_both(b, seed=400 + ci)
     check(hip, ref, f'dma[{ci}] tile{tile}')
+    check_ref64(b, hip['y'], f'dma[{ci}] tile{tile}')
 
 
 NARROW_CASES = [            # 3x3 / stride 1 / pad 1 on narrow maps (written for the strip-resident kernel of round 2; kept as cases of the halo tiles)
@@ -188,8 +217,10 @@ def test_conv_pc_tiles(ci, tile):
     c = PC_CASES[ci]
     if not O.pc_tile_ok(tile, cin=c['C1'] + c.get('C2', 0), kh=c['k'], stride=c.get('stride', 1), pad=c.get('pad', (c['k'] - 1) // 2), c2=c.get('C2', 0)):
         pytest.skip('halo tiles: 3x3 / stride 1 / pad 1 only')
-    hip, ref = run_both(_conv_build(c, tile), seed=1100 + ci)
+    b = _conv_build(c, tile)
+    hip, ref = run_both(b, seed=1100 + ci)
     check(hip, ref, f'pc conv[{ci}] tile{tile}')
+    check_ref64(b, hip['y'], f'pc conv[{ci}] tile{tile}')
 
 
 @pytest.mark.parametrize('splitk', [2, 3, 4, 9])
@@ -205,8 +236,10 @@ def test_conv_split_k(ci, tile, splitk):
         pytest.skip('the slice count must divide the K tiles')
     if splitk * c['B'] * c['H'] * c['W'] * ((c['Cout'] + 7) & ~7) > O.SPLITK_PART_FLOATS:
         pytest.skip('partials exceed the scratch')
-    hip, ref = run_both(_conv_build(c, tile, splitk), seed=500 + ci)
+    b = _conv_build(c, tile, splitk)
+    hip, ref = run_both(b, seed=500 + ci)
     check(hip, ref, f'conv[{ci}] tile{tile} splitk{splitk}')
+    check_ref64(b, hip['y'], f'conv[{ci}] tile{tile} splitk{splitk}')
 
 
 def test_conv_split_k_repeatable():
@@ -236,8 +269,10 @@ def test_conv_split_k_rejects_bad_factor():
 
 @pytest.mark.parametrize('ci', [8, 9])
 def test_conv_cout1_kernel(ci):
-    hip, ref = run_both(_conv_build(CONV_CASES[ci], O.COUT1_TILE), seed=300 + ci)
+    b = _conv_build(CONV_CASES[ci], O.COUT1_TILE)
+    hip, ref = run_both(b, seed=300 + ci)
     check(hip, ref, f'conv cout1 [{ci}]')
+    check_ref64(b, hip['y'], f'conv cout1 [{ci}]')
 
 
 ROWS_CASES = [CONV_CASES[15], CONV_CASES[16],
@@ -249,8 +284,10 @@ ROWS_CASES = [CONV_CASES[15], CONV_CASES[16],
 def test_conv_cout1_rows_kernel(ci):
     """Cout = 1, 3x3 on maps of >= 4096 pixels: conv_cout1_rows_kernel (a thread walks 4 output rows of a column) against the
     interpreter: ragged rows and columns, 8 / 16 / 32 lanes per pixel, ReLU on the input, every output form."""
-    hip, ref = run_both(_conv_build(ROWS_CASES[ci], O.COUT1_TILE), seed=700 + ci)
+    b = _conv_build(ROWS_CASES[ci], O.COUT1_TILE)
+    hip, ref = run_both(b, seed=700 + ci)
     check(hip, ref, f'conv cout1 rows [{ci}]')
+    check_ref64(b, hip['y'], f'conv cout1 rows [{ci}]')
 
 
 @pytest.mark.parametrize('ci', [0, 2])
@@ -274,8 +311,10 @@ def test_conv_cout1_tile_kernel_matches_rows_kernel(ci, monkeypatch):
 
 def test_conv_cout1_1x1_relu_in():
     c = dict(B=3, H=30, W=54, C1=256, Cout=1, k=1, relu_in=True, out_f32=True)
-    hip, ref = run_both(_conv_build(c, O.COUT1_TILE), seed=9)
+    b = _conv_build(c, O.COUT1_TILE)
+    hip, ref = run_both(b, seed=9)
     check(hip, ref, 'conv cout1 1x1')
+    check_ref64(b, hip['y'], 'conv cout1 1x1')
 
 
 def test_conv_strided_channel_slices():
@@ -463,6 +502,57 @@ def test_conv_gap_accumulation(tile, geo):
     check({k: hip[k] for k in ('t2', 'gap', 'y')}, {k: ref[k] for k in ('t2', 'gap', 'y')}, f'conv gap tile{tile}')
     exact = torch.round(hip['t2'].float().reshape(B, H * W, C).double() * 1048576.0).to(torch.int64).sum(1) * 16
     assert torch.equal(hip['sums'].cpu(), exact.cpu()), 'sums of the stored tensor: %d of %d accumulators differ' % (int((hip['sums'].cpu() != exact.cpu()).sum()), exact.numel())
+
+
+GAP_LARGE_TILES = [61, 66, 68, 82, 86, 100, 103, 108, 110, 142, 144, 120, 122, 129, 134, 146]
+
+
+@pytest.mark.parametrize('tile', GAP_LARGE_TILES)
+@pytest.mark.parametrize('beyond', [False, True])
+def test_conv_gap_large_values(tile, beyond):
+    """GAP side job on stored outputs far from 1: a residual of randn x 2^12 puts them in [2048, 2^20] (the round-6 conversion saturated
+    at 2048 and dropped NaN silently); beyond=True adds values past 2^20, infinities and NaNs, which the fixed point pins (DESIGN.md
+    section 5: +-2^20 saturate, NaN counts 0).  Tiles of every family that carries the side job (LDS-DMA, producer / consumer stream and
+    halo, pair steps).  The accumulator equals the per-value fixed point of the kernel's own stored values (and the interpreter's of
+    its own); in range, its mean is within 2^-21 (+ one fp32 rounding) of the float64 mean."""
+    B, H, W, C = 3, 30, 54, 256
+    HW = H * W
+
+    def build(dev, g):
+        w = torch.randn(C, C, 3, 3, generator=g) / math.sqrt(C * 9)
+        pc = pack_conv(w, torch.randn(C, generator=g) * 0.1, dev, segs=[(C, C)])
+        x = rnd(g, (B, H, W, C), dev=dev)
+        res = torch.randn((B, H, W, C), generator=g) * 4096
+        if beyond:
+            res[0, :4, :, :8] = 3e6
+            res[1, 5, 7, :16] = -5e7
+            res[2, 0, 0, 0] = float('inf')
+            res[2, 1, 1, 3] = float('-inf')
+            res[2, 2, 2, 5] = float('nan')
+            res[1, 3, 3, 9] = float('nan')
+        res = res.to(BF16).to(dev)
+        y = torch.zeros((B, H, W, C), dtype=BF16, device=dev)
+        sums = torch.full((B, C), 777, dtype=torch.int64, device=dev)
+        ol = O.OpList()
+        ol.conv(x, pc, y, B=B, H=H, W=W, C1=C, ldx1=C, OH=H, OW=W, ldy=C, pad=1, tile=tile,
+                res=res, ldr=C, zero=sums)
+        ol.conv(x, pc, y, B=B, H=H, W=W, C1=C, ldx1=C, OH=H, OW=W, ldy=C, pad=1, tile=tile, res=res, ldr=C, gap_acc=sums)
+        return ol, {'y': y, 'sums': sums}
+    hip, ref = run_both(build, seed=37)
+    st = hip['y'].float().reshape(B, HW, C)
+    exact = R.gap_fixed(st).sum(1) * 16
+    assert torch.equal(hip['sums'], exact), 'tile %d: %d of %d accumulators differ from the fixed point of the stored values' % (
+        tile, int((hip['sums'] != exact).sum()), exact.numel())
+    assert torch.equal(ref['sums'], R.gap_fixed(ref['y'].float().reshape(B, HW, C)).sum(1) * 16), 'the interpreter rounds per value too'
+    big = st.abs()
+    assert float(big[torch.isfinite(big)].max()) >= 2048
+    if not beyond:
+        assert bool(torch.isfinite(st).all()) and float(big.max()) <= 2 ** 20
+        mean = st.double().mean(1)
+        got = hip['sums'].double() * 2.0 ** -24 / HW
+        assert bool(((got - mean).abs() <= 2.0 ** -21 + 2.0 ** -24 * mean.abs()).all())
+    else:
+        assert bool(torch.isnan(st).any()) and float(big[torch.isfinite(big)].max()) > 2 ** 20
 
 
 @pytest.mark.parametrize('tile', [100, 103, 105, 110, 120, 123, 131, 134])

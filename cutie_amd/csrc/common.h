@@ -86,4 +86,5 @@ int launch_stem(const cutie_op* op, hipStream_t s);          // stem.hip: IMG_PR
 int launch_qchain(const cutie_op* op, hipStream_t s);        // qchain.hip: attention ops with flags 4 / 8, QFFN
 int launch_affinity(const cutie_op* op, hipStream_t s);      // affinity.hip
 int launch_bank(const cutie_op* op, hipStream_t s);          // bank.hip
+int launch_resize_ingest(const cutie_op* op, hipStream_t s); // ingest.hip: RESIZE with flags&2 / flags&4 (ABI 5)
 void cutie_set_error(const char* fmt, ...);

@@ -4,7 +4,7 @@ first-mask alignment, ``end`` on the last frame, FPS = frames / sum of device-ev
 
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
-        [--model small] [--flip-aug] [--save-scores]      (multi-scale testing: one run per --size with --save-scores, then
+        [--model small] [--flip-aug] [--save-scores] [--ingest device]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
 
 With several GPUs launch it under torch.distributed.run: videos are sharded over the ranks (cutie_amd/parallel.py)."""
@@ -19,7 +19,9 @@ from typing import Dict
 import torch
 
 from .config import default_config
+from .inference.data.device_ingest import to_device
 from .inference.data.prefetch import ReadAhead
+from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
 from .inference.utils.results_utils import ResultSaver, make_zip
@@ -29,8 +31,10 @@ log = logging.getLogger()
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4) -> Dict:
-    """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step)."""
+                  read_workers=4, ingest=None) -> Dict:
+    """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
+    ingest: 'host' | 'device' (VideoReader(ingest=...); default: the reader's own mode)."""
+    _check_ingest(ingest)
     processor = InferenceCore(network, cfg=cfg)
     saver = ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=processor.object_manager,
                         use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
@@ -41,7 +45,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     n = len(vid_reader)
     total, frames, first_mask_loaded = 0.0, 0, False
     try:
-        loader = iter(ReadAhead(vid_reader, workers=read_workers))      # decode runs ahead on threads (eval_vos.py:92)
+        loader = iter(_read_ahead(vid_reader, read_workers, ingest))   # decode runs ahead on threads (eval_vos.py:92)
         # the frames of the following steps, already on the device: step(next_images=...) runs the image encoder over a window of them
         # (InferenceCore.prefetch_window); the SAME tensors are handed to the later steps (the look-ahead matches frames by storage)
         from .inference import inference_core as IC
@@ -53,8 +57,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
                 d = next(loader, None)
                 if d is None:
                     break
-                d['rgb'] = d['rgb'].to(dev)
-                ahead.append(d)
+                ahead.append(to_device(d, dev))
 
         fill()
         for ti in range(n):
@@ -93,21 +96,36 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     return {'frames': frames, 'seconds': total}
 
 
+def _check_ingest(ingest):
+    if ingest is not None and ingest not in INGEST_MODES:
+        raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
+
+
+def _read_ahead(vid_reader, workers, ingest):
+    """ReadAhead over the reader's records in the given ingest mode (None: the reader's own)."""
+    if ingest is None:
+        return ReadAhead(vid_reader, workers=workers)
+    return ReadAhead(vid_reader, workers=workers, getitem=lambda i: vid_reader.get(i, ingest=ingest))
+
+
 def lockstep_key(vid_reader):
     """What the videos of a lock-step group must share (cutie_amd/inference/lockstep.py): frame size as the model sees it, the number of
     objects of the first mask, the mask schedule.  None: the video cannot join a group (no mask on its first frame)."""
     d0 = vid_reader[0]
     if d0.get('mask') is None:
         return None
-    return (tuple(d0['rgb'].shape[-2:]), int(len(d0['valid_labels'])), bool(vid_reader.use_all_mask))
+    hw = d0['rgb'].shape[-2:] if 'rgb' in d0 else d0['info']['rgb_shape']      # a device-ingest record: the shape it will have
+    return (tuple(int(v) for v in hw), int(len(d0['valid_labels'])), bool(vid_reader.use_all_mask))
 
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
-                            visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4) -> Dict[int, Dict]:
+                            visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
+                            ingest=None) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
     (the seconds of a lock-step frame are split evenly over its videos)."""
+    _check_ingest(ingest)
     from .inference import inference_core as IC
     from .inference.lockstep import LockstepCores
     from . import frame_context
@@ -137,7 +155,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
         return out, time.perf_counter() - t0
 
     try:
-        loaders = [iter(ReadAhead(rd, workers=read_workers)) for rd in vid_readers]
+        loaders = [iter(_read_ahead(rd, read_workers, ingest)) for rd in vid_readers]
         ahead = [deque() for _ in range(C)]
 
         def fill(c):
@@ -145,8 +163,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
                 d = next(loaders[c], None)
                 if d is None:
                     break
-                d['rgb'] = d['rgb'].to(dev)
-                ahead[c].append(d)
+                ahead[c].append(to_device(d, dev))
 
         for c in range(C):
             fill(c)
@@ -212,6 +229,8 @@ def main():
     ap.add_argument('--flip-aug', action='store_true')
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--save-scores', action='store_true')
+    ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES),
+                    help="device: upload the decoded uint8 frames, ToTensor + antialiased resize on the GPU (cutie_amd/inference/data/device_ingest.py)")
     args = ap.parse_args()
     from .model.cutie import CUTIE
     from .parallel import run_concurrent, shard_clips
@@ -224,7 +243,8 @@ def main():
     net = CUTIE(cfg).cuda().eval()
     if args.weights:
         net.load_weights(torch.load(args.weights, map_location='cpu'))
-    meta = VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=args.size, subset=args.subset)
+    meta = VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=args.size, subset=args.subset,
+                          ingest=args.ingest)
     readers = list(meta.get_datasets())
     mine = shard_clips(len(readers), rank, world)
     mask_root = path.join(args.output, 'Annotations')

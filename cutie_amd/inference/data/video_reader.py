@@ -42,6 +42,15 @@ def _decode_rgb(img_path: str):
     return torch.from_numpy(arr).permute(2, 0, 1).float().div_(255.0), (img.height, img.width)
 
 
+def _decode_rgb_u8(img_path: str):
+    """-> (uint8 [h, w, 3] as decoded, (h, w)): the device-ingest form (cutie_amd/inference/data/device_ingest.py finishes it)."""
+    img = Image.open(img_path).convert('RGB')
+    return np.array(img, dtype=np.uint8), (img.height, img.width)
+
+
+INGEST_MODES = ('host', 'device')
+
+
 def _decode_mask(mask_path: str, long_ids: bool, size: Optional[int]):
     """-> int64 [h, w] object ids; ``size``: nearest-neighbour resize of the shorter side first."""
     m = Image.open(mask_path)
@@ -59,7 +68,14 @@ def _decode_mask(mask_path: str, long_ids: bool, size: Optional[int]):
 class VideoReader(torch.utils.data.Dataset):
     def __init__(self, vid_name: str, image_dir: str, mask_dir: str, *, size: int = -1, to_save: Optional[List[str]] = None,
                  use_all_masks: bool = False, size_dir: Optional[str] = None, start: int = -1, end: int = -1,
-                 reverse: bool = False, object_name: str = None, enabled_frame_list: Optional[List[str]] = None):
+                 reverse: bool = False, object_name: str = None, enabled_frame_list: Optional[List[str]] = None,
+                 ingest: str = 'host'):
+        """ingest='host': records carry ``rgb`` = f32 [3, h, w] (ToTensor + antialiased resize here).  'device': the record carries
+        the decoded ``rgb_u8`` (uint8 [H, W, 3]) and ``info['rgb_shape']`` = (h, w) instead; device_ingest.to_device makes ``rgb``
+        from them on the GPU (one uint8 upload + one RESIZE launch), equal to the host record."""
+        if ingest not in INGEST_MODES:
+            raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
+        self.ingest = ingest
         # caller-visible attributes (names as in the reference)
         self.vid_name, self.object_name = vid_name, object_name
         self.image_dir, self.mask_dir = image_dir, mask_dir
@@ -85,26 +101,37 @@ class VideoReader(torch.utils.data.Dataset):
         return self.use_all_mask or _stem(frame) == _stem(self.first_mask_frame)
 
     def __getitem__(self, idx):
+        return self.get(idx)
+
+    def get(self, idx, ingest: Optional[str] = None):
+        """The record of frame ``idx``; ``ingest`` (default: the reader's own mode) picks its form (see __init__)."""
+        ingest = self.ingest if ingest is None else ingest
+        if ingest not in INGEST_MODES:
+            raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
         frame = self.frames[idx]
         im_path = os.path.join(self.image_dir, frame)
-        rgb, in_hw = _decode_rgb(im_path)
+        on_device = ingest == 'device'
+        rgb, in_hw = (_decode_rgb_u8 if on_device else _decode_rgb)(im_path)
         if self.size_dir == self.image_dir:
             out_hw = in_hw
         else:
             ref = Image.open(os.path.join(self.size_dir, frame))
             out_hw = (ref.height, ref.width)
         shrink = in_hw != out_hw or (self.size > 0 and min(in_hw) > self.size)
-        if shrink:
-            rgb = F.interpolate(rgb[None], size=_shorter_side_to(*in_hw, self.size), mode='bilinear', align_corners=False, antialias=True)[0]
+        rgb_hw = _shorter_side_to(*in_hw, self.size) if shrink else in_hw
+        if shrink and not on_device:
+            rgb = F.interpolate(rgb[None], size=rgb_hw, mode='bilinear', align_corners=False, antialias=True)[0]
         data = {}
         mask_path = os.path.join(self.mask_dir, _stem(frame) + '.png')
         if self._wants_mask(frame) and os.path.exists(mask_path):
             ids = _decode_mask(mask_path, self.use_long_id, self.size if shrink else None)
             present = torch.unique(ids)
             data['mask'], data['valid_labels'] = ids, present[present != 0]
-        data['rgb'] = rgb
+        data['rgb_u8' if on_device else 'rgb'] = rgb
         data['info'] = {'frame': frame, 'save': self.to_save is None or _stem(frame) in self.to_save, 'shape': out_hw,
                         'resize_needed': shrink, 'time_index': self._time_index[frame], 'path_to_image': im_path}
+        if on_device:
+            data['info']['rgb_shape'] = tuple(rgb_hw)
         return data
 
     def get_palette(self):

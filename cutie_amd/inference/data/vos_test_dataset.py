@@ -4,7 +4,7 @@ import json
 import os
 from typing import Dict, Iterable, List, Optional
 
-from .video_reader import VideoReader
+from .video_reader import INGEST_MODES, VideoReader
 
 
 def _video_names(mask_dir: str, subset: Optional[str]) -> List[str]:
@@ -26,8 +26,11 @@ def _required_frames(meta_json: Optional[str], videos: List[str]) -> Dict[str, L
 
 class VOSTestDataset:
     def __init__(self, image_dir: str, mask_dir: str, *, use_all_masks: bool, req_frames_json: Optional[str] = None,
-                 size: int = -1, size_dir: Optional[str] = None, subset: Optional[str] = None):
+                 size: int = -1, size_dir: Optional[str] = None, subset: Optional[str] = None, ingest: str = 'host'):
         self.image_dir, self.mask_dir, self.size_dir = image_dir, mask_dir, size_dir
+        if ingest not in INGEST_MODES:
+            raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
+        self.ingest = ingest                                # VideoReader(ingest=...): 'host' | 'device'
         self.use_all_masks, self.size = use_all_masks, size
         self.vid_list = _video_names(mask_dir, subset)
         self.req_frame_list = _required_frames(req_frames_json, self.vid_list)
@@ -35,7 +38,7 @@ class VOSTestDataset:
     def reader(self, video: str) -> VideoReader:
         sub = lambda root: os.path.join(root, video)       # noqa: E731
         return VideoReader(video, sub(self.image_dir), sub(self.mask_dir), size=self.size, use_all_masks=self.use_all_masks,
-                           to_save=self.req_frame_list.get(video), size_dir=None if self.size_dir is None else sub(self.size_dir))
+                           to_save=self.req_frame_list.get(video), size_dir=None if self.size_dir is None else sub(self.size_dir), ingest=self.ingest)
 
     def get_datasets(self) -> Iterable[VideoReader]:
         return (self.reader(v) for v in self.vid_list)

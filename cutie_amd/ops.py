@@ -235,6 +235,54 @@ def pick_tile(M, cout, cin=64, geom=None):
     return best
 
 
+def aa_taps(n_in, n_out):
+    """Tap ranges and weights of F.interpolate(mode='bilinear', align_corners=False, antialias=True) along one axis, rounded as
+    torch's CPU kernel rounds them (aten/src/ATen/native/cpu/UpSampleKernel.cpp, _compute_weights_aa for float input): scale and
+    support in fp32, center = fp32(scale * (i + 0.5)), the tap bounds truncate fp32(center -+ support) + 0.5 evaluated in fp64,
+    each weight is filter(fp32((fp32(j - center) + 0.5) * invscale)) with the fp64 product, the sum and the normalisation in fp32.
+    An axis whose size does not change is the identity (torch skips that pass).  -> (first int64 [n_out], count int64 [n_out],
+    weights f32 [n_out, K])."""
+    f32 = np.float32
+    i = np.arange(n_out)
+    if n_in == n_out:
+        return i, np.ones(n_out, dtype=np.int64), np.ones((n_out, 1), dtype=f32)
+    scale = f32(n_in) / f32(n_out)
+    support = scale if scale >= 1 else f32(1.0)
+    invscale = f32(1.0 / np.float64(scale)) if scale >= 1 else f32(1.0)
+    max_taps = int(np.ceil(support)) * 2 + 1
+    center = (np.float64(scale) * (i + 0.5)).astype(f32)
+    first = np.maximum(((center - support).astype(np.float64) + 0.5).astype(np.int64), 0)
+    count = np.minimum(((center + support).astype(np.float64) + 0.5).astype(np.int64), n_in) - first
+    count = np.clip(count, 0, max_taps)
+    j = np.arange(max_taps)
+    pos = (first[:, None] + j[None, :]).astype(f32)
+    arg = (((pos - center[:, None]).astype(np.float64) + 0.5) * np.float64(invscale)).astype(f32)
+    arg = np.abs(arg)
+    w = np.where(arg < 1, f32(1.0) - arg, f32(0.0)).astype(f32)
+    w[j[None, :] >= count[:, None]] = 0
+    total = np.zeros(n_out, dtype=f32)
+    for k in range(max_taps):                                   # fp32, ascending taps
+        total = (total + w[:, k]).astype(f32)
+    nz = total != 0
+    w[nz] = (w[nz] / total[nz, None]).astype(f32)
+    return first, count, w
+
+
+def resize_aa_table(H, W, OH, OW):
+    """The tap table of an antialiased RESIZE (p2): int32 [OW + OH, K + 2], row = (first tap, tap count, K fp32 weights as bits);
+    rows 0..OW-1 the horizontal pass, then OH rows of the vertical pass."""
+    parts = [aa_taps(W, OW), aa_taps(H, OH)]
+    K = max(int(w.shape[1]) for _, _, w in parts)
+    tab = np.zeros((OW + OH, K + 2), dtype=np.int32)
+    r = 0
+    for first, count, w in parts:
+        n = len(first)
+        tab[r:r + n, 0], tab[r:r + n, 1] = first, count
+        tab[r:r + n, 2:2 + w.shape[1]] = w.view(np.int32)
+        r += n
+    return tab
+
+
 class Dyn:
     """A named, per-call patched pointer (optionally with a byte offset)."""
     __slots__ = ('name', 'offset')
@@ -768,8 +816,21 @@ class OpList:
         code = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}[out.dtype]
         return self.add(PROB_TO_ID, code, [P, H, W, plane, ldrow], [], [prob, lut, out])
 
-    def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False):
-        return self.add(RESIZE, 1 if nearest else 0, [C, H, W, OH, OW, plane, ldrow], [], [src, dst])
+    def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
+        """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32
+        [OW + OH, K + 2]), scratch = f32 [C, H, OW].  src_u8: src is u8 [H, W, C] with row stride `ldrow` bytes (ToTensor on the fly;
+        without antialias OH == H, OW == W).  include/cutie_hip.h (ABI 5)."""
+        if nearest and (antialias or src_u8):
+            raise ValueError('resize: nearest excludes antialias / src_u8')
+        flags = (1 if nearest else 0) | (2 if antialias else 0) | (4 if src_u8 else 0)
+        ints = [C, H, W, OH, OW, plane, ldrow]
+        ptrs = [src, dst]
+        if antialias:
+            if taps is None or scratch is None:
+                raise ValueError('resize(antialias=True) needs taps= and scratch=')
+            ints.append(taps.shape[1] - 2)
+            ptrs += [taps, scratch]
+        return self.add(RESIZE, flags, ints, [], ptrs)
 
     def flip_w(self, src, dst, *, rows, W, slds=None, dlds=None, alpha=1.0, beta=0.0):
         return self.add(FLIP_W, 0, [rows, W, W if slds is None else slds, W if dlds is None else dlds], [alpha, beta], [src, dst])

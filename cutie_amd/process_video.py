@@ -13,7 +13,10 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
 (long-term memory on, mem_every 10, max_internal_size 480).
 
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
-        [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small]"""
+        [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device]
+
+``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
+cutie_amd/inference/data/device_ingest.py).  Any resize to max_internal_size stays InferenceCore's own."""
 import os
 from argparse import ArgumentParser
 from os import path
@@ -24,7 +27,9 @@ import torch
 from PIL import Image
 
 from .config import default_config
+from .inference.data.device_ingest import frame_to_device
 from .inference.data.prefetch import ReadAhead
+from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
 from .inference.utils.results_utils import ResultSaver
 
@@ -39,10 +44,12 @@ def video_config(**overrides):
 
 
 class FrameSource:
-    """Random access + sequential reading of frames as float [3,H,W] in [0,1] (gui/interactive_utils.py:11-15)."""
+    """Random access + sequential reading of frames as float [3,H,W] in [0,1] (gui/interactive_utils.py:11-15), or with
+    ``u8=True`` as the decoded uint8 [H,W,3] arrays (device ingest)."""
 
-    def __init__(self, video: str):
+    def __init__(self, video: str, *, u8: bool = False):
         self.cap = None
+        self.u8 = u8
         if path.isdir(video):
             self.names = sorted(n for n in os.listdir(video) if n.lower().endswith(IMAGE_EXT))
             self.root = video
@@ -72,6 +79,8 @@ class FrameSource:
             if arr is None:
                 return None
             arr = arr[:, :, ::-1].copy()                          # BGR -> RGB
+        if self.u8:
+            return arr
         return torch.from_numpy(arr).permute(2, 0, 1).float() / 255
 
     def __iter__(self) -> Iterator[torch.Tensor]:
@@ -113,9 +122,12 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 
 
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
-                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True) -> Dict:
+                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host') -> Dict:
+    if ingest not in INGEST_MODES:
+        raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
-    src = FrameSource(video)
+    src = FrameSource(video, u8=(ingest == 'device'))
+    upload = (lambda f: frame_to_device(f, dev)) if ingest == 'device' else (lambda f: f.to(dev))
     mask_names = sorted(n for n in os.listdir(mask_dir) if n.lower().endswith('.png'))
     if not mask_names:
         raise RuntimeError('No mask frames found!')
@@ -146,7 +158,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             frame = src.read(int(name[:-4]))
             if frame is None:
                 break
-            processor.step(frame.to(dev), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
+            processor.step(upload(frame), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
                            force_permanent=True)
         # 2. the whole video
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
@@ -155,10 +167,10 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         try:
             it = iter(src)
             nxt = next(it, None)
-            nxt = nxt.to(dev) if nxt is not None else None
+            nxt = upload(nxt) if nxt is not None else None
             while nxt is not None:
                 frame, nxt = nxt, next(it, None)
-                nxt = nxt.to(dev) if nxt is not None else None
+                nxt = upload(nxt) if nxt is not None else None
                 name = f'{n:07d}.png'
                 mask = one_hot_planes(index_mask(name), num_objects, dev) if path.exists(path.join(mask_dir, name)) else None
                 if on_gpu:
@@ -192,6 +204,7 @@ def main():
     ap.add_argument('--max_internal_size', type=int, default=480)
     ap.add_argument('--mem_cleanup_ratio', type=float, default=-1)
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
+    ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU')
     args = ap.parse_args()
     from .model.cutie import CUTIE
     cfg = video_config(model=args.model, mem_every=args.mem_every, max_internal_size=args.max_internal_size)
@@ -201,7 +214,7 @@ def main():
     else:
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
-                      mem_cleanup_ratio=args.mem_cleanup_ratio)
+                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest)
     print(f'Total processing time: {r["seconds"]}\nTotal processed frames: {r["frames"]}\n'
           f'FPS: {r["frames"] / max(r["seconds"], 1e-9)}\nMax allocated memory (MB): {torch.cuda.max_memory_allocated() / 2 ** 20}')
 

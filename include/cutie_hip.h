@@ -311,7 +311,18 @@ enum {
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
-     * p0=src f32 (C planes of H x W, plane stride i5, row stride i6) p1=dst f32 [C,OH,OW]   i: 0 C 1 H 2 W 3 OH 4 OW 5 6 */
+     * p0=src f32 (C planes of H x W, plane stride i5, row stride i6) p1=dst f32 [C,OH,OW]   i: 0 C 1 H 2 W 3 OH 4 OW 5 6
+     * ABI 5 -- frame ingest (video_reader.py:42-46,97-98: ToTensor + Resize of the dataset frames; cutie_amd/inference/data/device_ingest.py),
+     *    kernels in ingest.hip; flags&1 together with flags&2 or flags&4 is an error:
+     *  flags&2: antialiased bilinear, F.interpolate(mode='bilinear', align_corners=False, antialias=True) = torch's separable triangle filter
+     *    (_upsample_bilinear2d_aa): horizontal pass into the scratch, then vertical pass, taps summed in ascending order in fp32.
+     *    The tap table is computed on the HOST, once per geometry, and passed in (cutie_amd/ops.py aa_taps / resize_aa_table: it rounds
+     *    center, support and weights exactly as torch's CPU kernel does for float input, so the tap ranges and weights are torch's):
+     *    p2 = int32 [OW + OH][i7 + 2]: row = first tap, tap count, i7 fp32 weights (as bits); rows 0..OW-1 the horizontal pass, then OH rows
+     *    of the vertical pass (an axis whose size does not change is one tap of weight 1).  p3 = f32 scratch [C, H, OW].  i7 = taps per row.
+     *    dst and scratch 16-byte aligned.
+     *  flags&4: p0 = u8 [H, W, C] interleaved (what PIL / numpy decode), row stride i6 BYTES (>= W*C), pixel stride C (i5 ignored); every
+     *    value becomes v / 255.0f correctly rounded = u8.float().div_(255.0), bit for bit.  Without flags&2: ToTensor alone, OH == H, OW == W. */
     CUTIE_OP_RESIZE = 37,
     /* FLIP_W: dst = f0 * flip_last_dim(src) + f1 * dst   -- torch.flip(x, dims=[-1]) of the flip_aug path and the averaging
      * of the two passes (inference_core.py:162-165,234-235,303-305).  src and dst must not overlap.

@@ -1,0 +1,139 @@
+"""Device ingest probe (profiles/ingest_probe.md): what the host pays per frame in each ingest mode, and what the GPU pays.
+
+    python tools/ingest_probe.py cpu [--frames 24]            # host ms/frame of VideoReader[i], 'host' vs 'device', inline and ReadAhead(4)
+    python tools/ingest_probe.py gpu [--frames 40]            # RESIZE flags 4 / 6 us per frame (events), eval_vos wall-clock frames/s
+    [--out FILE.md]                                           # also append the markdown table to FILE
+
+Synthetic JPEG folders (smooth random content, quality 90) are generated in a temporary directory.  The eval_vos numbers are
+WALL-CLOCK around process_video / process_videos_lockstep (synchronised), not the driver's own step time, which excludes ingest."""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+from PIL import Image
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+
+SIZES = {'480p': (480, 854, -1), '720p': (720, 1280, 480), '1080p': (1080, 1920, 480)}
+
+
+def make_video(root, name, n, h, w, seed, ids=(1, 2)):
+    from cutie_amd.inference.utils.results_utils import davis_palette
+    rng = np.random.default_rng(seed)
+    os.makedirs(os.path.join(root, 'JPEGImages', name)); os.makedirs(os.path.join(root, 'Annotations', name))
+    base = rng.integers(0, 256, (h // 16 + 1, w // 16 + 1, 3), dtype=np.uint8)
+    for t in range(n):
+        small = np.roll(base, t, axis=1)
+        Image.fromarray(small).resize((w, h), Image.BILINEAR).save(os.path.join(root, 'JPEGImages', name, f'{t:05d}.jpg'), quality=90)
+    m = np.zeros((h, w), dtype=np.uint8)
+    for k, oid in enumerate(ids):
+        m[h // 4 * k + h // 8: h // 4 * k + h // 4, w // 4: w // 2 + k * w // 8] = oid
+    png = Image.fromarray(m)
+    png.putpalette(davis_palette)
+    png.save(os.path.join(root, 'Annotations', name, '00000.png'))
+
+
+def cpu_part(frames):
+    from cutie_amd.inference.data.prefetch import ReadAhead
+    from cutie_amd.inference.data.video_reader import VideoReader
+    rows = ['| source | size | mode | inline ms/frame | ReadAhead(4) ms/frame |', '|---|---|---|---|---|']
+    ratios = {}
+    with tempfile.TemporaryDirectory() as root:
+        for tag, (h, w, size) in SIZES.items():
+            make_video(root, tag, frames, h, w, seed=1)
+            res = {}
+            for mode in ('host', 'device'):
+                rd = VideoReader(tag, os.path.join(root, 'JPEGImages', tag), os.path.join(root, 'Annotations', tag), size=size, ingest=mode)
+                rd[0]
+                t0 = time.perf_counter()
+                for i in range(len(rd)):
+                    rd[i]
+                inline = (time.perf_counter() - t0) / len(rd) * 1e3
+                t0 = time.perf_counter()
+                for _ in ReadAhead(rd, workers=4):
+                    pass
+                ahead = (time.perf_counter() - t0) / len(rd) * 1e3
+                res[mode] = (inline, ahead)
+                rows.append(f'| {w}x{h} | {size} | {mode} | {inline:.2f} | {ahead:.2f} |')
+            ratios[tag] = (res['device'][0] / res['host'][0], res['device'][1] / res['host'][1])
+    rows.append('')
+    rows.append('device / host: ' + ', '.join(f'{k} {a:.2f} inline, {b:.2f} read-ahead' for k, (a, b) in ratios.items()))
+    return rows
+
+
+def gpu_part(frames):
+    from cutie_amd import ops as O
+    from cutie_amd.config import default_config
+    from cutie_amd.eval_vos import process_video, process_videos_lockstep
+    from cutie_amd.inference.data.vos_test_dataset import VOSTestDataset
+    from cutie_amd.model.cutie import CUTIE
+    from oracle.weights import make_state_dict
+    rows = ['| kernel | geometry | us per frame (events, 200 launches) |', '|---|---|---|']
+    for (H, W, OH, OW) in ((1080, 1920, 480, 853), (720, 1280, 480, 853), (480, 854, 480, 854)):
+        src = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device='cuda')
+        dst = torch.empty((3, OH, OW), device='cuda')
+        ol = O.OpList(prio=False)
+        if (H, W) == (OH, OW):
+            ol.resize(src, dst, C=3, H=H, W=W, OH=OH, OW=OW, plane=0, ldrow=W * 3, src_u8=True)
+        else:
+            ol.resize(src, dst, C=3, H=H, W=W, OH=OH, OW=OW, plane=0, ldrow=W * 3, src_u8=True, antialias=True,
+                      taps=torch.from_numpy(O.resize_aa_table(H, W, OH, OW)).cuda(), scratch=torch.empty((3, H, OW), device='cuda'))
+        ol.finalize()
+        for _ in range(20):
+            ol.run()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(200):
+            ol.run()
+        e1.record()
+        torch.cuda.synchronize()
+        rows.append(f'| RESIZE flags {int(ol.arr["flags"][0])} | {W}x{H} -> {OW}x{OH} | {e0.elapsed_time(e1) / 200 * 1e3:.1f} |')
+    rows += ['', '| eval_vos (1280x720, --size 480, 4 videos) | ingest | frames | wall s | wall frames/s | step-only frames/s |',
+             '|---|---|---|---|---|---|']
+    net = CUTIE(default_config()).cuda().eval()
+    net.load_weights(make_state_dict(seed=0))
+    cfg = default_config()
+    with tempfile.TemporaryDirectory() as root:
+        for v in range(4):
+            make_video(root, f'v{v}', frames, 720, 1280, seed=10 + v)
+        for lockstep in (1, 4):
+            for mode in ('host', 'device', 'host', 'device'):             # each mode twice: the first pass warms plans and allocator
+                ds = VOSTestDataset(os.path.join(root, 'JPEGImages'), os.path.join(root, 'Annotations'), use_all_masks=False, size=480, ingest=mode)
+                rds = list(ds.get_datasets())
+                out = os.path.join(root, f'out_{mode}_{lockstep}')
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                with torch.inference_mode():
+                    if lockstep == 1:
+                        st = [process_video(net, cfg, rd, out) for rd in rds]
+                    else:
+                        st = list(process_videos_lockstep(net, cfg, rds, out).values())
+                torch.cuda.synchronize()
+                wall = time.perf_counter() - t0
+                n = sum(s['frames'] for s in st)
+                step = sum(s['seconds'] for s in st)
+                rows.append(f'| --lockstep {lockstep} | {mode} | {n} | {wall:.2f} | {n / wall:.0f} | {n / max(step, 1e-9):.0f} |')
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('part', choices=['cpu', 'gpu'])
+    ap.add_argument('--frames', type=int, default=None)
+    ap.add_argument('--out')
+    a = ap.parse_args()
+    rows = cpu_part(a.frames or 24) if a.part == 'cpu' else gpu_part(a.frames or 40)
+    text = '\n'.join(rows) + '\n'
+    print(text)
+    if a.out:
+        with open(a.out, 'a') as f:
+            f.write(text + '\n')
+
+
+if __name__ == '__main__':
+    main()

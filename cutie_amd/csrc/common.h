@@ -87,4 +87,5 @@ int launch_qchain(const cutie_op* op, hipStream_t s);        // qchain.hip: atte
 int launch_affinity(const cutie_op* op, hipStream_t s);      // affinity.hip
 int launch_bank(const cutie_op* op, hipStream_t s);          // bank.hip
 int launch_resize_ingest(const cutie_op* op, hipStream_t s); // ingest.hip: RESIZE with flags&2 / flags&4 (ABI 5)
+int launch_jpeg(const cutie_op* op, hipStream_t s);          // jpeg.hip: RESIZE with flags&8 / 16 / 32 (ABI 6)
 void cutie_set_error(const char* fmt, ...);

@@ -1434,6 +1434,7 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
                                op->f[0], op->f[1]);
             break;
         case CUTIE_OP_RESIZE: {
+            if (op->flags & 56) return launch_jpeg(op, s);                  // JPEG decode stages: jpeg.hip
             if (op->flags & 6) return launch_resize_ingest(op, s);          // antialias / u8 source: ingest.hip
             const long n = (long)i[0] * i[3] * i[4];
             if (i[1] < 1 || i[2] < 1 || i[3] < 1 || i[4] < 1) { cutie_set_error("resize: empty shape"); return -2; }

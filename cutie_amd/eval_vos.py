@@ -4,7 +4,7 @@ first-mask alignment, ``end`` on the last frame, FPS = frames / sum of device-ev
 
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
-        [--model small] [--flip-aug] [--save-scores] [--ingest device]      (multi-scale testing: one run per --size with --save-scores, then
+        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
 
 With several GPUs launch it under torch.distributed.run: videos are sharded over the ranks (cutie_amd/parallel.py)."""
@@ -19,7 +19,7 @@ from typing import Dict
 import torch
 
 from .config import default_config
-from .inference.data.device_ingest import to_device
+from .inference.data.device_ingest import finish, to_device
 from .inference.data.prefetch import ReadAhead
 from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
@@ -33,7 +33,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                   read_workers=4, ingest=None) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
-    ingest: 'host' | 'device' (VideoReader(ingest=...); default: the reader's own mode)."""
+    ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode)."""
     _check_ingest(ingest)
     processor = InferenceCore(network, cfg=cfg)
     saver = ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=processor.object_manager,
@@ -57,11 +57,11 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
                 d = next(loader, None)
                 if d is None:
                     break
-                ahead.append(to_device(d, dev))
+                ahead.append(to_device(d, dev, defer_check=True))      # (checked when it leaves the window)
 
         fill()
         for ti in range(n):
-            data = ahead.popleft()
+            data = finish(ahead.popleft())
             fill()
             image = data['rgb']
             next_images = [d['rgb'] for d in ahead] if (lookahead and ahead) else None
@@ -163,12 +163,12 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
                 d = next(loaders[c], None)
                 if d is None:
                     break
-                ahead[c].append(to_device(d, dev))
+                ahead[c].append(to_device(d, dev, defer_check=True))
 
         for c in range(C):
             fill(c)
         for ti in range(T):
-            data = [ahead[c].popleft() for c in range(C)]
+            data = [finish(ahead[c].popleft()) for c in range(C)]
             for c in range(C):
                 fill(c)
             masks = [d['mask'].to(dev) if d.get('mask') is not None else None for d in data]
@@ -192,7 +192,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
             core = ls.cores[c]
             with frame_context.context(ls._ctx[c]):
                 for ti in range(T, lens[c]):
-                    d = ahead[c].popleft()
+                    d = finish(ahead[c].popleft())
                     fill(c)
                     nxt = [x['rgb'] for x in ahead[c]] if (lookahead and ahead[c]) else None
                     mask = d['mask'].to(dev) if d.get('mask') is not None else None
@@ -230,7 +230,8 @@ def main():
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--save-scores', action='store_true')
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES),
-                    help="device: upload the decoded uint8 frames, ToTensor + antialiased resize on the GPU (cutie_amd/inference/data/device_ingest.py)")
+                    help="device: upload the decoded uint8 frames, ToTensor + antialiased resize on the GPU (cutie_amd/inference/data/device_ingest.py); "
+                         "device-decode: upload the JPEG bytes and decode them on the GPU as well (baseline JPEG; other frames as 'device')")
     args = ap.parse_args()
     from .model.cutie import CUTIE
     from .parallel import run_concurrent, shard_clips

@@ -7,12 +7,16 @@ with numpy / torch.nn.functional (identical arithmetic: F.interpolate(..., antia
 Structure (ours): the frame list, the mask format and the two decoders are separate helpers; ``__getitem__`` only assembles the
 record.  Behaviour is pinned by recordings of the executed reference class (tests/golden/io, tests/test_io_fixtures_cpu.py)."""
 import os
+import threading
+from collections import Counter
 from typing import List, Optional
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 from PIL import Image
+
+from . import jpeg
 
 # PIL mode of the first mask -> (ids are 24-bit RGB triples, the palette is kept)
 _MASK_FORMATS = {'P': (False, True), 'RGB': (True, False), 'L': (False, False)}
@@ -48,7 +52,7 @@ def _decode_rgb_u8(img_path: str):
     return np.array(img, dtype=np.uint8), (img.height, img.width)
 
 
-INGEST_MODES = ('host', 'device')
+INGEST_MODES = ('host', 'device', 'device-decode')
 
 
 def _decode_mask(mask_path: str, long_ids: bool, size: Optional[int]):
@@ -72,10 +76,14 @@ class VideoReader(torch.utils.data.Dataset):
                  ingest: str = 'host'):
         """ingest='host': records carry ``rgb`` = f32 [3, h, w] (ToTensor + antialiased resize here).  'device': the record carries
         the decoded ``rgb_u8`` (uint8 [H, W, 3]) and ``info['rgb_shape']`` = (h, w) instead; device_ingest.to_device makes ``rgb``
-        from them on the GPU (one uint8 upload + one RESIZE launch), equal to the host record."""
+        from them on the GPU (one uint8 upload + one RESIZE launch), equal to the host record.  'device-decode': the record carries
+        the parsed JPEG (``jpeg``, inference/data/jpeg.py Packet) instead, decoded on the GPU by device_ingest.to_device into the
+        same ``rgb``; a frame the GPU decoder does not take gets the 'device' record, counted by reason in ``decode_fallbacks``."""
         if ingest not in INGEST_MODES:
             raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
         self.ingest = ingest
+        self.decode_fallbacks = Counter()                            # 'device-decode': frames decoded on the host, by reason
+        self._fallback_lock = threading.Lock()                       # (records are read on several threads)
         # caller-visible attributes (names as in the reference)
         self.vid_name, self.object_name = vid_name, object_name
         self.image_dir, self.mask_dir = image_dir, mask_dir
@@ -110,8 +118,17 @@ class VideoReader(torch.utils.data.Dataset):
             raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
         frame = self.frames[idx]
         im_path = os.path.join(self.image_dir, frame)
-        on_device = ingest == 'device'
-        rgb, in_hw = (_decode_rgb_u8 if on_device else _decode_rgb)(im_path)
+        on_device = ingest != 'host'
+        pkt = None
+        if ingest == 'device-decode':
+            pkt, why = jpeg.parse_file(im_path)
+            if pkt is None:
+                with self._fallback_lock:
+                    self.decode_fallbacks[why] += 1
+        if pkt is not None:
+            rgb, in_hw = None, pkt.shape
+        else:
+            rgb, in_hw = (_decode_rgb_u8 if on_device else _decode_rgb)(im_path)
         if self.size_dir == self.image_dir:
             out_hw = in_hw
         else:
@@ -127,7 +144,10 @@ class VideoReader(torch.utils.data.Dataset):
             ids = _decode_mask(mask_path, self.use_long_id, self.size if shrink else None)
             present = torch.unique(ids)
             data['mask'], data['valid_labels'] = ids, present[present != 0]
-        data['rgb_u8' if on_device else 'rgb'] = rgb
+        if pkt is not None:
+            data['jpeg'] = pkt
+        else:
+            data['rgb_u8' if on_device else 'rgb'] = rgb
         data['info'] = {'frame': frame, 'save': self.to_save is None or _stem(frame) in self.to_save, 'shape': out_hw,
                         'resize_needed': shrink, 'time_index': self._time_index[frame], 'path_to_image': im_path}
         if on_device:

@@ -30,7 +30,7 @@ class VOSTestDataset:
         self.image_dir, self.mask_dir, self.size_dir = image_dir, mask_dir, size_dir
         if ingest not in INGEST_MODES:
             raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
-        self.ingest = ingest                                # VideoReader(ingest=...): 'host' | 'device'
+        self.ingest = ingest                                # VideoReader(ingest=...): 'host' | 'device' | 'device-decode'
         self.use_all_masks, self.size = use_all_masks, size
         self.vid_list = _video_names(mask_dir, subset)
         self.req_frame_list = _required_frames(req_frames_json, self.vid_list)

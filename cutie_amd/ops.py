@@ -299,6 +299,9 @@ def _ptr(t):
     return t.data_ptr()
 
 
+JPEG_SYNC_ROUNDS = 4        # sync rounds of the speculative Huffman decode before a segment is finished serially (jpeg.hip)
+
+
 class OpList:
     # kinds whose kernels raise their waves' issue priority under F_PRIO (include/cutie_hip.h); CONV and the affinity ops carry a `prio` argument
     PRIO_KINDS = frozenset((UPSAMPLE2X_ADD, AREA_DOWN3, ECA_APPLY, GRU, UP4_SOFTMAX, ATTN_Q2P, ATTN_SELF, ATTN_P2Q, QFFN))
@@ -831,6 +834,29 @@ class OpList:
             ints.append(taps.shape[1] - 2)
             ptrs += [taps, scratch]
         return self.add(RESIZE, flags, ints, [], ptrs)
+
+    def _jpeg(self, flag, pkt, *, work=None, coef=None, status=None, planes=None, rgb=None, rounds=JPEG_SYNC_ROUNDS):
+        """RESIZE flags 8 / 16 / 32 (include/cutie_hip.h, ABI 6): one stage of the JPEG decode of `pkt` (inference/data/jpeg.py
+        Packet; its uint8 buffer on the device is `pkt_dev`) -- the geometry comes from the packet header."""
+        from .inference.data import jpeg as J
+        host, dev = pkt
+        h = host.hdr
+        ints = [h[J.HDR_NCHUNK], h[J.HDR_NSEG], h[J.HDR_NBLOCK], h[J.HDR_CHUNK_BITS], rounds, host.buf.nbytes, h[J.HDR_PLANE_BYTES],
+                h[J.HDR_H], h[J.HDR_W], 0 if work is None else work.numel(), h[J.HDR_NCOMP], 3 * int(h[J.HDR_W])]
+        return self.add(RESIZE, flag, ints, [], [dev, work, coef, status, planes, rgb])
+
+    def jpeg_huff(self, pkt, *, work, coef, status, rounds=JPEG_SYNC_ROUNDS):
+        """Stage 1: entropy decode -> coef int16 [nblock, 64] (natural order, quantised, absolute DC).  pkt = (Packet, device uint8
+        copy of Packet.buf); work int32 >= jpeg.work_words(...), status int32 [4] (error bits, sync rounds, serial segments)."""
+        return self._jpeg(8, pkt, work=work, coef=coef, status=status, rounds=rounds)
+
+    def jpeg_idct(self, pkt, *, coef, planes):
+        """Stage 2: ISLOW IDCT -> planes uint8 (every component, whole blocks)."""
+        return self._jpeg(16, pkt, coef=coef, planes=planes)
+
+    def jpeg_color(self, pkt, *, planes, rgb):
+        """Stage 3: fancy upsampling + YCbCr -> RGB -> rgb uint8 [H, W, 3] packed."""
+        return self._jpeg(32, pkt, planes=planes, rgb=rgb)
 
     def flip_w(self, src, dst, *, rows, W, slds=None, dlds=None, alpha=1.0, beta=0.0):
         return self.add(FLIP_W, 0, [rows, W, W if slds is None else slds, W if dlds is None else dlds], [alpha, beta], [src, dst])

@@ -16,8 +16,11 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device]
 
 ``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
-cutie_amd/inference/data/device_ingest.py).  Any resize to max_internal_size stays InferenceCore's own."""
+cutie_amd/inference/data/device_ingest.py).  ``--ingest device-decode``: JPEG frames of a directory are parsed on the host and
+decoded on the GPU (the other frames as with ``device``).  Any resize to max_internal_size stays InferenceCore's own."""
 import os
+import threading
+from collections import Counter
 from argparse import ArgumentParser
 from os import path
 from typing import Callable, Dict, Iterator, Optional, Tuple
@@ -27,7 +30,8 @@ import torch
 from PIL import Image
 
 from .config import default_config
-from .inference.data.device_ingest import frame_to_device
+from .inference.data import jpeg
+from .inference.data.device_ingest import frame_to_device, jpeg_to_device
 from .inference.data.prefetch import ReadAhead
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
@@ -45,11 +49,15 @@ def video_config(**overrides):
 
 class FrameSource:
     """Random access + sequential reading of frames as float [3,H,W] in [0,1] (gui/interactive_utils.py:11-15), or with
-    ``u8=True`` as the decoded uint8 [H,W,3] arrays (device ingest)."""
+    ``u8=True`` as the decoded uint8 [H,W,3] arrays (device ingest), with ``packets=True`` JPEG files of a directory as parsed
+    packets (inference/data/jpeg.py; the others as uint8 arrays, counted by reason in ``decode_fallbacks``)."""
 
-    def __init__(self, video: str, *, u8: bool = False):
+    def __init__(self, video: str, *, u8: bool = False, packets: bool = False):
         self.cap = None
-        self.u8 = u8
+        self.u8 = u8 or packets
+        self.packets = packets
+        self.decode_fallbacks = Counter()
+        self._lock = threading.Lock()
         if path.isdir(video):
             self.names = sorted(n for n in os.listdir(video) if n.lower().endswith(IMAGE_EXT))
             self.root = video
@@ -72,6 +80,12 @@ class FrameSource:
         if self.cap is None:
             if not 0 <= index < self.count:
                 return None
+            if self.packets:
+                pkt, why = jpeg.parse_file(path.join(self.root, self.names[index]))
+                if pkt is not None:
+                    return pkt
+                with self._lock:
+                    self.decode_fallbacks[why] += 1
             arr = np.array(Image.open(path.join(self.root, self.names[index])).convert('RGB'))
         else:
             self.cap.set(self.cv2.CAP_PROP_POS_FRAMES, index)
@@ -126,8 +140,19 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
-    src = FrameSource(video, u8=(ingest == 'device'))
-    upload = (lambda f: frame_to_device(f, dev)) if ingest == 'device' else (lambda f: f.to(dev))
+    src = FrameSource(video, u8=(ingest == 'device'), packets=(ingest == 'device-decode'))
+
+    def upload(f):
+        """-> (frame on the device, its deferred decode check or None)"""
+        if isinstance(f, jpeg.Packet):
+            return jpeg_to_device(f, dev, check=False)              # (a bad frame raises, naming its file, when it is checked)
+        return (f.to(dev) if ingest == 'host' else frame_to_device(f, dev)), None
+
+    def checked(pair):
+        frame, chk = pair
+        if chk is not None:
+            chk()
+        return frame
     mask_names = sorted(n for n in os.listdir(mask_dir) if n.lower().endswith('.png'))
     if not mask_names:
         raise RuntimeError('No mask frames found!')
@@ -158,7 +183,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             frame = src.read(int(name[:-4]))
             if frame is None:
                 break
-            processor.step(upload(frame), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
+            processor.step(checked(upload(frame)), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
                            force_permanent=True)
         # 2. the whole video
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
@@ -169,7 +194,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             nxt = next(it, None)
             nxt = upload(nxt) if nxt is not None else None
             while nxt is not None:
-                frame, nxt = nxt, next(it, None)
+                frame, nxt = checked(nxt), next(it, None)
                 nxt = upload(nxt) if nxt is not None else None
                 name = f'{n:07d}.png'
                 mask = one_hot_planes(index_mask(name), num_objects, dev) if path.exists(path.join(mask_dir, name)) else None
@@ -177,7 +202,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                     torch.cuda.synchronize()
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
-                hint = nxt if lookahead else None
+                hint = nxt[0] if (lookahead and nxt is not None) else None
                 prob = processor.step(frame, mask, idx_mask=False, next_image=hint) if mask is not None \
                     else processor.step(frame, next_image=hint)
                 if on_gpu:
@@ -204,7 +229,7 @@ def main():
     ap.add_argument('--max_internal_size', type=int, default=480)
     ap.add_argument('--mem_cleanup_ratio', type=float, default=-1)
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
-    ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU')
+    ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU; device-decode: decode JPEG frames on the GPU too')
     args = ap.parse_args()
     from .model.cutie import CUTIE
     cfg = video_config(model=args.model, mem_every=args.mem_every, max_internal_size=args.max_internal_size)

@@ -322,7 +322,24 @@ enum {
      *    of the vertical pass (an axis whose size does not change is one tap of weight 1).  p3 = f32 scratch [C, H, OW].  i7 = taps per row.
      *    dst and scratch 16-byte aligned.
      *  flags&4: p0 = u8 [H, W, C] interleaved (what PIL / numpy decode), row stride i6 BYTES (>= W*C), pixel stride C (i5 ignored); every
-     *    value becomes v / 255.0f correctly rounded = u8.float().div_(255.0), bit for bit.  Without flags&2: ToTensor alone, OH == H, OW == W. */
+     *    value becomes v / 255.0f correctly rounded = u8.float().div_(255.0), bit for bit.  Without flags&2: ToTensor alone, OH == H, OW == W.
+     * ABI 6 -- baseline JPEG decode on the GPU (ingest='device-decode'; kernels in jpeg.hip): flags 8 / 16 / 32 are the three stages and
+     *    may be set together (they run in that order); with any of them flags 1 / 2 / 4 are an error and the RESIZE fields above do not apply.
+     *    p0 = the packet (uint8, 4-byte aligned), built by cutie_amd/inference/data/jpeg.py: header, segment / chunk / component tables,
+     *    quant and Huffman tables, destuffed entropy data.  Every result equals libjpeg's (PIL's Image.open(...).convert('RGB')) bit for bit.
+     *    i: 0 chunks 1 segments 2 blocks 3 chunk bits 4 sync rounds 5 packet bytes 6 plane bytes 7 H 8 W 9 work words 10 components
+     *       11 rgb row stride (bytes, >= 3 W) -- copied from the packet header by ops.py OpList.jpeg_*.
+     *  flags&8 Huffman: self-synchronising speculative decode, one thread per chunk of i3 bits; i4 sync rounds, then any segment that
+     *    has not synchronised is decoded serially.  p1 = int32 work (8-byte aligned, >= 10 * i0 + (i4 + 1) * i1 words: chunk exits,
+     *    block counts and DC sums with their scans, per-round flags), p2 = int16 coef [i2][64] (natural order, quantised as in the file, absolute DC),
+     *    p3 = int32 status [4], cleared by the launch: 0 error bits (1 bad Huffman code, 2 data ends early -- where libjpeg goes on
+     *    with zeros and a warning; nonzero = the frame is bad), 1 sync rounds used (max over segments; i4 + 1 = serial), 2 serial segments.
+     *  flags&16 IDCT: libjpeg's ISLOW (jidctint.c: CONST_BITS 13, PASS1_BITS 2, DESCALE rounding, 64-bit intermediates, the range-limit
+     *    table with its 10-bit wrap), dequantising p2 with the packet's tables -> p4 = uint8 planes (i6 bytes, 8-byte aligned): per
+     *    component blocks_w * 8 wide, whole blocks.
+     *  flags&32 colour: libjpeg's fancy upsampling (h2v1 / h2v2 where the chroma width is > 2, h1v2 always; else replication) and its
+     *    fixed-point YCbCr -> RGB tables (SCALEBITS 16); one component is replicated -> p5 = uint8 [H, W, 3], row stride i11 bytes:
+     *    the source of RESIZE flags 4 / 6. */
     CUTIE_OP_RESIZE = 37,
     /* FLIP_W: dst = f0 * flip_last_dim(src) + f1 * dst   -- torch.flip(x, dims=[-1]) of the flip_aug path and the averaging
      * of the two passes (inference_core.py:162-165,234-235,303-305).  src and dst must not overlap.

@@ -1,7 +1,11 @@
-"""Device ingest probe (profiles/ingest_probe.md): what the host pays per frame in each ingest mode, and what the GPU pays.
+"""Device ingest probe (profiles/ingest_probe.md, profiles/jpeg_decode.md): what the host pays per frame in each ingest mode, and what
+the GPU pays.
 
-    python tools/ingest_probe.py cpu [--frames 24]            # host ms/frame of VideoReader[i], 'host' vs 'device', inline and ReadAhead(4)
-    python tools/ingest_probe.py gpu [--frames 40]            # RESIZE flags 4 / 6 us per frame (events), eval_vos wall-clock frames/s
+    python tools/ingest_probe.py cpu [--frames 24]            # host ms/frame of VideoReader[i] per mode, inline and ReadAhead(4)
+    python tools/ingest_probe.py gpu [--frames 40]            # RESIZE flags 4 / 6 and the JPEG decode us per frame (events), the decode's
+                                                              # sync rounds / serial segments, eval_vos wall-clock frames/s per mode
+    python tools/ingest_probe.py decode [--frames 40]         # only the JPEG decodes at 480p / 720p / 1080p, for
+                                                              # rocprofv3 --kernel-trace --stats (per-stage kernel times)
     [--out FILE.md]                                           # also append the markdown table to FILE
 
 Synthetic JPEG folders (smooth random content, quality 90) are generated in a temporary directory.  The eval_vos numbers are
@@ -19,6 +23,7 @@ from PIL import Image
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 
 SIZES = {'480p': (480, 854, -1), '720p': (720, 1280, 480), '1080p': (1080, 1920, 480)}
+MODES = ('host', 'device', 'device-decode')
 
 
 def make_video(root, name, n, h, w, seed, ids=(1, 2)):
@@ -46,7 +51,7 @@ def cpu_part(frames):
         for tag, (h, w, size) in SIZES.items():
             make_video(root, tag, frames, h, w, seed=1)
             res = {}
-            for mode in ('host', 'device'):
+            for mode in MODES:
                 rd = VideoReader(tag, os.path.join(root, 'JPEGImages', tag), os.path.join(root, 'Annotations', tag), size=size, ingest=mode)
                 rd[0]
                 t0 = time.perf_counter()
@@ -59,9 +64,39 @@ def cpu_part(frames):
                 ahead = (time.perf_counter() - t0) / len(rd) * 1e3
                 res[mode] = (inline, ahead)
                 rows.append(f'| {w}x{h} | {size} | {mode} | {inline:.2f} | {ahead:.2f} |')
-            ratios[tag] = (res['device'][0] / res['host'][0], res['device'][1] / res['host'][1])
+            ratios[tag] = {m: (res[m][0] / res['host'][0], res[m][1] / res['host'][1]) for m in MODES[1:]}
     rows.append('')
-    rows.append('device / host: ' + ', '.join(f'{k} {a:.2f} inline, {b:.2f} read-ahead' for k, (a, b) in ratios.items()))
+    for m in MODES[1:]:
+        rows.append(f'{m} / host: ' + ', '.join(f'{k} {r[m][0]:.2f} inline, {r[m][1]:.2f} read-ahead' for k, r in ratios.items()))
+    return rows
+
+
+def decode_part(frames, rows=None):
+    """The GPU JPEG decode of one synthetic frame per size, `frames` times after a warm-up: us per frame (events, packet upload
+    included), and the sync statistics of the last decode."""
+    from cutie_amd.inference.data import device_ingest as D
+    from cutie_amd.inference.data import jpeg as J
+    rows = rows if rows is not None else []
+    rows += ['| JPEG decode (device_ingest.jpeg_to_device, native size) | bytes | chunks | us per frame (events) | sync rounds | serial segments |',
+             '|---|---|---|---|---|---|']
+    with tempfile.TemporaryDirectory() as root:
+        for tag, (h, w, _) in SIZES.items():
+            make_video(root, tag, 1, h, w, seed=3)
+            pkt, why = J.parse_file(os.path.join(root, 'JPEGImages', tag, '00000.jpg'))
+            assert pkt is not None, why
+            for _ in range(5):
+                D.jpeg_to_device(pkt, 'cuda', stream=torch.cuda.current_stream())
+            torch.cuda.synchronize()
+            stats0 = dict(D.decode_stats)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(frames):
+                D.jpeg_to_device(pkt, 'cuda', stream=torch.cuda.current_stream())
+            e1.record()
+            torch.cuda.synchronize()
+            serial = D.decode_stats['serial_segments'] - stats0['serial_segments']
+            rows.append(f'| {w}x{h} | {pkt.buf.nbytes} | {int(pkt.hdr[J.HDR_NCHUNK])} | {e0.elapsed_time(e1) / frames * 1e3:.1f} | '
+                        f'{D.decode_stats["max_sync_rounds"]} | {serial} |')
     return rows
 
 
@@ -93,6 +128,8 @@ def gpu_part(frames):
         e1.record()
         torch.cuda.synchronize()
         rows.append(f'| RESIZE flags {int(ol.arr["flags"][0])} | {W}x{H} -> {OW}x{OH} | {e0.elapsed_time(e1) / 200 * 1e3:.1f} |')
+    rows.append('')
+    decode_part(frames, rows)
     rows += ['', '| eval_vos (1280x720, --size 480, 4 videos) | ingest | frames | wall s | wall frames/s | step-only frames/s |',
              '|---|---|---|---|---|---|']
     net = CUTIE(default_config()).cuda().eval()
@@ -102,7 +139,7 @@ def gpu_part(frames):
         for v in range(4):
             make_video(root, f'v{v}', frames, 720, 1280, seed=10 + v)
         for lockstep in (1, 4):
-            for mode in ('host', 'device', 'host', 'device'):             # each mode twice: the first pass warms plans and allocator
+            for mode in MODES + MODES:                                     # each mode twice: the first pass warms plans and allocator
                 ds = VOSTestDataset(os.path.join(root, 'JPEGImages'), os.path.join(root, 'Annotations'), use_all_masks=False, size=480, ingest=mode)
                 rds = list(ds.get_datasets())
                 out = os.path.join(root, f'out_{mode}_{lockstep}')
@@ -123,11 +160,11 @@ def gpu_part(frames):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('part', choices=['cpu', 'gpu'])
+    ap.add_argument('part', choices=['cpu', 'gpu', 'decode'])
     ap.add_argument('--frames', type=int, default=None)
     ap.add_argument('--out')
     a = ap.parse_args()
-    rows = cpu_part(a.frames or 24) if a.part == 'cpu' else gpu_part(a.frames or 40)
+    rows = {'cpu': cpu_part, 'gpu': gpu_part, 'decode': decode_part}[a.part](a.frames or (24 if a.part == 'cpu' else 40))
     text = '\n'.join(rows) + '\n'
     print(text)
     if a.out:

@@ -1198,6 +1198,63 @@ __global__ void prob_to_id_kernel(const float* __restrict__ prob, const int* __r
     out[idx] = (OUT)lut[arg];
 }
 
+// PROB_TO_ID flags&4 (ABI 7): the ids of the planes resampled to OH x OW -- RESIZE (flags == 0) and PROB_TO_ID in one launch, without the
+// resampled probabilities in memory.  Per plane the sample is resize_kernel's expression, operation for operation (same source index, same
+// lambdas, same order of multiplies and adds; the library is built without contraction), so the ids equal the two-launch chain's bit for
+// bit.  Four output pixels of a row per thread: they share the two source rows and the vertical lambda, and the ids leave as one store
+// (`packed`: OW % 4 == 0 and an output aligned to the store -- decided by the launch; else element by element).
+template <typename OUT>
+__global__ void prob_to_id_resample_kernel(const float* __restrict__ prob, const int* __restrict__ lut, OUT* __restrict__ out,
+                                           int P, int H, int W, int OH, int OW, long plane, int ldrow, int packed) {
+    const int OW4 = (OW + 3) >> 2;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)OH * OW4) return;
+    const int oy = (int)(idx / OW4), ox0 = (int)(idx - (long)oy * OW4) * 4;
+    const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
+    const float fy = fmaxf((oy + 0.5f) * sy - 0.5f, 0.f);
+    const int y0 = min((int)fy, H - 1), y1 = min(y0 + 1, H - 1);
+    const float ly = fy - (float)y0;
+    int x0[4], x1[4];
+    float lx[4], best[4];
+    int arg[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ox = min(ox0 + k, OW - 1);                       // (a lane past the row's end repeats the last pixel; it is not stored)
+        const float fx = fmaxf((ox + 0.5f) * sx - 0.5f, 0.f);
+        x0[k] = min((int)fx, W - 1);
+        x1[k] = min(x0[k] + 1, W - 1);
+        lx[k] = fx - (float)x0[k];
+        arg[k] = 0;
+    }
+    for (int q = 0; q < P; ++q) {
+        const float* r0 = prob + (long)q * plane + (long)y0 * ldrow;
+        const float* r1 = prob + (long)q * plane + (long)y1 * ldrow;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float a = r0[x0[k]], b = r0[x1[k]], cc = r1[x0[k]], d = r1[x1[k]];
+            const float v = (1.f - ly) * ((1.f - lx[k]) * a + lx[k] * b) + ly * ((1.f - lx[k]) * cc + lx[k] * d);
+            if (q == 0) best[k] = v;
+            else if (v > best[k]) { best[k] = v; arg[k] = q; }
+        }
+    }
+    OUT* o = out + (long)oy * OW + ox0;
+    if constexpr (sizeof(OUT) == 1) {
+        if (packed) {
+            *(uint32_t*)o = (uint32_t)(uint8_t)lut[arg[0]] | (uint32_t)(uint8_t)lut[arg[1]] << 8 | (uint32_t)(uint8_t)lut[arg[2]] << 16 |
+                            (uint32_t)(uint8_t)lut[arg[3]] << 24;
+            return;
+        }
+    } else {
+        if (packed) {
+            *(int4*)o = make_int4(lut[arg[0]], lut[arg[1]], lut[arg[2]], lut[arg[3]]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (ox0 + k < OW) o[k] = (OUT)lut[arg[k]];
+}
+
 // ---------------------------------------------------------------------------------------------
 int launch_elementwise(const cutie_op* op, hipStream_t s) {
     const int32_t* i = op->i;
@@ -1443,15 +1500,33 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
             break;
         }
         case CUTIE_OP_PROB_TO_ID: {
+            if (op->flags & ~15) { cutie_set_error("prob_to_id: unknown flags %d", op->flags); return -2; }
+            const bool resample = op->flags & 4, deflate = op->flags & 8;
+            const int OH = resample ? i[5] : i[1], OW = resample ? i[6] : i[2];      // the id plane's geometry
             const long n = (long)i[1] * i[2];
             const long plane = (long)i[3];
+            if (deflate && (op->flags & 3) != 0) { cutie_set_error("prob_to_id: the PNG stage (flags&8) reads uint8 ids (flags&3 == 0)"); return -2; }
+            if (deflate && !p[0]) return launch_png_deflate(op, OH, OW, s);          // the stage on its own, on an existing plane
             if (i[0] < 1) { cutie_set_error("prob_to_id: P >= 1"); return -2; }
-            if ((op->flags & 3) == 0)
+            if (resample && (i[1] < 1 || i[2] < 1 || OH < 1 || OW < 1)) { cutie_set_error("prob_to_id: empty shape"); return -2; }
+            if (resample && (op->flags & 3) == 2) { cutie_set_error("prob_to_id: resampled ids (flags&4) are uint8 or int32"); return -2; }
+            if (resample && (OH != i[1] || OW != i[2])) {                             // (the same size: every sample is its source pixel -- the plain kernel)
+                const long n4 = (long)OH * ((OW + 3) / 4);
+                const int packed = (OW & 3) == 0 && (p[2] & ((op->flags & 3) == 0 ? 3 : 15)) == 0;     // one 4- / 16-byte store per thread
+                if ((op->flags & 3) == 0)
+                    hipLaunchKernelGGL(prob_to_id_resample_kernel<uint8_t>, GRID1D(n4, BS), dim3(BS), 0, s, (const float*)p[0], (const int*)p[1], (uint8_t*)p[2], i[0], i[1], i[2], OH, OW, plane, i[4], packed);
+                else
+                    hipLaunchKernelGGL(prob_to_id_resample_kernel<int32_t>, GRID1D(n4, BS), dim3(BS), 0, s, (const float*)p[0], (const int*)p[1], (int32_t*)p[2], i[0], i[1], i[2], OH, OW, plane, i[4], packed);
+            } else if ((op->flags & 3) == 0)
                 hipLaunchKernelGGL(prob_to_id_kernel<uint8_t>, GRID1D(n, BS), dim3(BS), 0, s, (const float*)p[0], (const int*)p[1], (uint8_t*)p[2], i[0], i[1], i[2], plane, i[4]);
             else if ((op->flags & 3) == 1)
                 hipLaunchKernelGGL(prob_to_id_kernel<int32_t>, GRID1D(n, BS), dim3(BS), 0, s, (const float*)p[0], (const int*)p[1], (int32_t*)p[2], i[0], i[1], i[2], plane, i[4]);
             else
                 hipLaunchKernelGGL(prob_to_id_kernel<long long>, GRID1D(n, BS), dim3(BS), 0, s, (const float*)p[0], (const int*)p[1], (long long*)p[2], i[0], i[1], i[2], plane, i[4]);
+            if (deflate) {
+                const int rc = (int)hipGetLastError();
+                return rc ? rc : launch_png_deflate(op, OH, OW, s);
+            }
             break;
         }
         default:

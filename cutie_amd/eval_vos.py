@@ -4,7 +4,7 @@ first-mask alignment, ``end`` on the last frame, FPS = frames / sum of device-ev
 
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
-        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode]      (multi-scale testing: one run per --size with --save-scores, then
+        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
 
 With several GPUs launch it under torch.distributed.run: videos are sharded over the ranks (cutie_amd/parallel.py)."""
@@ -24,22 +24,23 @@ from .inference.data.prefetch import ReadAhead
 from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
-from .inference.utils.results_utils import ResultSaver, make_zip
+from .inference.utils.results_utils import EGRESS_MODES, ResultSaver, make_zip
 
 log = logging.getLogger()
 
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None) -> Dict:
+                  read_workers=4, ingest=None, egress='host') -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
-    ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode)."""
+    ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
+    egress: 'host' | 'device' (ResultSaver(egress=...): the GPU writes the masks' PNG streams)."""
     _check_ingest(ingest)
     processor = InferenceCore(network, cfg=cfg)
     saver = ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=processor.object_manager,
                         use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                         visualize_output_root=visualize_output_root, processor=processor, save_scores=save_scores,
-                        score_output_root=score_output_root)
+                        score_output_root=score_output_root, egress=egress)
     dev = network.device
     on_gpu = dev.type == 'cuda'
     n = len(vid_reader)
@@ -120,7 +121,7 @@ def lockstep_key(vid_reader):
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None) -> Dict[int, Dict]:
+                            ingest=None, egress='host') -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
@@ -135,7 +136,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     on_gpu = dev.type == 'cuda'
     savers = [ResultSaver(mask_output_root, rd.vid_name, dataset=dataset, object_manager=ls.cores[c].object_manager, use_long_id=rd.use_long_id,
                           palette=rd.get_palette(), visualize=visualize, visualize_output_root=visualize_output_root, processor=ls.cores[c],
-                          save_scores=save_scores, score_output_root=score_output_root) for c, rd in enumerate(vid_readers)]
+                          save_scores=save_scores, score_output_root=score_output_root, egress=egress) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     depth = 16 if lookahead else 1
@@ -210,7 +211,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     return stats
 
 
-def main():
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', required=True)
     ap.add_argument('--masks', required=True)
@@ -232,7 +233,14 @@ def main():
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES),
                     help="device: upload the decoded uint8 frames, ToTensor + antialiased resize on the GPU (cutie_amd/inference/data/device_ingest.py); "
                          "device-decode: upload the JPEG bytes and decode them on the GPU as well (baseline JPEG; other frames as 'device')")
-    args = ap.parse_args()
+    ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES),
+                    help='device: the GPU resamples + argmaxes the result in one kernel and writes the PNG zlib stream; the host copies a few '
+                         'KB per frame without blocking and only wraps them in PNG chunks (cutie_amd/inference/utils/results_utils.py)')
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     from .model.cutie import CUTIE
     from .parallel import run_concurrent, shard_clips
     import torch.distributed as dist
@@ -252,7 +260,7 @@ def main():
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, dataset=args.dataset, visualize=args.visualize,
                                         visualize_output_root=path.join(args.output, 'Visualizations'),
                                         save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'),
-                                        read_workers=args.read_workers)
+                                        read_workers=args.read_workers, egress=args.egress)
     res = {}
     with torch.inference_mode():
         if args.lockstep > 1 and not args.flip_aug:
@@ -273,7 +281,8 @@ def main():
             for grp in grouped:
                 st = process_videos_lockstep(net, cfg, [readers[c] for c in grp], mask_root, dataset=args.dataset, visualize=args.visualize,
                                              visualize_output_root=path.join(args.output, 'Visualizations'), save_scores=args.save_scores,
-                                             score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers)
+                                             score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
+                                             egress=args.egress)
                 for j, c in enumerate(grp):
                     res[c] = st[j]
             mine = [c for c in mine if c not in res]

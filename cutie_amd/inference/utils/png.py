@@ -1,0 +1,36 @@
+"""PNG container around a finished zlib stream (``ResultSaver(egress='device')``): the device hands over the compressed,
+filtered image (csrc/png.hip: filter byte 0 in front of every row of ids), the host adds signature, IHDR, PLTE, one IDAT and
+IEND with their CRCs.  No PIL here; a few KB per frame go through ``zlib.crc32``.
+
+The files differ from PIL's in bytes (other filter, fixed Huffman codes, always 8 bits per pixel where PIL packs palettes of
+<= 16 colours into 1 / 2 / 4 bits) and are equal in content: ``Image.open`` gives the same mode, palette and pixels."""
+import struct
+import zlib
+from typing import Optional, Sequence, Union
+
+SIGNATURE = b'\x89PNG\r\n\x1a\n'
+
+
+def _chunk(kind: bytes, data: bytes) -> bytes:
+    return struct.pack('>I', len(data)) + kind + data + struct.pack('>I', zlib.crc32(kind + data) & 0xffffffff)
+
+
+def plte_bytes(palette: Union[bytes, Sequence[int]]) -> bytes:
+    """The PLTE chunk data PIL writes for ``putpalette(palette)`` (PngImagePlugin._save): the RGB triples as given, at most
+    256 and at least one of them, zero-padded to whole entries."""
+    data = bytes(palette)
+    colors = max(min(len(data) // 3, 256), 1)
+    return data[:colors * 3].ljust(colors * 3, b'\0')
+
+
+def assemble(stream: bytes, H: int, W: int, palette: Optional[Union[bytes, Sequence[int]]] = None) -> bytes:
+    """File bytes of an 8-bit PNG of H x W pixels whose IDAT data is ``stream`` (a complete zlib stream of the filtered
+    rows).  ``palette`` (flat RGB, what ``Image.putpalette`` takes): colour type 3 with that PLTE; None: greyscale."""
+    if H < 1 or W < 1:
+        raise ValueError('assemble: empty image')
+    ihdr = struct.pack('>IIBBBBB', W, H, 8, 3 if palette is not None else 0, 0, 0, 0)
+    parts = [SIGNATURE, _chunk(b'IHDR', ihdr)]
+    if palette is not None:
+        parts.append(_chunk(b'PLTE', plte_bytes(palette)))
+    parts += [_chunk(b'IDAT', bytes(stream)), _chunk(b'IEND', b'')]
+    return b''.join(parts)

@@ -9,13 +9,20 @@ this image, so the container here is ``<frame>.npz`` (key ``prob``) and ``backwa
 ``cutie_amd.merge_multi_scale`` reads these (and ``.hkl`` when hickle is importable).  Not supported (raise): the BURST
 json writer (``init_json``: its RLE masks need pycocotools, which is not in this image).
 Long ids (RGB masks): as in the reference (:171-178) every object gets a random colour (utils/pano_utils.ID2RGBConverter), NOT the
-inverse of VideoReader's R + 256 G + 65536 B decoding.  Behaviour recorded from the executed reference: tests/golden/io/."""
+inverse of VideoReader's R + 256 G + 65536 B decoding.  Behaviour recorded from the executed reference: tests/golden/io/.
+
+``egress='device'`` (not in the reference): the mask leaves the GPU as a finished zlib stream instead of an id
+plane.  One op list per frame on the caller's stream -- argmax + remap (fused with the bilinear resampling when the frame was resized on
+the way in, so the full-size probabilities never exist) and the PNG filter + DEFLATE + Adler-32 stage (csrc/png.hip) -- then ONE
+non-blocking copy of the status block and the first slab of the stream into pinned memory with an event behind it.  ``process`` does
+not wait; the writer thread waits on the event, checks the error word, wraps the bytes (utils/png.py) and writes the file.  The files
+hold the same mode, palette and pixels as the host path's; their bytes differ (other filter and Huffman codes, always 8 bits)."""
 import logging
 import os
 import shutil
 from dataclasses import dataclass
 from os import path
-from queue import Queue
+from queue import Empty, Queue
 from threading import Thread
 from typing import Optional, Tuple
 
@@ -25,6 +32,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 from ...utils.pano_utils import ID2RGBConverter
+from . import png as png_container
 
 log = logging.getLogger()
 
@@ -47,6 +55,25 @@ davis_palette_np = voc_palette()
 davis_palette = davis_palette_np.tobytes()
 
 
+EGRESS_MODES = ('host', 'device')
+EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
+
+
+class _EgressBuffers:
+    """What one frame in flight owns (egress='device'): the id plane, [status | stream] on the device, the pinned slab and the event
+    recorded behind the copy.  Recycled through ResultSaver's pool once the writer thread is done with them."""
+
+    def __init__(self, H, W, device):
+        from ... import ops as O
+        self.H, self.W = H, W
+        cap = O.OpList.png_capacity(H, W)
+        self.ids = torch.empty((H, W), dtype=torch.uint8, device=device)
+        self.dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
+        self.status, self.stream = self.dev[:16].view(torch.int32), self.dev[16:]
+        self.host = torch.empty(min(16 + cap, EGRESS_SLAB), dtype=torch.uint8).pin_memory()
+        self.event = torch.cuda.Event()
+
+
 @dataclass
 class _Job:
     saver: 'ResultSaver'
@@ -57,14 +84,25 @@ class _Job:
     prob: Optional[torch.Tensor] = None      # CPU uint8 [K+1,H,W] (save_scores)
     last_frame: bool = False
     tmp_to_obj: Optional[dict] = None        # {tmp_id: object id} at the time of the frame
+    egress: Optional[_EgressBuffers] = None  # egress='device': the mask arrives in these (mask is None)
 
 
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
-                 processor=None):
+                 processor=None, egress='host'):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
-        without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore)."""
+        without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
+        ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
+        stream, see the module docstring; needs ``processor``).  A saver falls back to the host path -- ``self.egress`` says which one
+        runs -- with ``use_long_id`` (RGB masks), with ``visualize`` (the overlay needs the ids on the host) and without ``save_mask``;
+        ``save_scores`` keeps its own copy of the probabilities next to the device-encoded mask: with it -- multi-scale runs -- ``process``
+        still builds the full-size fp32 probabilities when the frame was resized and blocks on their copy, so 'device' saves only the
+        PNG encode there, not the stall."""
+        if egress not in EGRESS_MODES:
+            raise ValueError(f'egress must be one of {EGRESS_MODES}, not {egress!r}')
+        if egress == 'device' and processor is None:
+            raise ValueError("egress='device' needs the processor (its device and object table)")
         if save_scores and score_output_root is None:
             raise ValueError('save_scores needs score_output_root')
         self.save_scores, self.score_output_root = save_scores, score_output_root
@@ -74,6 +112,9 @@ class ResultSaver:
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
+        self.egress = 'device' if (egress == 'device' and not use_long_id and not visualize and save_mask) else 'host'
+        self._free: Queue = Queue()              # recycled _EgressBuffers
+        self._allocated, self._luts, self._scratch, self._wstream = 0, {}, None, None
         if self.visualize:
             self.colors = np.array(self.palette, dtype=np.uint8).reshape(-1, 3) if self.palette is not None else davis_palette_np
         self.need_remapping = True
@@ -84,6 +125,8 @@ class ResultSaver:
 
     def process(self, prob: torch.Tensor, frame_name: str, resize_needed: bool = False, shape: Optional[Tuple[int, int]] = None,
                 last_frame: bool = False, path_to_image: str = None):
+        if self.egress == 'device':
+            return self._process_device(prob, frame_name, resize_needed, shape, last_frame)
         if resize_needed:
             prob = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0]
         out_dtype = torch.int32 if self.use_long_id else torch.uint8
@@ -101,10 +144,78 @@ class ResultSaver:
                             prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None))
 
+    # ---- egress='device' --------------------------------------------------------------------------------------------------------
+    def _take(self, H, W, device) -> _EgressBuffers:
+        """Buffers for one frame: a recycled set, a new one while fewer than the queue can hold (+ the one in the writer's hands and
+        this one) exist, else the next set the writer gives back."""
+        while True:
+            try:
+                b = self._free.get_nowait()
+            except Empty:
+                if self._allocated < self.queue.maxsize + 2:
+                    self._allocated += 1
+                    return _EgressBuffers(H, W, device)
+                b = self._free.get()
+            if (b.H, b.W) == (H, W):
+                return b
+            self._allocated -= 1                 # another geometry: dropped
+
+    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame):
+        from ... import ops as O
+        core = self.processor
+        dev = core.network.device
+        P, h, w = prob.shape
+        H, W = (int(shape[0]), int(shape[1])) if resize_needed else (h, w)
+        lut = [0] * P
+        for tmp_id, obj in self.object_manager.tmp_id_to_obj.items():
+            if tmp_id < P:
+                lut[tmp_id] = int(obj.id)
+        if max(lut) > 255:
+            raise ValueError('object ids above 255 need use_long_id')
+        lut_dev = self._luts.get(tuple(lut))
+        if lut_dev is None:                      # (changes when objects come or go, not per frame)
+            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
+        if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
+            prob = prob.to(device=dev, dtype=torch.float32).contiguous()
+        if self._scratch is None or self._scratch[0] != (H, W):
+            self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+        b = self._take(H, W, dev)
+        ol = O.OpList()
+        ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
+                      out_hw=(H, W) if resize_needed else None, png=(b.stream, b.status, self._scratch[1]))
+        ol.run()
+        b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
+        b.event.record()
+        q = None
+        if self.save_scores:                     # as the host path: the scores of the output size
+            full = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
+            q = (full * 255).to(torch.uint8).cpu()
+        self.queue.put(_Job(self, None, frame_name, None, [o.id for o in self.object_manager.obj_to_tmp_id], prob=q, last_frame=last_frame,
+                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b))
+
+    def _fetch(self, b: _EgressBuffers) -> bytes:
+        """Writer thread: the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
+        b.event.synchronize()
+        length, _, err, _ = (int(v) for v in b.host[:16].view(torch.int32))
+        if err != 0:
+            raise RuntimeError(f'device PNG encoder: error bits {err} (stream of {length} bytes, capacity {b.stream.numel()})')
+        have = b.host.numel() - 16
+        head = b.host[16:16 + min(length, have)].numpy().tobytes()
+        if length <= have:
+            return head
+        if self._wstream is None:                # the rare long stream: the rest, on a stream of the writer's own
+            self._wstream = torch.cuda.Stream(device=b.dev.device)
+        rest = torch.empty(length - have, dtype=torch.uint8).pin_memory()
+        with torch.cuda.stream(self._wstream):
+            rest.copy_(b.stream[have:length], non_blocking=True)
+        self._wstream.synchronize()
+        return head + rest.numpy().tobytes()
+
     def end(self):
         self.queue.put(None)
         self.queue.join()
         self.thread.join()
+        self._free, self._allocated, self._scratch = Queue(), 0, None
 
 
 def _writer(queue: Queue):
@@ -115,9 +226,19 @@ def _writer(queue: Queue):
             break
         try:
             s = job.saver
-            out_mask = job.mask.numpy()
+            if job.egress is not None:                             # egress='device': wrap the finished stream, no PIL
+                b = job.egress
+                try:
+                    data = png_container.assemble(s._fetch(b), b.H, b.W, s.palette)
+                finally:
+                    s._free.put(b)
+                out_dir = path.join(s.output_root, s.video_name)
+                os.makedirs(out_dir, exist_ok=True)
+                with open(path.join(out_dir, job.frame_name[:-4] + '.png'), 'wb') as f:
+                    f.write(data)
+            out_mask = job.mask.numpy() if job.mask is not None else None
             rgb_mask = None
-            if s.save_mask:
+            if s.save_mask and job.egress is None:
                 if s.use_long_id:
                     m = out_mask.astype(np.uint32)
                     rgb_mask = np.zeros((*m.shape[-2:], 3), dtype=np.uint8)

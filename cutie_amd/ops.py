@@ -814,10 +814,37 @@ class OpList:
     def consol_read(self, S, colmax, vptrs, cshr, scratch, out_shr, *, n, P, C, K, src, dst):
         return self.add(CONSOL_READ, 0, [n, P, C, K, self.consol_lds(n), src, dst], [], [S, colmax, vptrs, cshr, scratch, out_shr])
 
-    def prob_to_id(self, prob, lut, out, *, P, H, W, plane, ldrow):
-        """out dtype picks the kernel: uint8 / int32 / int64."""
+    def prob_to_id(self, prob, lut, out, *, P, H, W, plane, ldrow, out_hw=None, png=None):
+        """out dtype picks the kernel: uint8 / int32 / int64.  ABI 7 (include/cutie_hip.h): out_hw = (OH, OW) -- the ids of the planes
+        resampled bilinearly to that size (out [OH, OW], uint8 / int32) without the resampled probabilities in memory, bit-identical to
+        resize() + prob_to_id(); png = (stream, status, scratch) -- the uint8 ids also leave as the zlib stream of a PNG (png_deflate)."""
         code = {torch.uint8: 0, torch.int32: 1, torch.int64: 2}[out.dtype]
-        return self.add(PROB_TO_ID, code, [P, H, W, plane, ldrow], [], [prob, lut, out])
+        ints = [P, H, W, plane, ldrow]
+        if out_hw is not None:
+            code |= 4
+            ints += [int(out_hw[0]), int(out_hw[1])]
+        if png is None:
+            return self.add(PROB_TO_ID, code, ints, [], [prob, lut, out])
+        stream, status, scratch = png
+        ints += [0] * (7 - len(ints)) + [stream.numel(), scratch.numel()]
+        return self.add(PROB_TO_ID, code | 8, ints, [], [prob, lut, out, stream, status, scratch])
+
+    @staticmethod
+    def png_capacity(H, W):
+        """Bytes that hold the zlib stream of ANY uint8 plane [H, W]: with the fixed Huffman codes a filtered byte costs at most 9 bits;
+        2 bytes header, block header + end of block (10 bits), 4 bytes Adler-32; rounded up to a multiple of 4."""
+        return -(-(-(-((W + 1) * H * 9 + 10) // 8) + 6) // 4) * 4
+
+    @staticmethod
+    def png_scratch_words(H, W):
+        """int32 words of the scratch of png_deflate: per row 4 words of bookkeeping and the row's bits (csrc/png.hip png_row_words)."""
+        return H * (4 + (9 * (W + 1) + 31) // 32 + 2)
+
+    def png_deflate(self, ids, stream, status, scratch, *, H, W):
+        """PROB_TO_ID flags&8 on its own: ids uint8 [H, W] (contiguous) -> stream uint8 [capacity] = the complete zlib stream of the
+        PNG-filtered plane (filter 0), status int32 [4] = (stream bytes, Adler-32, error bits: 1 = the capacity is too small and nothing
+        was written, 0).  scratch int32 [>= png_scratch_words(H, W)], 16-byte aligned.  cutie_amd/inference/utils/png.py wraps the stream."""
+        return self.add(PROB_TO_ID, 8, [0, H, W, 0, 0, 0, 0, stream.numel(), scratch.numel()], [], [None, None, ids, stream, status, scratch])
 
     def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
         """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32

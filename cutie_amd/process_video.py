@@ -13,7 +13,7 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
 (long-term memory on, mem_every 10, max_internal_size 480).
 
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
-        [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device]
+        [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
 
 ``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
 cutie_amd/inference/data/device_ingest.py).  ``--ingest device-decode``: JPEG frames of a directory are parsed on the host and
@@ -35,7 +35,7 @@ from .inference.data.device_ingest import frame_to_device, jpeg_to_device
 from .inference.data.prefetch import ReadAhead
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
-from .inference.utils.results_utils import ResultSaver
+from .inference.utils.results_utils import EGRESS_MODES, ResultSaver
 
 IMAGE_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
 
@@ -136,7 +136,7 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 
 
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
-                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host') -> Dict:
+                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host') -> Dict:
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -187,7 +187,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                            force_permanent=True)
         # 2. the whole video
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
-                            palette=palette, processor=processor)
+                            palette=palette, processor=processor, egress=egress)
         total, n, cleanups = 0.0, 0, 0
         try:
             it = iter(src)
@@ -218,7 +218,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     return {'frames': n, 'seconds': total, 'cleanups': cleanups, 'num_objects': num_objects, 'processor': processor}
 
 
-def main():
+def arg_parser() -> ArgumentParser:
     ap = ArgumentParser()
     ap.add_argument('-v', '--video', required=True, help='directory of frames (or a video file when OpenCV is available)')
     ap.add_argument('-m', '--mask_dir', required=True, help='masks named <frame number, 7 digits>.png')
@@ -230,7 +230,12 @@ def main():
     ap.add_argument('--mem_cleanup_ratio', type=float, default=-1)
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU; device-decode: decode JPEG frames on the GPU too')
-    args = ap.parse_args()
+    ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES), help='device: the GPU writes the PNG streams of the masks (ResultSaver(egress=...))')
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
     from .model.cutie import CUTIE
     cfg = video_config(model=args.model, mem_every=args.mem_every, max_internal_size=args.max_internal_size)
     net = CUTIE(cfg).cuda().eval()
@@ -239,7 +244,7 @@ def main():
     else:
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
-                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest)
+                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress)
     print(f'Total processing time: {r["seconds"]}\nTotal processed frames: {r["frames"]}\n'
           f'FPS: {r["frames"] / max(r["seconds"], 1e-9)}\nMax allocated memory (MB): {torch.cuda.max_memory_allocated() / 2 ** 20}')
 

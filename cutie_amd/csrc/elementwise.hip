@@ -1255,6 +1255,70 @@ __global__ void prob_to_id_resample_kernel(const float* __restrict__ prob, const
         if (ox0 + k < OW) o[k] = (OUT)lut[arg[k]];
 }
 
+// PROB_TO_ID flags&16 (ABI 8): the ids of S sources merged -- what the multi-scale protocol does with files (every run dumps its uint8
+// scores, a host tool sums them and takes the argmax) in one launch.  Per plane q and output pixel: sum = sum over the sources of
+// (int)(uint8)(sample * 255.f), sample = prob_to_id_resample_kernel's (= resize_kernel's) expression on that source, operation for
+// operation; the quantisation truncates like (prob * 255).to(torch.uint8).  The sums are 32-bit integers, so neither the order of the
+// sources nor the launch shape can change an id.  Planes outside, sources inside: one integer per pixel and the running best are all that
+// lives across the loops (no P x 4 accumulators, nothing per pixel in memory); a source's geometry is read from the table through
+// wave-uniform addresses and its coordinates are recomputed per plane -- a handful of VALU operations next to sixteen loads.  Four output
+// pixels of a row per thread and the packed store as in the one-source kernel.
+template <typename OUT>
+__global__ void prob_to_id_merge_kernel(const uint64_t* __restrict__ srcs, const int4* __restrict__ geom, const int* __restrict__ lut,
+                                        OUT* __restrict__ out, int S, int P, int OH, int OW, int packed) {
+    const int OW4 = (OW + 3) >> 2;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (long)OH * OW4) return;
+    const int oy = (int)(idx / OW4), ox0 = (int)(idx - (long)oy * OW4) * 4;
+    int best[4], arg[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { best[k] = 0; arg[k] = 0; }
+    for (int q = 0; q < P; ++q) {
+        int sum[4] = {0, 0, 0, 0};
+        for (int sI = 0; sI < S; ++sI) {
+            const int4 g = geom[sI];                                   // H, W, plane stride, row stride
+            const int H = g.x, W = g.y;
+            if (H < 1 || W < 1) continue;
+            const float* prob = (const float*)srcs[sI] + (long)q * g.z;
+            const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
+            const float fy = fmaxf((oy + 0.5f) * sy - 0.5f, 0.f);
+            const int y0 = min((int)fy, H - 1), y1 = min(y0 + 1, H - 1);
+            const float ly = fy - (float)y0;
+            const float* r0 = prob + (long)y0 * g.w;
+            const float* r1 = prob + (long)y1 * g.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ox = min(ox0 + k, OW - 1);                   // (a lane past the row's end repeats the last pixel; it is not stored)
+                const float fx = fmaxf((ox + 0.5f) * sx - 0.5f, 0.f);
+                const int x0 = min((int)fx, W - 1), x1 = min(x0 + 1, W - 1);
+                const float lx = fx - (float)x0;
+                const float a = r0[x0], b = r0[x1], cc = r1[x0], d = r1[x1];
+                const float v = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * cc + lx * d);
+                sum[k] += (int)(uint8_t)(int)(v * 255.f);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (q == 0 || sum[k] > best[k]) { best[k] = sum[k]; arg[k] = q; }
+    }
+    OUT* o = out + (long)oy * OW + ox0;
+    if constexpr (sizeof(OUT) == 1) {
+        if (packed) {
+            *(uint32_t*)o = (uint32_t)(uint8_t)lut[arg[0]] | (uint32_t)(uint8_t)lut[arg[1]] << 8 | (uint32_t)(uint8_t)lut[arg[2]] << 16 |
+                            (uint32_t)(uint8_t)lut[arg[3]] << 24;
+            return;
+        }
+    } else {
+        if (packed) {
+            *(int4*)o = make_int4(lut[arg[0]], lut[arg[1]], lut[arg[2]], lut[arg[3]]);
+            return;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (ox0 + k < OW) o[k] = (OUT)lut[arg[k]];
+}
+
 // ---------------------------------------------------------------------------------------------
 int launch_elementwise(const cutie_op* op, hipStream_t s) {
     const int32_t* i = op->i;
@@ -1500,8 +1564,31 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
             break;
         }
         case CUTIE_OP_PROB_TO_ID: {
-            if (op->flags & ~15) { cutie_set_error("prob_to_id: unknown flags %d", op->flags); return -2; }
+            if (op->flags & ~31) { cutie_set_error("prob_to_id: unknown flags %d", op->flags); return -2; }
             const bool resample = op->flags & 4, deflate = op->flags & 8;
+            if (op->flags & 16) {                                                     // S sources merged (ABI 8): every check before any launch
+                const int S = i[9], MOH = i[5], MOW = i[6];
+                if (!resample) { cutie_set_error("prob_to_id: the merge (flags&16) is a resampling path: flags&4 must accompany it"); return -2; }
+                if ((op->flags & 3) == 2) { cutie_set_error("prob_to_id: merged ids (flags&16) are uint8 or int32"); return -2; }
+                if (deflate && (op->flags & 3) != 0) { cutie_set_error("prob_to_id: the PNG stage (flags&8) reads uint8 ids (flags&3 == 0)"); return -2; }
+                if (S < 1 || S > CUTIE_MERGE_MAX_SOURCES) { cutie_set_error("prob_to_id: merge of %d sources, 1 <= S <= %d", S, CUTIE_MERGE_MAX_SOURCES); return -2; }
+                if (!p[0] || !p[6]) { cutie_set_error("prob_to_id: the merge (flags&16) needs the source table (p0) and the geometry table (p6)"); return -2; }
+                if ((p[0] & 7) || (p[6] & 15)) { cutie_set_error("prob_to_id: merge tables: p0 8-byte aligned, p6 16-byte aligned"); return -2; }
+                if (!p[1] || !p[2]) { cutie_set_error("prob_to_id: the merge (flags&16) needs the lut (p1) and the output (p2)"); return -2; }
+                if (i[0] < 1) { cutie_set_error("prob_to_id: P >= 1"); return -2; }
+                if (MOH < 1 || MOW < 1) { cutie_set_error("prob_to_id: empty shape"); return -2; }
+                const long n4 = (long)MOH * ((MOW + 3) / 4);
+                const int packed = (MOW & 3) == 0 && (p[2] & ((op->flags & 3) == 0 ? 3 : 15)) == 0;     // one 4- / 16-byte store per thread
+                if ((op->flags & 3) == 0)
+                    hipLaunchKernelGGL(prob_to_id_merge_kernel<uint8_t>, GRID1D(n4, BS), dim3(BS), 0, s, (const uint64_t*)p[0], (const int4*)p[6], (const int*)p[1], (uint8_t*)p[2], S, i[0], MOH, MOW, packed);
+                else
+                    hipLaunchKernelGGL(prob_to_id_merge_kernel<int32_t>, GRID1D(n4, BS), dim3(BS), 0, s, (const uint64_t*)p[0], (const int4*)p[6], (const int*)p[1], (int32_t*)p[2], S, i[0], MOH, MOW, packed);
+                if (deflate) {
+                    const int rc = (int)hipGetLastError();
+                    return rc ? rc : launch_png_deflate(op, MOH, MOW, s);
+                }
+                break;
+            }
             const int OH = resample ? i[5] : i[1], OW = resample ? i[6] : i[2];      // the id plane's geometry
             const long n = (long)i[1] * i[2];
             const long plane = (long)i[3];

@@ -6,6 +6,8 @@ first-mask alignment, ``end`` on the last frame, FPS = frames / sum of device-ev
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
         [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
+        [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
+                                            no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
 
 With several GPUs launch it under torch.distributed.run: videos are sharded over the ranks (cutie_amd/parallel.py)."""
 import argparse
@@ -92,6 +94,94 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
             if save_all or info['save']:
                 saver.process(prob, info['frame'], resize_needed=info['resize_needed'], shape=info['shape'],
                               last_frame=(ti == n - 1), path_to_image=info['path_to_image'])
+    finally:
+        saver.end()
+    return {'frames': frames, 'seconds': total}
+
+
+def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
+                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
+                             read_workers=4, ingest=None, egress='host') -> Dict:
+    """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
+    scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
+    One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
+    and frame context; per member exactly ``process_video``'s handling -- and after the S steps of a frame ``ResultSaver.process_merged``
+    sums the members' quantised probabilities at the original size and writes the mask (one kernel; no score files, no full-size plane).
+    The members' probabilities stay referenced until the merge has been issued: a pooled plan output that somebody holds is not recycled
+    (plans.SlotPool), and everything runs on the caller's stream.  Returns {'frames', 'seconds'}; seconds = the sum over the members."""
+    _check_ingest(ingest)
+    if save_scores:
+        raise ValueError('process_video_multiscale merges on the device and writes no scores: save_scores is not supported')
+    from . import frame_context
+    from .inference import inference_core as IC
+    S = len(vid_readers)
+    if S < 1:
+        raise ValueError('process_video_multiscale needs at least one reader')
+    rd0 = vid_readers[0]
+    n = len(rd0)
+    if any(rd.vid_name != rd0.vid_name or len(rd) != n for rd in vid_readers):
+        raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
+    cores = [InferenceCore(network, cfg=cfg) for _ in range(S)]
+    ctxs = [frame_context.new_context() for _ in range(S)]
+    for s, core in enumerate(cores):
+        core.memory._clip_tag = s                # (its own read-out slots in the engine's pool, as the clips of a lock-step group)
+    saver = ResultSaver(mask_output_root, rd0.vid_name, dataset=dataset, object_manager=cores[0].object_manager,
+                        use_long_id=rd0.use_long_id, palette=rd0.get_palette(), visualize=visualize,
+                        visualize_output_root=visualize_output_root, processor=cores[0], egress=egress)
+    dev = network.device
+    on_gpu = dev.type == 'cuda'
+    total, frames, first_mask_loaded = 0.0, 0, False
+    try:
+        loaders = [iter(_read_ahead(rd, read_workers, ingest)) for rd in vid_readers]
+        depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
+        ahead = [deque() for _ in range(S)]
+
+        def fill(s):
+            while len(ahead[s]) < depth:
+                d = next(loaders[s], None)
+                if d is None:
+                    break
+                ahead[s].append(to_device(d, dev, defer_check=True))
+
+        for s in range(S):
+            fill(s)
+        for ti in range(n):
+            data = [finish(ahead[s].popleft()) for s in range(S)]
+            for s in range(S):
+                fill(s)
+            info = data[0]['info']
+            if any(d['info']['frame'] != info['frame'] or tuple(d['info']['shape']) != tuple(info['shape']) for d in data):
+                raise ValueError(f"process_video_multiscale: the readers disagree on frame {ti} ({[d['info']['frame'] for d in data]})")
+            if not first_mask_loaded:
+                if data[0].get('mask') is None:
+                    continue                                  # nothing to do before the first mask
+                first_mask_loaded = True
+            probs = []
+            for s, (core, d) in enumerate(zip(cores, data)):
+                mask = d.get('mask')
+                mask = mask.to(dev) if mask is not None else None
+                valid = d.get('valid_labels')
+                valid = valid.tolist() if valid is not None else None
+                next_images = [x['rgb'] for x in ahead[s]] if (lookahead and ahead[s]) else None
+                if on_gpu:
+                    torch.cuda.synchronize()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                else:
+                    t0 = time.perf_counter()
+                with frame_context.context(ctxs[s]):
+                    probs.append(core.step(d['rgb'], mask, valid, end=(ti == n - 1), next_images=next_images))
+                if on_gpu:
+                    e1.record()
+                    torch.cuda.synchronize()
+                    total += e0.elapsed_time(e1) / 1000
+                else:
+                    total += time.perf_counter() - t0
+            frames += 1
+            if save_all or info['save']:
+                saver.process_merged(probs, info['frame'], info['shape'], last_frame=(ti == n - 1), path_to_image=info['path_to_image'],
+                                     id_maps=[{t: o.id for t, o in c.object_manager.tmp_id_to_obj.items()} for c in cores])
+            del probs
     finally:
         saver.end()
     return {'frames': frames, 'seconds': total}
@@ -219,6 +309,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--weights')
     ap.add_argument('--dataset', default='generic')
     ap.add_argument('--size', type=int, default=-1)
+    ap.add_argument('--sizes', type=int, nargs='+', default=None,
+                    help='multi-scale testing in one run: at least two distinct --size values (-1: the original size); the scales of a video '
+                         'advance side by side and their quantised scores are summed and argmaxed on the GPU (process_video_multiscale), '
+                         'no score files.  Excludes --size, --save-scores and --lockstep > 1')
     ap.add_argument('--subset')
     ap.add_argument('--use-all-masks', action='store_true')
     ap.add_argument('--long-term', action='store_true')
@@ -239,8 +333,27 @@ def arg_parser() -> argparse.ArgumentParser:
     return ap
 
 
+def check_args(ap: argparse.ArgumentParser, args) -> None:
+    """The rules between switches that argparse cannot state (ap.error: usage + exit status 2)."""
+    if args.sizes is not None:
+        if len(set(args.sizes)) != len(args.sizes) or len(args.sizes) < 2:
+            ap.error('--sizes takes at least two distinct values')
+        if any(v != -1 and v < 1 for v in args.sizes):
+            ap.error('--sizes: a size is positive, or -1 for the original size')
+        if len(args.sizes) > 8:
+            ap.error('--sizes: at most 8 scales are merged in one launch')
+        if args.size != -1:
+            ap.error('--sizes and --size exclude each other')
+        if args.save_scores:
+            ap.error('--sizes merges on the GPU and writes no scores: it excludes --save-scores')
+        if args.lockstep > 1:
+            ap.error('--sizes does not run in lock step: it excludes --lockstep > 1 (use --clips-in-flight)')
+
+
 def main():
-    args = arg_parser().parse_args()
+    ap = arg_parser()
+    args = ap.parse_args()
+    check_args(ap, args)
     from .model.cutie import CUTIE
     from .parallel import run_concurrent, shard_clips
     import torch.distributed as dist
@@ -261,6 +374,14 @@ def main():
                                         visualize_output_root=path.join(args.output, 'Visualizations'),
                                         save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'),
                                         read_workers=args.read_workers, egress=args.egress)
+    if args.sizes is not None:
+        # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is
+        # scales[s][c] -- every dataset lists the folder in the same sorted order
+        scales = [list(VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=sz, subset=args.subset,
+                                      ingest=args.ingest).get_datasets()) for sz in args.sizes]
+        run = lambda view, c: process_video_multiscale(view, cfg, [sc[c] for sc in scales], mask_root, dataset=args.dataset,
+                                                       visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
+                                                       read_workers=args.read_workers, egress=args.egress)
     res = {}
     with torch.inference_mode():
         if args.lockstep > 1 and not args.flip_aug:

@@ -193,6 +193,62 @@ class ResultSaver:
         self.queue.put(_Job(self, None, frame_name, None, [o.id for o in self.object_manager.obj_to_tmp_id], prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b))
 
+    # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
+    def process_merged(self, probs, frame_name: str, shape: Tuple[int, int], last_frame: bool = False, path_to_image: str = None, *,
+                       id_maps=None):
+        """One frame of a multi-scale run (not in the reference, whose protocol is one run per size with ``save_scores`` and
+        scripts/merge_multi_scale.py afterwards): ``probs`` = the members' [K+1, h_s, w_s] probabilities of the frame,
+        every one resampled to ``shape``, quantised to uint8 and summed as the file route does, argmax + remap -- ONE kernel (PROB_TO_ID
+        flags&16) that reads the members' views in place; no full-size plane and no score file exists.  egress='host': the id plane
+        (uint8, int32 with long ids) is copied to the host and the writer thread does the rest (visualize, long ids); egress='device':
+        the same op carries the PNG stage, as in ``process``.  ``id_maps``: the members' {tmp id: object id} tables -- they must be
+        equal (the members see the same first masks in the same order); this saver's object manager is the first member's."""
+        from ... import ops as O
+        if self.save_scores:
+            raise ValueError('process_merged writes no scores: save_scores and the merge exclude each other')
+        if self.processor is None:
+            raise ValueError('process_merged needs the processor (its device; the merge has no host implementation)')
+        own = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items()}
+        for m in (id_maps or ()):
+            if {int(t): int(o) for t, o in m.items()} != own:
+                raise ValueError(f'process_merged: the members disagree on tmp id -> object id ({m} against {own})')
+        probs = list(probs)
+        if not 1 <= len(probs) <= O.OpList.MERGE_MAX_SOURCES:
+            raise ValueError(f'process_merged: {len(probs)} members, 1 .. {O.OpList.MERGE_MAX_SOURCES}')
+        dev = self.processor.network.device
+        P = int(probs[0].shape[0])
+        if any(int(p.shape[0]) != P for p in probs):
+            raise ValueError('process_merged: the members disagree on the number of planes')
+        H, W = int(shape[0]), int(shape[1])
+        lut = [0] * P
+        for tmp_id, obj_id in own.items():
+            if tmp_id < P:
+                lut[tmp_id] = obj_id
+        device_egress = self.egress == 'device'
+        if max(lut) > 255 and (device_egress or not self.use_long_id):
+            raise ValueError('object ids above 255 need use_long_id')
+        lut_dev = self._luts.get(tuple(lut))
+        if lut_dev is None:                      # (changes when objects come or go, not per frame)
+            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
+        probs = [p if (p.dtype == torch.float32 and p.device == dev and p.stride(2) == 1) else p.to(device=dev, dtype=torch.float32).contiguous()
+                 for p in probs]
+        ol = O.OpList()
+        all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
+        if not device_egress:
+            ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=dev)
+            ol.prob_to_id_merged(probs, lut_dev, ids, out_hw=(H, W))
+            ol.run()
+            self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame))
+            return
+        if self._scratch is None or self._scratch[0] != (H, W):
+            self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+        b = self._take(H, W, dev)
+        ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W), png=(b.stream, b.status, self._scratch[1]))
+        ol.run()
+        b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
+        b.event.record()
+        self.queue.put(_Job(self, None, frame_name, None, all_ids, last_frame=last_frame, egress=b))
+
     def _fetch(self, b: _EgressBuffers) -> bytes:
         """Writer thread: the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
         b.event.synchronize()

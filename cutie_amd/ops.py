@@ -829,6 +829,56 @@ class OpList:
         ints += [0] * (7 - len(ints)) + [stream.numel(), scratch.numel()]
         return self.add(PROB_TO_ID, code | 8, ints, [], [prob, lut, out, stream, status, scratch])
 
+    MERGE_MAX_SOURCES = 8     # CUTIE_MERGE_MAX_SOURCES (include/cutie_hip.h)
+    MERGE_TABLES = 64         # cached table pairs (a frame-slot pool hands a member's planes out at a few addresses in turn)
+    _merge_tables = {}        # (device, stream, ((data_ptr, shape, strides), ...)) -> (u64 [S] plane pointers, i32 [S, 4] geometry)
+
+    @classmethod
+    def merge_tables(cls, probs):
+        """The two device tables of a merge (PROB_TO_ID flags&16): plane pointers and (H, W, plane stride, row stride) per source.  They
+        change when a buffer changes, not per frame: cached per (data_ptr, shape, strides) of every source -- and per stream: a table
+        that is dropped goes back to the allocator of the stream that built it, behind the launches that read it."""
+        dev = probs[0].device
+        sig = tuple((t.data_ptr(), tuple(t.shape), tuple(t.stride())) for t in probs)
+        key = (str(dev), torch.cuda.current_stream(dev).cuda_stream if dev.type == 'cuda' else 0, sig)
+        tabs = cls._merge_tables.get(key)
+        if tabs is None:
+            while len(cls._merge_tables) >= cls.MERGE_TABLES:
+                cls._merge_tables.pop(next(iter(cls._merge_tables)), None)
+            ptrs = torch.from_numpy(np.array([t.data_ptr() for t in probs], dtype=np.uint64).view(np.int64)).to(dev)
+            geom = torch.tensor([[t.shape[1], t.shape[2], t.stride(0), t.stride(1)] for t in probs], dtype=torch.int32).to(dev)
+            tabs = cls._merge_tables[key] = (ptrs, geom)
+        return tabs
+
+    def prob_to_id_merged(self, probs, lut, out, *, out_hw, png=None):
+        """PROB_TO_ID flags 4 | 16 (ABI 8, include/cutie_hip.h): the ids of S sources merged -- probs = list of f32 [P, h_s, w_s] (any
+        plane / row strides, last dimension contiguous: the un-padded views `step` returns are read in place), every one resampled
+        bilinearly to out_hw, quantised like (x * 255).to(uint8) and summed as integers; out [OH, OW] uint8 / int32 = lut[first largest
+        sum].  png = (stream, status, scratch) as in prob_to_id.  The caller keeps the sources alive until the launch has run."""
+        S = len(probs)
+        if not 1 <= S <= self.MERGE_MAX_SOURCES:
+            raise ValueError(f'prob_to_id_merged: {S} sources, 1 <= S <= {self.MERGE_MAX_SOURCES}')
+        P = int(probs[0].shape[0])
+        for t in probs:
+            if t.dim() != 3 or t.dtype != torch.float32 or t.shape[0] != P or t.stride(2) != 1 or t.device != probs[0].device or t.shape[1] < 1 or t.shape[2] < 1:
+                raise ValueError('prob_to_id_merged: sources are f32 [P, h, w] of one P and device with a contiguous last dimension')
+            if max(t.stride(0), t.stride(1)) >= 1 << 31:
+                raise ValueError('prob_to_id_merged: strides are 32-bit')
+        if out.dtype not in (torch.uint8, torch.int32):
+            raise ValueError('prob_to_id_merged: out is uint8 or int32')
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        if tuple(out.shape) != (OH, OW) or not out.is_contiguous():
+            raise ValueError('prob_to_id_merged: out is a contiguous [OH, OW]')
+        code = {torch.uint8: 0, torch.int32: 1}[out.dtype] | 4 | 16
+        ptrs, geom = self.merge_tables(probs)
+        self.keep.extend(probs)
+        ints = [P, 0, 0, 0, 0, OH, OW, 0, 0, S]
+        if png is None:
+            return self.add(PROB_TO_ID, code, ints, [], [ptrs, lut, out, None, None, None, geom])
+        stream, status, scratch = png
+        ints[7], ints[8] = stream.numel(), scratch.numel()
+        return self.add(PROB_TO_ID, code | 8, ints, [], [ptrs, lut, out, stream, status, scratch, geom])
+
     @staticmethod
     def png_capacity(H, W):
         """Bytes that hold the zlib stream of ANY uint8 plane [H, W]: with the fixed Huffman codes a filtered byte costs at most 9 bits;

@@ -27,6 +27,7 @@ extern "C" {
 #define CUTIE_OP_NI 24
 #define CUTIE_OP_NF 6
 #define CUTIE_OP_NP 16
+#define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
 
 typedef struct cutie_op {
     int32_t kind;               /* CUTIE_OP_* */
@@ -322,7 +323,20 @@ enum {
      *    p4 = status int32 [4], written by the launch: 0 stream bytes, 1 Adler-32, 2 error bits (1: the stream does not fit the capacity;
      *    NOTHING is written to p3 then -- with i7 < 4 it may be null --, [0] still says what it needs), 3 zero.  p5 = int32 scratch of i8 words, 16-byte aligned,
      *    i8 >= H * (4 + ceil(9 (W + 1) / 32) + 2).  W <= 32767 (a row is one match distance).  The bytes depend on the plane alone.
-     *    cutie_amd/inference/utils/png.py wraps the stream into a file (signature, IHDR, PLTE, one IDAT, IEND). */
+     *    cutie_amd/inference/utils/png.py wraps the stream into a file (signature, IHDR, PLTE, one IDAT, IEND).
+     * ABI 8 -- multi-scale merge on the device (scripts/merge_multi_scale.py of the reference: the uint8 score dumps of several runs are
+     *    summed and the argmax of the sum is the mask; ResultSaver.process_merged, eval_vos --sizes); flags other than 1 | 2 | 4 | 8 | 16 are
+     *    an error:
+     *  flags&16: the ids of S sources merged.  Per output pixel and plane q: sum[q] = sum over the sources s of (int)(uint8)(sample_s * 255.f)
+     *    -- sample_s = exactly the flags&4 (= RESIZE flags == 0) sample of source s at the pixel, quantised by TRUNCATION as
+     *    (prob * 255).to(torch.uint8) / numpy astype(uint8) do -- in 32-bit integers, so the result depends neither on the order of the
+     *    sources nor on the launch shape; id = lut[first q with the largest sum].  Every source has its own size and strides; one whose size
+     *    equals the output samples itself exactly.  flags&4 MUST accompany flags&16 (the output geometry is that path's i5 x i6; 16 alone is
+     *    an error); flags&3 is 0 | 1 (u8 | i32; 2 is an error); combines with flags&8 (unchanged).  Slots that differ from the above:
+     *    p0 = u64 [S] device table: the sources' first planes (f32, P planes each, last dimension contiguous), 8-byte aligned
+     *    p6 = i32 [S, 4] device table, 16-byte aligned: per source H, W, plane stride, row stride (elements; H, W >= 1 -- a source that says
+     *    otherwise is left out of the sum)       i9 = S, 1 <= S <= CUTIE_MERGE_MAX_SOURCES       i1 .. i4 unused.
+     *    The launcher checks what it can see (flags, S, null / misaligned tables, P, OH, OW); the tables' contents are the caller's. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).

@@ -2,6 +2,11 @@
 first-mask alignment, ``end`` on the last frame, FPS = frames / sum of device-event time around ``step``), on top of
 ``VOSTestDataset`` / ``VideoReader`` / ``ResultSaver``.
 
+Three drivers -- ``process_video``, ``process_video_multiscale``, ``process_videos_lockstep`` -- over one copy of each piece: ``_feed``
+(decode threads -> the device look-ahead window, inference/data/prefetch.py ``Window``) and ``_take`` (a frame's record, mask, valid
+labels and hints), ``timed_step`` (the FPS protocol), ``_saver`` / ``_save``, and ``_run_video``: the frames of one video on its
+member cores -- the whole of the first two drivers and the tail of a lock-step group.
+
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
         [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device]      (multi-scale testing: one run per --size with --save-scores, then
@@ -14,7 +19,7 @@ import argparse
 import logging
 import os
 import time
-from collections import deque
+from contextlib import nullcontext
 from os import path
 from typing import Dict
 
@@ -22,7 +27,7 @@ import torch
 
 from .config import default_config
 from .inference.data.device_ingest import finish, to_device
-from .inference.data.prefetch import ReadAhead
+from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
@@ -31,160 +36,20 @@ from .inference.utils.results_utils import EGRESS_MODES, ResultSaver, make_zip
 log = logging.getLogger()
 
 
-def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
-                  visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host') -> Dict:
-    """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
-    ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
-    egress: 'host' | 'device' (ResultSaver(egress=...): the GPU writes the masks' PNG streams)."""
-    _check_ingest(ingest)
-    processor = InferenceCore(network, cfg=cfg)
-    saver = ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=processor.object_manager,
-                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
-                        visualize_output_root=visualize_output_root, processor=processor, save_scores=save_scores,
-                        score_output_root=score_output_root, egress=egress)
-    dev = network.device
-    on_gpu = dev.type == 'cuda'
-    n = len(vid_reader)
-    total, frames, first_mask_loaded = 0.0, 0, False
-    try:
-        loader = iter(_read_ahead(vid_reader, read_workers, ingest))   # decode runs ahead on threads (eval_vos.py:92)
-        # the frames of the following steps, already on the device: step(next_images=...) runs the image encoder over a window of them
-        # (InferenceCore.prefetch_window); the SAME tensors are handed to the later steps (the look-ahead matches frames by storage)
-        from .inference import inference_core as IC
-        depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
-        ahead = deque()
-
-        def fill():
-            while len(ahead) < depth:
-                d = next(loader, None)
-                if d is None:
-                    break
-                ahead.append(to_device(d, dev, defer_check=True))      # (checked when it leaves the window)
-
-        fill()
-        for ti in range(n):
-            data = finish(ahead.popleft())
-            fill()
-            image = data['rgb']
-            next_images = [d['rgb'] for d in ahead] if (lookahead and ahead) else None
-            mask = data.get('mask')
-            mask = mask.to(dev) if mask is not None else None
-            valid = data.get('valid_labels')
-            valid = valid.tolist() if valid is not None else None
-            info = data['info']
-            if not first_mask_loaded:
-                if mask is None:
-                    continue                                  # nothing to do before the first mask
-                first_mask_loaded = True
-            if on_gpu:
-                torch.cuda.synchronize()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            else:
-                t0 = time.perf_counter()
-            prob = processor.step(image, mask, valid, end=(ti == n - 1), next_images=next_images)
-            if on_gpu:
-                e1.record()
-                torch.cuda.synchronize()
-                total += e0.elapsed_time(e1) / 1000
-            else:
-                total += time.perf_counter() - t0
-            frames += 1
-            if save_all or info['save']:
-                saver.process(prob, info['frame'], resize_needed=info['resize_needed'], shape=info['shape'],
-                              last_frame=(ti == n - 1), path_to_image=info['path_to_image'])
-    finally:
-        saver.end()
-    return {'frames': frames, 'seconds': total}
-
-
-def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
-                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host') -> Dict:
-    """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
-    scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
-    One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
-    and frame context; per member exactly ``process_video``'s handling -- and after the S steps of a frame ``ResultSaver.process_merged``
-    sums the members' quantised probabilities at the original size and writes the mask (one kernel; no score files, no full-size plane).
-    The members' probabilities stay referenced until the merge has been issued: a pooled plan output that somebody holds is not recycled
-    (plans.SlotPool), and everything runs on the caller's stream.  Returns {'frames', 'seconds'}; seconds = the sum over the members."""
-    _check_ingest(ingest)
-    if save_scores:
-        raise ValueError('process_video_multiscale merges on the device and writes no scores: save_scores is not supported')
-    from . import frame_context
-    from .inference import inference_core as IC
-    S = len(vid_readers)
-    if S < 1:
-        raise ValueError('process_video_multiscale needs at least one reader')
-    rd0 = vid_readers[0]
-    n = len(rd0)
-    if any(rd.vid_name != rd0.vid_name or len(rd) != n for rd in vid_readers):
-        raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
-    cores = [InferenceCore(network, cfg=cfg) for _ in range(S)]
-    ctxs = [frame_context.new_context() for _ in range(S)]
-    for s, core in enumerate(cores):
-        core.memory._clip_tag = s                # (its own read-out slots in the engine's pool, as the clips of a lock-step group)
-    saver = ResultSaver(mask_output_root, rd0.vid_name, dataset=dataset, object_manager=cores[0].object_manager,
-                        use_long_id=rd0.use_long_id, palette=rd0.get_palette(), visualize=visualize,
-                        visualize_output_root=visualize_output_root, processor=cores[0], egress=egress)
-    dev = network.device
-    on_gpu = dev.type == 'cuda'
-    total, frames, first_mask_loaded = 0.0, 0, False
-    try:
-        loaders = [iter(_read_ahead(rd, read_workers, ingest)) for rd in vid_readers]
-        depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
-        ahead = [deque() for _ in range(S)]
-
-        def fill(s):
-            while len(ahead[s]) < depth:
-                d = next(loaders[s], None)
-                if d is None:
-                    break
-                ahead[s].append(to_device(d, dev, defer_check=True))
-
-        for s in range(S):
-            fill(s)
-        for ti in range(n):
-            data = [finish(ahead[s].popleft()) for s in range(S)]
-            for s in range(S):
-                fill(s)
-            info = data[0]['info']
-            if any(d['info']['frame'] != info['frame'] or tuple(d['info']['shape']) != tuple(info['shape']) for d in data):
-                raise ValueError(f"process_video_multiscale: the readers disagree on frame {ti} ({[d['info']['frame'] for d in data]})")
-            if not first_mask_loaded:
-                if data[0].get('mask') is None:
-                    continue                                  # nothing to do before the first mask
-                first_mask_loaded = True
-            probs = []
-            for s, (core, d) in enumerate(zip(cores, data)):
-                mask = d.get('mask')
-                mask = mask.to(dev) if mask is not None else None
-                valid = d.get('valid_labels')
-                valid = valid.tolist() if valid is not None else None
-                next_images = [x['rgb'] for x in ahead[s]] if (lookahead and ahead[s]) else None
-                if on_gpu:
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                else:
-                    t0 = time.perf_counter()
-                with frame_context.context(ctxs[s]):
-                    probs.append(core.step(d['rgb'], mask, valid, end=(ti == n - 1), next_images=next_images))
-                if on_gpu:
-                    e1.record()
-                    torch.cuda.synchronize()
-                    total += e0.elapsed_time(e1) / 1000
-                else:
-                    total += time.perf_counter() - t0
-            frames += 1
-            if save_all or info['save']:
-                saver.process_merged(probs, info['frame'], info['shape'], last_frame=(ti == n - 1), path_to_image=info['path_to_image'],
-                                     id_maps=[{t: o.id for t, o in c.object_manager.tmp_id_to_obj.items()} for c in cores])
-            del probs
-    finally:
-        saver.end()
-    return {'frames': frames, 'seconds': total}
+def timed_step(fn, on_gpu):
+    """-> (fn(), seconds): the reference's FPS protocol around one ``step`` (eval_vos.py:126-145: synchronize, event, step, event,
+    synchronize); wall seconds on a CPU device."""
+    if not on_gpu:
+        t0 = time.perf_counter()
+        out = fn()
+        return out, time.perf_counter() - t0
+    torch.cuda.synchronize()
+    e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return out, e0.elapsed_time(e1) / 1000
 
 
 def _check_ingest(ingest):
@@ -197,6 +62,127 @@ def _read_ahead(vid_reader, workers, ingest):
     if ingest is None:
         return ReadAhead(vid_reader, workers=workers)
     return ReadAhead(vid_reader, workers=workers, getitem=lambda i: vid_reader.get(i, ingest=ingest))
+
+
+def _feed(vid_reader, dev, depth, read_workers, ingest) -> Window:
+    """The records of a video: decoded ahead on threads (eval_vos.py:92), then up to ``depth`` of them on the device ahead of the step
+    that takes them (uploaded as they enter the window, their deferred decode check made as they leave it)."""
+    return Window(_read_ahead(vid_reader, read_workers, ingest), lambda d: to_device(d, dev, defer_check=True), finish, depth)
+
+
+def _take(window, dev, lookahead):
+    """The next frame of a feed -> (record, its mask on the device or None, its valid labels or None, hints or None).  The hints are
+    the frames of the following steps, already on the device: step(next_images=...) runs the image encoder over a window of them
+    (InferenceCore.prefetch_window); the SAME tensors come with the later records (the look-ahead matches frames by storage)."""
+    d = window.pop()
+    mask, valid = d.get('mask'), d.get('valid_labels')
+    hints = [x['rgb'] for x in window.queued] if (lookahead and window.queued) else None
+    return d, (mask.to(dev) if mask is not None else None), (valid.tolist() if valid is not None else None), hints
+
+
+def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
+           score_output_root=None) -> ResultSaver:
+    return ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=core.object_manager,
+                       use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
+                       visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
+                       score_output_root=score_output_root, egress=egress)
+
+
+def _save(saver, prob, info, last_frame, save_all):
+    if save_all or info['save']:
+        saver.process(prob, info['frame'], resize_needed=info['resize_needed'], shape=info['shape'], last_frame=last_frame,
+                      path_to_image=info['path_to_image'])
+
+
+def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
+    """Frames start .. n-1 of ONE video (eval_vos.py:97-151) on its member cores, stepped one after another per frame: one member for
+    process_video and for a video that outlives its lock-step group, the S scales for process_video_multiscale.  members[s]() enters
+    what member s runs in and gives its InferenceCore; feeds[s] is its window of records.  Frames before the first mask of a video
+    that starts here are not stepped; ``end`` comes with the last frame; save(probs, info, last_frame) receives the members'
+    probabilities of every stepped frame, which stay referenced until it returns.  stats: 'frames' += 1 per stepped frame, 'seconds'
+    += the time around every member's step."""
+    on_gpu = dev.type == 'cuda'
+    first_mask_loaded = start > 0
+    for ti in range(start, n):
+        taken = [_take(w, dev, lookahead) for w in feeds]
+        info = taken[0][0]['info']
+        if any(d['info']['frame'] != info['frame'] or tuple(d['info']['shape']) != tuple(info['shape']) for d, *_ in taken):
+            raise ValueError(f"process_video_multiscale: the readers disagree on frame {ti} ({[d['info']['frame'] for d, *_ in taken]})")
+        if not first_mask_loaded:
+            if taken[0][1] is None:
+                continue                                  # nothing to do before the first mask
+            first_mask_loaded = True
+        probs = []
+        for enter, (d, mask, valid, hints) in zip(members, taken):
+            with enter() as core:
+                prob, secs = timed_step(lambda: core.step(d['rgb'], mask, valid, end=(ti == n - 1), next_images=hints), on_gpu)
+            probs.append(prob)
+            stats['seconds'] += secs
+        stats['frames'] += 1
+        save(probs, info, ti == n - 1)
+
+
+def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
+                  visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
+                  read_workers=4, ingest=None, egress='host') -> Dict:
+    """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
+    ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
+    egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams)."""
+    _check_ingest(ingest)
+    from .inference import inference_core as IC
+    processor = InferenceCore(network, cfg=cfg)
+    saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
+                   egress=egress, save_scores=save_scores, score_output_root=score_output_root)
+    stats = {'frames': 0, 'seconds': 0.0}
+    try:
+        feed = _feed(vid_reader, network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest)
+        _run_video([lambda: nullcontext(processor)], [feed], len(vid_reader), 0, stats,
+                   lambda probs, info, last: _save(saver, probs[0], info, last, save_all), dev=network.device, lookahead=lookahead)
+    finally:
+        saver.end()
+    return stats
+
+
+def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
+                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
+                             read_workers=4, ingest=None, egress='host') -> Dict:
+    """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
+    scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
+    One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
+    and frame context (``ClipCores``); per member exactly ``process_video``'s handling (``_run_video``) -- and after the S steps of a frame
+    ``ResultSaver.process_merged`` sums the members' quantised probabilities at the original size and writes the mask (one kernel; no
+    score files, no full-size plane).
+    The members' probabilities stay referenced until the merge has been issued: a pooled plan output that somebody holds is not recycled
+    (plans.SlotPool), and everything runs on the caller's stream.  Returns {'frames', 'seconds'}; seconds = the sum over the members."""
+    _check_ingest(ingest)
+    if save_scores:
+        raise ValueError('process_video_multiscale merges on the device and writes no scores: save_scores is not supported')
+    from .inference import inference_core as IC
+    from .inference.lockstep import ClipCores
+    S = len(vid_readers)
+    if S < 1:
+        raise ValueError('process_video_multiscale needs at least one reader')
+    rd0 = vid_readers[0]
+    n = len(rd0)
+    if any(rd.vid_name != rd0.vid_name or len(rd) != n for rd in vid_readers):
+        raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
+    members = ClipCores(network, cfg, S)
+    saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
+                   egress=egress)
+
+    def save(probs, info, last_frame):
+        if save_all or info['save']:
+            saver.process_merged(probs, info['frame'], info['shape'], last_frame=last_frame, path_to_image=info['path_to_image'],
+                                 id_maps=[{t: o.id for t, o in c.object_manager.tmp_id_to_obj.items()} for c in members.cores])
+
+    stats = {'frames': 0, 'seconds': 0.0}
+    try:
+        depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
+        feeds = [_feed(rd, network.device, depth, read_workers, ingest) for rd in vid_readers]
+        _run_video([lambda s=s: members.clip(s) for s in range(S)], feeds, n, 0, stats, save, dev=network.device, lookahead=lookahead)
+    finally:
+        saver.end()
+    return stats
 
 
 def lockstep_key(vid_reader):
@@ -217,84 +203,34 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
     (the seconds of a lock-step frame are split evenly over its videos)."""
     _check_ingest(ingest)
-    from .inference import inference_core as IC
     from .inference.lockstep import LockstepCores
-    from . import frame_context
     C = len(vid_readers)
     ls = LockstepCores(network, cfg, C)
     dev = network.device
-    on_gpu = dev.type == 'cuda'
-    savers = [ResultSaver(mask_output_root, rd.vid_name, dataset=dataset, object_manager=ls.cores[c].object_manager, use_long_id=rd.use_long_id,
-                          palette=rd.get_palette(), visualize=visualize, visualize_output_root=visualize_output_root, processor=ls.cores[c],
-                          save_scores=save_scores, score_output_root=score_output_root, egress=egress) for c, rd in enumerate(vid_readers)]
+    savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
+                     egress=egress, save_scores=save_scores, score_output_root=score_output_root) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
-    depth = 16 if lookahead else 1
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
-
-    def timed(fn):
-        if on_gpu:
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            out = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return out, e0.elapsed_time(e1) / 1000
-        t0 = time.perf_counter()
-        out = fn()
-        return out, time.perf_counter() - t0
-
     try:
-        loaders = [iter(_read_ahead(rd, read_workers, ingest)) for rd in vid_readers]
-        ahead = [deque() for _ in range(C)]
-
-        def fill(c):
-            while len(ahead[c]) < depth:
-                d = next(loaders[c], None)
-                if d is None:
-                    break
-                ahead[c].append(to_device(d, dev, defer_check=True))
-
-        for c in range(C):
-            fill(c)
+        feeds = [_feed(rd, dev, 16 if lookahead else 1, read_workers, ingest) for rd in vid_readers]
         for ti in range(T):
-            data = [finish(ahead[c].popleft()) for c in range(C)]
-            for c in range(C):
-                fill(c)
-            masks = [d['mask'].to(dev) if d.get('mask') is not None else None for d in data]
-            valid = [d['valid_labels'].tolist() if d.get('valid_labels') is not None else None for d in data]
+            data, masks, valid, hints = (list(v) for v in zip(*[_take(w, dev, lookahead) for w in feeds]))
             any_mask = any(m is not None for m in masks)
             hint = None
-            if lookahead and not any_mask and all(len(a) > 0 for a in ahead) and ti < T - 1:
-                n = min(min(len(a) for a in ahead), T - 1 - ti)
-                hint = [[d['rgb'] for d in list(a)[:n]] for a in ahead]
-            end = all(ti == n_ - 1 for n_ in lens)
-            probs, secs = timed(lambda: ls.step([d['rgb'] for d in data], masks if any_mask else None, valid if any_mask else None,
-                                                end=end, next_images=hint))
+            if all(h is not None for h in hints) and not any_mask and ti < T - 1:
+                n = min(min(len(h) for h in hints), T - 1 - ti)
+                hint = [h[:n] for h in hints]
+            end = all(ti == n_ - 1 for n_ in lens)          # (open, ADVICE.md: a shorter video of an unequal group never gets end=True)
+            probs, secs = timed_step(lambda: ls.step([d['rgb'] for d in data], masks if any_mask else None, valid if any_mask else None,
+                                                     end=end, next_images=hint), dev.type == 'cuda')
             for c in range(C):
                 stats[c]['frames'] += 1
                 stats[c]['seconds'] += secs / C
-                info = data[c]['info']
-                if save_all or info['save']:
-                    savers[c].process(probs[c], info['frame'], resize_needed=info['resize_needed'], shape=info['shape'],
-                                      last_frame=(ti == lens[c] - 1), path_to_image=info['path_to_image'])
+                _save(savers[c], probs[c], data[c]['info'], ti == lens[c] - 1, save_all)
         for c in range(C):                                   # the videos longer than the shortest one: on their own cores
-            core = ls.cores[c]
-            with frame_context.context(ls._ctx[c]):
-                for ti in range(T, lens[c]):
-                    d = finish(ahead[c].popleft())
-                    fill(c)
-                    nxt = [x['rgb'] for x in ahead[c]] if (lookahead and ahead[c]) else None
-                    mask = d['mask'].to(dev) if d.get('mask') is not None else None
-                    val = d['valid_labels'].tolist() if d.get('valid_labels') is not None else None
-                    prob, secs = timed(lambda: core.step(d['rgb'], mask, val, end=(ti == lens[c] - 1), next_images=nxt))
-                    stats[c]['frames'] += 1
-                    stats[c]['seconds'] += secs
-                    info = d['info']
-                    if save_all or info['save']:
-                        savers[c].process(prob, info['frame'], resize_needed=info['resize_needed'], shape=info['shape'],
-                                          last_frame=(ti == lens[c] - 1), path_to_image=info['path_to_image'])
+            _run_video([lambda: ls.clip(c)], [feeds[c]], lens[c], T, stats[c],
+                       lambda probs, info, last: _save(savers[c], probs[0], info, last, save_all), dev=dev, lookahead=lookahead)
     finally:
         for s in savers:
             s.end()
@@ -370,18 +306,16 @@ def main():
     readers = list(meta.get_datasets())
     mine = shard_clips(len(readers), rank, world)
     mask_root = path.join(args.output, 'Annotations')
-    run = lambda view, c: process_video(view, cfg, readers[c], mask_root, dataset=args.dataset, visualize=args.visualize,
-                                        visualize_output_root=path.join(args.output, 'Visualizations'),
-                                        save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'),
-                                        read_workers=args.read_workers, egress=args.egress)
+    common = dict(dataset=args.dataset, visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
+                  save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
+                  egress=args.egress)                         # (no ingest=: the readers carry the mode)
+    run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is
         # scales[s][c] -- every dataset lists the folder in the same sorted order
         scales = [list(VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=sz, subset=args.subset,
                                       ingest=args.ingest).get_datasets()) for sz in args.sizes]
-        run = lambda view, c: process_video_multiscale(view, cfg, [sc[c] for sc in scales], mask_root, dataset=args.dataset,
-                                                       visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
-                                                       read_workers=args.read_workers, egress=args.egress)
+        run = lambda view, c: process_video_multiscale(view, cfg, [sc[c] for sc in scales], mask_root, **common)   # (check_args: no --save-scores here)
     res = {}
     with torch.inference_mode():
         if args.lockstep > 1 and not args.flip_aug:
@@ -400,10 +334,7 @@ def main():
                     if len(grp) >= 2:
                         grouped.append(grp)
             for grp in grouped:
-                st = process_videos_lockstep(net, cfg, [readers[c] for c in grp], mask_root, dataset=args.dataset, visualize=args.visualize,
-                                             visualize_output_root=path.join(args.output, 'Visualizations'), save_scores=args.save_scores,
-                                             score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
-                                             egress=args.egress)
+                st = process_videos_lockstep(net, cfg, [readers[c] for c in grp], mask_root, **common)
                 for j, c in enumerate(grp):
                     res[c] = st[j]
             mine = [c for c in mine if c not in res]

@@ -2,7 +2,8 @@
 works on earlier frames.  This is what ``DataLoader(vid_reader, batch_size=None, num_workers=4)`` does in the reference's
 eval loop (cutie/eval_vos.py:92) -- threads instead of worker processes: PIL and torch release the GIL while decoding /
 resizing, nothing has to be pickled, and the items arrive in index order with at most ``depth`` decoded frames alive.
-A model at several hundred frames/s is otherwise limited by single-threaded JPEG decode (3-5 ms per 480p frame)."""
+A model at several hundred frames/s is otherwise limited by single-threaded JPEG decode (3-5 ms per 480p frame).
+``Window`` is the stage behind it in the drivers: the next few records already uploaded to the device."""
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
 from typing import Callable, Iterator, Optional
@@ -41,3 +42,29 @@ class ReadAhead:
             for f in pending:
                 f.cancel()
             pool.shutdown(wait=True)
+
+
+class Window:
+    """The device look-ahead window of a driver: up to ``depth`` records of an iterator are queued, ``upload(record)`` runs when a
+    record enters and ``check(queued record)`` when it leaves through ``pop`` (a deferred decode check: the host does not wait for
+    every decode).  ``queued`` holds what is still waiting, in order; a caller builds its ``next_images`` hints from it -- the
+    same objects arrive later through ``pop``, which is what the look-ahead of ``InferenceCore.step`` matches frames by."""
+
+    def __init__(self, records, upload: Callable, check: Callable, depth: int):
+        self.records, self.upload, self.check, self.depth = iter(records), upload, check, max(1, depth)
+        self.queued = deque()
+        self._fill()
+
+    def _fill(self):
+        while len(self.queued) < self.depth:
+            try:
+                record = next(self.records)
+            except StopIteration:
+                return
+            self.queued.append(self.upload(record))
+
+    def pop(self):
+        """The oldest queued record, checked; the window is filled up again behind it."""
+        record = self.check(self.queued.popleft())
+        self._fill()
+        return record

@@ -42,7 +42,24 @@ from .inference_core import InferenceCore, pad_geometry, unpad
 BF16, F32 = torch.bfloat16, torch.float32
 
 
-class LockstepCores:
+class ClipCores:
+    """n ``InferenceCore``s side by side on one network: each with its own frame context and its own read-out slots in the engine's
+    pool (the tag of its ``MemoryManager``).  The clips of a lock-step group; the scales of eval_vos.process_video_multiscale."""
+
+    def __init__(self, network, cfg, n: int):
+        self.cores = [InferenceCore(network, cfg) for _ in range(n)]
+        for c, core in enumerate(self.cores):
+            core.memory._clip_tag = c
+        self._ctx = [frame_context.new_context() for _ in range(n)]
+
+    @contextlib.contextmanager
+    def clip(self, c: int):
+        """with cores.clip(c) as core: clip c's own ``InferenceCore`` inside its frame context (to step it on its own)."""
+        with frame_context.context(self._ctx[c]):
+            yield self.cores[c]
+
+
+class LockstepCores(ClipCores):
     # frames of every clip per batched encoder plan (C x WINDOW frames per plan) / encoded frames left ahead when the next batch starts
     # (defaults set per group size in __init__: clips x WINDOW ~ 12 frames per plan, the batch the conv tile table was swept for)
     WINDOW = int(os.environ.get('CUTIE_AMD_LS_WINDOW', '0'))
@@ -52,14 +69,11 @@ class LockstepCores:
     JOINT = os.environ.get('CUTIE_AMD_LS_JOINT', '1') not in ('', '0')
 
     def __init__(self, network, cfg, clips: int):
+        super().__init__(network, cfg, clips)
         self.network = network
         self.cfg = cfg
-        self.cores = [InferenceCore(network, cfg) for _ in range(clips)]
         if self.WINDOW <= 0:
             self.WINDOW = max(1, round(12 / clips))
-        for c, core in enumerate(self.cores):
-            core.memory._clip_tag = c
-        self._ctx = [frame_context.new_context() for _ in range(clips)]
         self._state = None              # (sens_f32 [C*K,h,w,CS], sens_bf16, objv [C*K,Q,CE+1]): the stacked per-object state of the group
         self._md_valid = False          # Engine.mask_down_bufs hold MASK_DOWN of the current last masks (written by the batched segment)
         self._qtoken = None             # content tokens of the object summaries the transformer's queries were initialised from

@@ -214,7 +214,6 @@ def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight
     the clips of a group should share geometry, object count and length (a group whose clips differ still runs -- clip by clip where the
     states differ, see LockstepCores).  on_frame(clip_index, t, prob, core) receives every result (default: the uint8 object-id masks are
     collected).  Returns {clip index: [per-frame results]}."""
-    from . import frame_context
     from .inference.lockstep import LockstepCores
     results: Dict[int, List] = {i: [] for i in range(len(clips))}
     if on_frame is None:
@@ -232,7 +231,7 @@ def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight
             hint = {}
             if lookahead > 0 and 0 < t < T - 1:
                 hint = dict(next_images=[[f[j] for j in range(t + 1, min(T, t + 1 + lookahead))] for f in frames])
-            end = all(t == len(f) - 1 for f in frames)
+            end = all(t == len(f) - 1 for f in frames)      # (open, ADVICE.md: a shorter clip of an unequal group never gets end=True)
             if t == 0:
                 probs = ls.step([f[0] for f in frames], [clips[i]['mask'] for i in group], [clips[i]['objects'] for i in group], end=end)
             else:
@@ -242,9 +241,9 @@ def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight
             yield
         for c, i in enumerate(group):                       # clips longer than the shortest of their group: the rest on their own
             f = frames[c]
-            with frame_context.context(ls._ctx[c]):
+            with ls.clip(c) as core:
                 for t in range(T, len(f)):
-                    on_frame(i, t, ls.cores[c].step(f[t], end=(t == len(f) - 1)), ls.cores[c])
+                    on_frame(i, t, core.step(f[t], end=(t == len(f) - 1)), core)
                     yield
         return None
 

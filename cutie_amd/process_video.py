@@ -4,7 +4,9 @@
 1. every mask in ``--mask_dir`` (``<frame number, 7 digits>.png``; palette 'P', 'L' or RGB long ids) is committed to
    PERMANENT memory first: ``step(frame, one_hot[1:], idx_mask=False, force_permanent=True)`` (:94-120);
 2. the video then runs from frame 0; frames that have a mask are stepped with it, the others propagate (:139-176); every
-   output goes through ``ResultSaver`` (fused argmax + id remap on the device, PNG encoding on a writer thread);
+   output goes through ``ResultSaver`` (fused argmax + id remap on the device, PNG encoding on a writer thread); the next frame
+   is uploaded one step ahead (``prefetch.Window``, depth 1) and the time is taken around ``step`` by ``eval_vos.timed_step``
+   (device events on the GPU, wall seconds on a CPU device);
 3. ``--mem_cleanup_ratio r``: when used / total device memory exceeds r the non-permanent memory is cleared (:214-228).
 
 Frame source: a directory of images (sorted by name) or, when OpenCV is importable, a video file.  Differences from the
@@ -30,9 +32,10 @@ import torch
 from PIL import Image
 
 from .config import default_config
+from .eval_vos import timed_step
 from .inference.data import jpeg
 from .inference.data.device_ingest import frame_to_device, jpeg_to_device
-from .inference.data.prefetch import ReadAhead
+from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
 from .inference.utils.results_utils import EGRESS_MODES, ResultSaver
@@ -176,7 +179,6 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     if num_objects is None or num_objects < 1:
         num_objects = len(np.unique(index_mask(mask_names[0]))) - 1
     processor = InferenceCore(network, cfg=cfg)
-    on_gpu = dev.type == 'cuda'
     with torch.inference_mode():
         # 1. commit the annotated frames to permanent memory
         for name in mask_names:
@@ -190,25 +192,15 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             palette=palette, processor=processor, egress=egress)
         total, n, cleanups = 0.0, 0, 0
         try:
-            it = iter(src)
-            nxt = next(it, None)
-            nxt = upload(nxt) if nxt is not None else None
-            while nxt is not None:
-                frame, nxt = checked(nxt), next(it, None)
-                nxt = upload(nxt) if nxt is not None else None
+            ahead = Window(src, upload, checked, 1)           # the next frame is on the device while this one is stepped
+            while ahead.queued:
+                frame = ahead.pop()
                 name = f'{n:07d}.png'
                 mask = one_hot_planes(index_mask(name), num_objects, dev) if path.exists(path.join(mask_dir, name)) else None
-                if on_gpu:
-                    torch.cuda.synchronize()
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                hint = nxt[0] if (lookahead and nxt is not None) else None
-                prob = processor.step(frame, mask, idx_mask=False, next_image=hint) if mask is not None \
-                    else processor.step(frame, next_image=hint)
-                if on_gpu:
-                    e1.record()
-                    torch.cuda.synchronize()
-                    total += e0.elapsed_time(e1) / 1000
+                hint = ahead.queued[0][0] if (lookahead and ahead.queued) else None
+                prob, secs = timed_step(lambda: processor.step(frame, mask, idx_mask=False, next_image=hint) if mask is not None
+                                        else processor.step(frame, next_image=hint), dev.type == 'cuda')
+                total += secs
                 saver.process(prob, name, resize_needed=False, shape=None, last_frame=(n == len(src) - 1), path_to_image=None)
                 cleanups += check_to_clear_non_permanent_memory(processor, mem_cleanup_ratio, mem_get_info)
                 n += 1

@@ -300,3 +300,103 @@ def test_read_ahead_is_ordered_and_bounded():
     assert list(ReadAhead(list(range(9)), workers=0)) == list(range(9))
     assert list(ReadAhead(None, workers=2, length=4, getitem=lambda i: -i)) == [0, -1, -2, -3]
     assert list(ReadAhead([], workers=3)) == []
+
+
+def test_drivers_make_the_same_step_calls(tmp_path, product_net, monkeypatch):
+    """What the three dataset drivers hand to ``step``, with ``InferenceCore.step`` / ``LockstepCores.step`` replaced by recorders:
+    first-mask alignment, ``end``, the number of look-ahead hints (window depth WINDOW + WINDOW_LEAD + 1 for one video and for its
+    scales, 16 for a group, nothing with lookahead=False; in a group none on a mask frame or the last group frame and never past
+    it), every hint the very tensor a later call brings as its image, and the tail of a group of unequal lengths on the longer
+    video's own core in that clip's frame context.  The expected values below are written out from those rules."""
+    from cutie_amd import frame_context
+    from cutie_amd.eval_vos import process_video, process_video_multiscale, process_videos_lockstep
+    from cutie_amd.inference import inference_core as IC
+    from cutie_amd.inference.data.vos_test_dataset import VOSTestDataset
+    from cutie_amd.inference.lockstep import LockstepCores
+    from cutie_amd.inference.utils.results_utils import ResultSaver
+    root = str(tmp_path)
+    for name, n in (('vA', 5), ('vB', 7), ('vC', 7)):
+        _make_video(root, name, n=n, h=64, w=96, ids=(1, 3))
+    os.rename(os.path.join(root, 'Annotations', 'vC', '00000.png'), os.path.join(root, 'Annotations', 'vC', '00002.png'))   # first mask on frame 2
+
+    def readers(size=-1):
+        ds = VOSTestDataset(os.path.join(root, 'JPEGImages'), os.path.join(root, 'Annotations'), use_all_masks=False, size=size)
+        return {rd.vid_name: rd for rd in ds.get_datasets()}
+    full, small = readers(), readers(48)
+    monkeypatch.setattr(IC, 'WINDOW', 2)
+    monkeypatch.setattr(IC, 'WINDOW_LEAD', 1)          # -> a window of 4 frames for one video, so that it is shorter than the videos
+    calls, groups, saved = [], [], []
+
+    def prob_for(image):
+        return torch.full((3,) + tuple(image.shape[-2:]), 1 / 3)
+
+    def core_step(self, image, mask=None, objects=None, *, end=False, next_images=None, **kw):
+        assert not kw
+        calls.append(dict(core=self, table=frame_context._table(), image=image, mask=mask is not None, valid=objects, end=end,
+                          hints=list(next_images or [])))
+        return prob_for(image)
+
+    def group_step(self, images, masks=None, objects=None, *, end=False, next_images=None, **kw):
+        assert not kw
+        groups.append(dict(ls=self, images=list(images), mask=None if masks is None else [m is not None for m in masks], valid=objects,
+                           end=end, hints=None if next_images is None else [list(h) for h in next_images]))
+        return [prob_for(im) for im in images]
+    monkeypatch.setattr(IC.InferenceCore, 'step', core_step)
+    monkeypatch.setattr(LockstepCores, 'step', group_step)
+    monkeypatch.setattr(ResultSaver, 'process', lambda self, prob, frame, **kw: saved.append((self.video_name, frame, kw['last_frame'])))
+    monkeypatch.setattr(ResultSaver, 'process_merged',
+                        lambda self, probs, frame, shape, **kw: saved.append((self.video_name, frame, kw['last_frame'], len(probs))))
+
+    def summary(cs):
+        return [(c['mask'], c['valid'], c['end'], len(c['hints'])) for c in cs]
+
+    def hints_arrive(cs):
+        """every hint of call k is the image of call k + 1 + j, the same object"""
+        return all(h is cs[k + 1 + j]['image'] for k, c in enumerate(cs) for j, h in enumerate(c['hints']))
+
+    def reset():
+        del calls[:], groups[:], saved[:]
+    cfg = default_config(mem_every=2)
+    out = os.path.join(root, 'out')
+    with torch.inference_mode():
+        # ---- process_video: mask on frame 0 (7 frames), first mask on frame 2 (frames 0 and 1 are not stepped)
+        for la, hints in ((True, [4, 4, 4, 3, 2, 1, 0]), (False, [0] * 7)):
+            reset()
+            assert process_video(product_net, cfg, full['vB'], out, lookahead=la)['frames'] == 7
+            assert summary(calls) == [(ti == 0, [1, 3] if ti == 0 else None, ti == 6, hints[ti]) for ti in range(7)]
+            assert hints_arrive(calls) and len({id(c['core']) for c in calls}) == 1
+            assert saved == [('vB', f'{ti:05d}.jpg', ti == 6) for ti in range(7)]
+        for la, hints in ((True, [4, 3, 2, 1, 0]), (False, [0] * 5)):
+            reset()
+            assert process_video(product_net, cfg, full['vC'], out, lookahead=la)['frames'] == 5
+            assert summary(calls) == [(ti == 2, [1, 3] if ti == 2 else None, ti == 6, hints[ti - 2]) for ti in range(2, 7)]
+            assert hints_arrive(calls)
+            assert saved == [('vC', f'{ti:05d}.jpg', ti == 6) for ti in range(2, 7)]
+        # ---- process_video_multiscale, S = 2: per frame member 0 then member 1, each as process_video, each in its own frame context
+        for la, hints in ((True, [4, 3, 2, 1, 0]), (False, [0] * 5)):
+            reset()
+            assert process_video_multiscale(product_net, cfg, [full['vC'], small['vC']], out, lookahead=la)['frames'] == 5
+            assert len(calls) == 10
+            for s, hw in ((0, (64, 96)), (1, (48, 72))):
+                member = calls[s::2]
+                assert summary(member) == [(ti == 2, [1, 3] if ti == 2 else None, ti == 6, hints[ti - 2]) for ti in range(2, 7)]
+                assert hints_arrive(member) and all(tuple(c['image'].shape[-2:]) == hw for c in member)
+                assert len({id(c['core']) for c in member}) == 1 and len({id(c['table']) for c in member}) == 1
+            assert calls[0]['core'] is not calls[1]['core'] and calls[0]['table'] is not calls[1]['table']
+            assert saved == [('vC', f'{ti:05d}.jpg', ti == 6, 2) for ti in range(2, 7)]
+        # ---- process_videos_lockstep, 5 and 7 frames: 5 group frames (no `end`: the videos do not end together), then frames 5 and 6
+        # of the longer video on its own core
+        for la, ghints, thints in ((True, [None, 3, 2, 1, None], [1, 0]), (False, [None] * 5, [0, 0])):
+            reset()
+            st = process_videos_lockstep(product_net, cfg, [full['vA'], full['vB']], out, lookahead=la)
+            assert (st[0]['frames'], st[1]['frames']) == (5, 7)
+            assert [(g['mask'], g['valid'], g['end']) for g in groups] == [([True, True], [[1, 3], [1, 3]], False)] + [(None, None, False)] * 4
+            assert [None if g['hints'] is None else [len(h) for h in g['hints']] for g in groups] == [None if n is None else [n, n] for n in ghints]
+            ls = groups[0]['ls']
+            assert all(g['ls'] is ls for g in groups)
+            assert summary(calls) == [(False, None, False, thints[0]), (False, None, True, thints[1])]
+            assert all(c['core'] is ls.cores[1] and c['table'] is ls._ctx[1][0] for c in calls)
+            for c in range(2):                           # per clip: the group frames' images, then the tail's
+                seq = [dict(image=g['images'][c], hints=[] if g['hints'] is None else g['hints'][c]) for g in groups] + (calls if c == 1 else [])
+                assert hints_arrive(seq)
+            assert sorted(saved) == sorted([('vA', f'{ti:05d}.jpg', ti == 4) for ti in range(5)] + [('vB', f'{ti:05d}.jpg', ti == 6) for ti in range(7)])

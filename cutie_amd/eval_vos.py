@@ -14,6 +14,11 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
         [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
                                             no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
 
+BURST (a --dataset name containing "burst", e.g. burst-val | burst-test; eval_vos.py:42-54,108,156-157,171-172 of the reference):
+    python -m cutie_amd.eval_vos --dataset burst-val --images DIR/frames/val --json DIR/val/first_frame_annotations.json --output OUT
+        [--skip-frames N] [--size 600] [--egress device] [--lockstep 4] ...      (no --masks: the first masks are the json's RLE strings; no --sizes)
+    masks are written on the annotated frames only, and OUT/predictions.json holds every sequence's RLE strings (BURSTResultHandler).
+
 With several GPUs launch it under torch.distributed.run: videos are sharded over the ranks (cutie_amd/parallel.py)."""
 import argparse
 import logging
@@ -27,10 +32,12 @@ import torch
 
 from .config import default_config
 from .inference.data.device_ingest import finish, to_device
+from .inference.data.burst_test_dataset import BURSTTestDataset
 from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
+from .inference.utils.burst_utils import BURSTResultHandler
 from .inference.utils.results_utils import EGRESS_MODES, ResultSaver, make_zip
 
 log = logging.getLogger()
@@ -85,7 +92,19 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
     return ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=core.object_manager,
                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
-                       score_output_root=score_output_root, egress=egress)
+                       score_output_root=score_output_root, egress=egress,
+                       init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
+
+
+def is_burst(dataset: str) -> bool:
+    return 'burst' in dataset.lower()
+
+
+def _with_json(stats, saver):
+    """BURST: the sequence's json with the predicted segmentations (complete once the saver has ended) joins the video's stats."""
+    if saver.json_style == 'burst':
+        stats['video_json'] = saver.video_json
+    return stats
 
 
 def _save(saver, prob, info, last_frame, save_all):
@@ -140,7 +159,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
                    lambda probs, info, last: _save(saver, probs[0], info, last, save_all), dev=network.device, lookahead=lookahead)
     finally:
         saver.end()
-    return stats
+    return _with_json(stats, saver)
 
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
@@ -155,6 +174,8 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
     The members' probabilities stay referenced until the merge has been issued: a pooled plan output that somebody holds is not recycled
     (plans.SlotPool), and everything runs on the caller's stream.  Returns {'frames', 'seconds'}; seconds = the sum over the members."""
     _check_ingest(ingest)
+    if is_burst(dataset):
+        raise ValueError('process_video_multiscale: BURST has no multi-scale protocol')
     if save_scores:
         raise ValueError('process_video_multiscale merges on the device and writes no scores: save_scores is not supported')
     from .inference import inference_core as IC
@@ -234,13 +255,17 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     finally:
         for s in savers:
             s.end()
+    for c in range(C):
+        _with_json(stats[c], savers[c])
     return stats
 
 
 def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', required=True)
-    ap.add_argument('--masks', required=True)
+    ap.add_argument('--masks', help='the folder of first-frame masks (every dataset but BURST)')
+    ap.add_argument('--json', help='BURST: the first-frame annotation json (its RLE strings are the first masks)')
+    ap.add_argument('--skip-frames', type=int, default=-1, help='BURST: run on every N-th frame and the annotated ones (-1: on all)')
     ap.add_argument('--output', required=True)
     ap.add_argument('--weights')
     ap.add_argument('--dataset', default='generic')
@@ -271,6 +296,13 @@ def arg_parser() -> argparse.ArgumentParser:
 
 def check_args(ap: argparse.ArgumentParser, args) -> None:
     """The rules between switches that argparse cannot state (ap.error: usage + exit status 2)."""
+    if is_burst(args.dataset):
+        if args.json is None:
+            ap.error('a BURST dataset needs --json (the first-frame annotation file)')
+        if args.sizes is not None:
+            ap.error('--sizes: BURST has no multi-scale protocol')
+    elif args.masks is None:
+        ap.error('the following arguments are required: --masks')
     if args.sizes is not None:
         if len(set(args.sizes)) != len(args.sizes) or len(args.sizes) < 2:
             ap.error('--sizes takes at least two distinct values')
@@ -286,29 +318,22 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error('--sizes does not run in lock step: it excludes --lockstep > 1 (use --clips-in-flight)')
 
 
-def main():
-    ap = arg_parser()
-    args = ap.parse_args()
-    check_args(ap, args)
-    from .model.cutie import CUTIE
+def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
+    """The videos of this rank's shard through the drivers, as the switches say -> {index of the video: its stats}.  BURST: the
+    sequences' predictions go to ``predictions.json`` in the output root (rank 0, the other ranks' sequences gathered)."""
     from .parallel import run_concurrent, shard_clips
-    import torch.distributed as dist
-    world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
-    if world > 1:
-        dist.init_process_group(backend='nccl')
-    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
-    cfg = default_config(model=args.model, use_long_term=args.long_term, flip_aug=args.flip_aug, save_scores=args.save_scores)
-    net = CUTIE(cfg).cuda().eval()
-    if args.weights:
-        net.load_weights(torch.load(args.weights, map_location='cpu'))
-    meta = VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=args.size, subset=args.subset,
-                          ingest=args.ingest)
+    burst = is_burst(args.dataset)
+    if burst:                                                 # (eval_vos.py:42-54; save_all is False there, eval_config.yaml)
+        meta = BURSTTestDataset(args.images, args.json, size=args.size, skip_frames=args.skip_frames, ingest=args.ingest)
+    else:
+        meta = VOSTestDataset(args.images, args.masks, use_all_masks=args.use_all_masks, size=args.size, subset=args.subset,
+                              ingest=args.ingest)
     readers = list(meta.get_datasets())
     mine = shard_clips(len(readers), rank, world)
     mask_root = path.join(args.output, 'Annotations')
     common = dict(dataset=args.dataset, visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
                   save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
-                  egress=args.egress)                         # (no ingest=: the readers carry the mode)
+                  egress=args.egress, save_all=not burst)     # (no ingest=: the readers carry the mode)
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is
@@ -339,13 +364,44 @@ def main():
                     res[c] = st[j]
             mine = [c for c in mine if c not in res]
         res.update(run_concurrent(net, mine, run, streams=max(1, args.clips_in_flight)))
+    if burst:                                                 # (eval_vos.py:156-157,171-172)
+        seqs = {c: r['video_json'] for c, r in res.items()}
+        if world > 1:
+            import torch.distributed as dist
+            parts = [None] * world
+            dist.all_gather_object(parts, seqs)
+            seqs = {c: v for part in parts for c, v in part.items()}
+        if rank == 0:
+            handler = BURSTResultHandler(meta.json)
+            for c in sorted(seqs):
+                handler.add_sequence(seqs[c])
+            os.makedirs(args.output, exist_ok=True)
+            handler.dump(args.output)
+    return res
+
+
+def main():
+    ap = arg_parser()
+    args = ap.parse_args()
+    check_args(ap, args)
+    from .model.cutie import CUTIE
+    import torch.distributed as dist
+    world, rank = int(os.environ.get('WORLD_SIZE', '1')), int(os.environ.get('RANK', '0'))
+    if world > 1:
+        dist.init_process_group(backend='nccl')
+    torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
+    cfg = default_config(model=args.model, use_long_term=args.long_term, flip_aug=args.flip_aug, save_scores=args.save_scores)
+    net = CUTIE(cfg).cuda().eval()
+    if args.weights:
+        net.load_weights(torch.load(args.weights, map_location='cpu'))
+    res = run_dataset(net, cfg, args, rank, world)
     frames, secs = sum(r['frames'] for r in res.values()), sum(r['seconds'] for r in res.values())
     print(f'rank {rank}: {frames} frames, {secs:.2f} s in step, FPS {frames / max(secs, 1e-9):.1f}')
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        make_zip(args.dataset, args.output, 'cutie_amd', mask_root)
+        make_zip(args.dataset, args.output, 'cutie_amd', path.join(args.output, 'Annotations'))
 
 
 if __name__ == '__main__':

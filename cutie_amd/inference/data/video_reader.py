@@ -55,12 +55,17 @@ def _decode_rgb_u8(img_path: str):
 INGEST_MODES = ('host', 'device', 'device-decode')
 
 
+def _nearest(m: Image.Image, size: int) -> Image.Image:
+    """Nearest-neighbour resize of the shorter side of a mask image to ``size``."""
+    nh, nw = _shorter_side_to(m.height, m.width, size)
+    return m.resize((nw, nh), Image.NEAREST)
+
+
 def _decode_mask(mask_path: str, long_ids: bool, size: Optional[int]):
     """-> int64 [h, w] object ids; ``size``: nearest-neighbour resize of the shorter side first."""
     m = Image.open(mask_path)
     if size is not None:
-        nh, nw = _shorter_side_to(m.height, m.width, size)
-        m = m.resize((nw, nh), Image.NEAREST)
+        m = _nearest(m, size)
     ids = torch.from_numpy(np.array(m)).long()
     if long_ids:
         assert ids.dim() == 3, 'RGB masks should have 3 dimensions'
@@ -118,6 +123,23 @@ class VideoReader(torch.utils.data.Dataset):
             raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
         frame = self.frames[idx]
         im_path = os.path.join(self.image_dir, frame)
+        img, out_hw, shrink, rgb_hw = self._image(frame, im_path, ingest)
+        data = {}
+        mask_path = os.path.join(self.mask_dir, _stem(frame) + '.png')
+        if self._wants_mask(frame) and os.path.exists(mask_path):
+            ids = _decode_mask(mask_path, self.use_long_id, self.size if shrink else None)
+            present = torch.unique(ids)
+            data['mask'], data['valid_labels'] = ids, present[present != 0]
+        data.update(img)
+        data['info'] = {'frame': frame, 'save': self.to_save is None or _stem(frame) in self.to_save, 'shape': out_hw,
+                        'resize_needed': shrink, 'time_index': self._time_index[frame], 'path_to_image': im_path}
+        if ingest != 'host':
+            data['info']['rgb_shape'] = tuple(rgb_hw)
+        return data
+
+    def _image(self, frame: str, im_path: str, ingest: str, always: bool = False):
+        """The image of a record in its ingest form -> ({'rgb' | 'rgb_u8' | 'jpeg': ...}, output (h, w), is the frame resized, the
+        (h, w) the model sees).  ``always``: a ``size`` > 0 resizes every frame (the BURST reader), not only the larger ones."""
         on_device = ingest != 'host'
         pkt = None
         if ingest == 'device-decode':
@@ -134,25 +156,16 @@ class VideoReader(torch.utils.data.Dataset):
         else:
             ref = Image.open(os.path.join(self.size_dir, frame))
             out_hw = (ref.height, ref.width)
-        shrink = in_hw != out_hw or (self.size > 0 and min(in_hw) > self.size)
+        shrink = in_hw != out_hw or (self.size > 0 and (always or min(in_hw) > self.size))
         rgb_hw = _shorter_side_to(*in_hw, self.size) if shrink else in_hw
         if shrink and not on_device:
             rgb = F.interpolate(rgb[None], size=rgb_hw, mode='bilinear', align_corners=False, antialias=True)[0]
         data = {}
-        mask_path = os.path.join(self.mask_dir, _stem(frame) + '.png')
-        if self._wants_mask(frame) and os.path.exists(mask_path):
-            ids = _decode_mask(mask_path, self.use_long_id, self.size if shrink else None)
-            present = torch.unique(ids)
-            data['mask'], data['valid_labels'] = ids, present[present != 0]
         if pkt is not None:
             data['jpeg'] = pkt
         else:
             data['rgb_u8' if on_device else 'rgb'] = rgb
-        data['info'] = {'frame': frame, 'save': self.to_save is None or _stem(frame) in self.to_save, 'shape': out_hw,
-                        'resize_needed': shrink, 'time_index': self._time_index[frame], 'path_to_image': im_path}
-        if on_device:
-            data['info']['rgb_shape'] = tuple(rgb_hw)
-        return data
+        return data, out_hw, shrink, rgb_hw
 
     def get_palette(self):
         return self.palette

@@ -6,8 +6,10 @@ long ids), so the device-to-host copy is H*W bytes instead of the (K+1)*H*W*4 by
 only encodes the PNG.  ``save_scores`` (multi-scale testing, :94,195-209): probabilities are quantised to uint8 (x255,
 truncation) ON THE DEVICE, so the copy is 4x smaller too; the reference stores them with hickle (HDF5, lzf), which is not in
 this image, so the container here is ``<frame>.npz`` (key ``prob``) and ``backward.npz`` (keys ``obj_ids`` / ``tmp_ids``) --
-``cutie_amd.merge_multi_scale`` reads these (and ``.hkl`` when hickle is importable).  Not supported (raise): the BURST
-json writer (``init_json``: its RLE masks need pycocotools, which is not in this image).
+``cutie_amd.merge_multi_scale`` reads these (and ``.hkl`` when hickle is importable).
+BURST (a dataset name containing 'burst', :67-74,153-171): ``init_json`` is the sequence's json; on its annotated frames every object
+with a non-empty mask is recorded as ``{'rle': <COCO compressed RLE>}`` in ``segmentations`` / ``video_json`` (collected by
+utils/burst_utils.py BURSTResultHandler).  The strings come from utils/coco_rle.py, not pycocotools -- the same bytes.
 Long ids (RGB masks): as in the reference (:171-178) every object gets a random colour (utils/pano_utils.ID2RGBConverter), NOT the
 inverse of VideoReader's R + 256 G + 65536 B decoding.  Behaviour recorded from the executed reference: tests/golden/io/.
 
@@ -16,7 +18,10 @@ plane.  One op list per frame on the caller's stream -- argmax + remap (fused wi
 the way in, so the full-size probabilities never exist) and the PNG filter + DEFLATE + Adler-32 stage (csrc/png.hip) -- then ONE
 non-blocking copy of the status block and the first slab of the stream into pinned memory with an event behind it.  ``process`` does
 not wait; the writer thread waits on the event, checks the error word, wraps the bytes (utils/png.py) and writes the file.  The files
-hold the same mode, palette and pixels as the host path's; their bytes differ (other filter and Huffman codes, always 8 bits)."""
+hold the same mode, palette and pixels as the host path's; their bytes differ (other filter and Huffman codes, always 8 bits).
+With BURST the same op list carries the RLE stage (csrc/rle.hip) over the id plane on annotated frames: the objects' strings, their
+table and a status block ride a second pinned copy in front of the same event, and the writer thread slices the strings out; if the
+strings did not fit the device stream the writer encodes that frame on the host from a copy of the id plane."""
 import logging
 import os
 import shutil
@@ -32,6 +37,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 from ...utils.pano_utils import ID2RGBConverter
+from . import coco_rle
 from . import png as png_container
 
 log = logging.getLogger()
@@ -57,15 +63,22 @@ davis_palette = davis_palette_np.tobytes()
 
 EGRESS_MODES = ('host', 'device')
 EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
+RLE_TABLE = 16 + 255 * 16   # BURST: bytes of the status block and the table of up to 255 objects in front of the RLE strings
+RLE_SLAB = 256 * 1024       # ... and of the whole device-to-host copy: status, table and the strings (a frame that needs more is encoded on the host)
 
 
 class _EgressBuffers:
     """What one frame in flight owns (egress='device'): the id plane, [status | stream] on the device, the pinned slab and the event
     recorded behind the copy.  Recycled through ResultSaver's pool once the writer thread is done with them."""
 
-    def __init__(self, H, W, device):
+    def __init__(self, H, W, device, rle=False):
         from ... import ops as O
         self.H, self.W = H, W
+        if rle:                                  # BURST: [status | table | strings] on the device and pinned
+            self.rle_dev = torch.empty(RLE_SLAB, dtype=torch.uint8, device=device)
+            self.rle_status, self.rle_table = self.rle_dev[:16].view(torch.int32), self.rle_dev[16:RLE_TABLE].view(torch.int32).view(-1, 4)
+            self.rle_stream = self.rle_dev[RLE_TABLE:]
+            self.rle_host = torch.empty(RLE_SLAB, dtype=torch.uint8).pin_memory()
         cap = O.OpList.png_capacity(H, W)
         self.ids = torch.empty((H, W), dtype=torch.uint8, device=device)
         self.dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
@@ -85,6 +98,7 @@ class _Job:
     last_frame: bool = False
     tmp_to_obj: Optional[dict] = None        # {tmp_id: object id} at the time of the frame
     egress: Optional[_EgressBuffers] = None  # egress='device': the mask arrives in these (mask is None)
+    rle: bool = False                        # egress='device', BURST: the objects' RLE strings arrive in them as well
 
 
 class ResultSaver:
@@ -106,9 +120,18 @@ class ResultSaver:
         if save_scores and score_output_root is None:
             raise ValueError('save_scores needs score_output_root')
         self.save_scores, self.score_output_root = save_scores, score_output_root
-        if init_json is not None or 'burst' in dataset.lower():
-            raise NotImplementedError('the BURST json writer is not supported')
+        if 'burst' in dataset.lower() and init_json is None:
+            raise NotImplementedError('a BURST dataset needs init_json (the json of the sequence): the predictions are written into it')
         self.output_root, self.video_name, self.dataset = output_root, video_name, dataset.lower()
+        self.json_style = None
+        if 'burst' in self.dataset:              # results_utils.py:67-74
+            self.input_segmentations = init_json['segmentations']
+            self.segmentations = [{} for _ in init_json['segmentations']]
+            self.annotated_frames = init_json['annotated_image_paths']
+            self.video_json = {k: v for k, v in init_json.items() if k != 'segmentations'}
+            self.video_json['segmentations'] = self.segmentations
+            self.json_style = 'burst'
+        self._rle_objs, self._rle_scratch, self._rle_warned = {}, None, False
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
@@ -154,7 +177,7 @@ class ResultSaver:
             except Empty:
                 if self._allocated < self.queue.maxsize + 2:
                     self._allocated += 1
-                    return _EgressBuffers(H, W, device)
+                    return _EgressBuffers(H, W, device, rle=self.json_style == 'burst')
                 b = self._free.get()
             if (b.H, b.W) == (H, W):
                 return b
@@ -183,15 +206,27 @@ class ResultSaver:
         ol = O.OpList()
         ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
                       out_hw=(H, W) if resize_needed else None, png=(b.stream, b.status, self._scratch[1]))
+        all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
+        rle = self.json_style == 'burst' and frame_name in self.annotated_frames
+        if rle:                                  # the objects' RLE strings of the finished plane, in the order of all_ids
+            n = len(all_ids)
+            objs = self._rle_objs.get(tuple(all_ids))
+            if objs is None:
+                objs = self._rle_objs[tuple(all_ids)] = torch.tensor(all_ids or [0], dtype=torch.int32).to(dev)
+            if self._rle_scratch is None or self._rle_scratch[0] != (H, W, n):
+                self._rle_scratch = ((H, W, n), torch.empty(O.OpList.rle_scratch_words(H, W, n), dtype=torch.int32, device=dev))
+            ol.rle_encode(b.ids, objs, b.rle_stream, b.rle_table, b.rle_status, self._rle_scratch[1], H=H, W=W, n_objects=n)
         ol.run()
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
+        if rle:
+            b.rle_host.copy_(b.rle_dev, non_blocking=True)
         b.event.record()
         q = None
         if self.save_scores:                     # as the host path: the scores of the output size
             full = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
             q = (full * 255).to(torch.uint8).cpu()
-        self.queue.put(_Job(self, None, frame_name, None, [o.id for o in self.object_manager.obj_to_tmp_id], prob=q, last_frame=last_frame,
-                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b))
+        self.queue.put(_Job(self, None, frame_name, None, all_ids, prob=q, last_frame=last_frame,
+                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b, rle=rle))
 
     # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
     def process_merged(self, probs, frame_name: str, shape: Tuple[int, int], last_frame: bool = False, path_to_image: str = None, *,
@@ -204,6 +239,8 @@ class ResultSaver:
         the same op carries the PNG stage, as in ``process``.  ``id_maps``: the members' {tmp id: object id} tables -- they must be
         equal (the members see the same first masks in the same order); this saver's object manager is the first member's."""
         from ... import ops as O
+        if self.json_style == 'burst':
+            raise ValueError('process_merged: BURST has no multi-scale protocol (no json is written from merged scales)')
         if self.save_scores:
             raise ValueError('process_merged writes no scores: save_scores and the merge exclude each other')
         if self.processor is None:
@@ -267,11 +304,42 @@ class ResultSaver:
         self._wstream.synchronize()
         return head + rest.numpy().tobytes()
 
+    def _fetch_rle(self, b: _EgressBuffers, all_obj_ids) -> dict:
+        """Writer thread, BURST: {object id: RLE string} of the frame's non-empty objects from the device encoder (its copy has
+        landed: the event is behind it).  If the strings did not fit the device stream, the frame is encoded here from a copy of the id
+        plane (logged once)."""
+        b.event.synchronize()
+        total, err, _, _ = (int(v) for v in b.rle_host[:16].view(torch.int32))
+        if err != 0:
+            if not self._rle_warned:
+                self._rle_warned = True
+                log.warning(f'device RLE encoder: a frame of {self.video_name} needs {total} bytes, the stream holds {b.rle_stream.numel()}; '
+                            f'such frames are encoded on the host')
+            if self._wstream is None:
+                self._wstream = torch.cuda.Stream(device=b.dev.device)
+            with torch.cuda.stream(self._wstream):
+                ids = b.ids.to('cpu', non_blocking=False).numpy()
+            return _host_rle(ids, all_obj_ids)
+        n = len(all_obj_ids)
+        table = b.rle_host[16:16 + 16 * n].view(torch.int32).view(-1, 4).numpy()
+        raw = b.rle_host[RLE_TABLE:RLE_TABLE + total].numpy().tobytes()
+        return {oid: raw[off:off + ln].decode('ascii') for oid, (off, ln, _, area) in zip(all_obj_ids, table.tolist()) if area > 0}
+
     def end(self):
         self.queue.put(None)
         self.queue.join()
         self.thread.join()
         self._free, self._allocated, self._scratch = Queue(), 0, None
+
+
+def _host_rle(ids: np.ndarray, all_obj_ids) -> dict:
+    """{object id: RLE string} of the objects with a non-empty mask (results_utils.py:166-171)."""
+    out = {}
+    for oid in all_obj_ids:
+        seg = ids == oid
+        if seg.sum() > 0:
+            out[oid] = coco_rle.encode(seg)
+    return out
 
 
 def _writer(queue: Queue):
@@ -282,9 +350,12 @@ def _writer(queue: Queue):
             break
         try:
             s = job.saver
+            strings = None
             if job.egress is not None:                             # egress='device': wrap the finished stream, no PIL
                 b = job.egress
                 try:
+                    if job.rle:
+                        strings = s._fetch_rle(b, job.all_obj_ids)
                     data = png_container.assemble(s._fetch(b), b.H, b.W, s.palette)
                 finally:
                     s._free.put(b)
@@ -293,6 +364,18 @@ def _writer(queue: Queue):
                 with open(path.join(out_dir, job.frame_name[:-4] + '.png'), 'wb') as f:
                     f.write(data)
             out_mask = job.mask.numpy() if job.mask is not None else None
+            if s.json_style == 'burst' and job.frame_name in s.annotated_frames:      # results_utils.py:153-171
+                index = s.annotated_frames.index(job.frame_name)
+                input_segments, frame_segments = s.input_segmentations[index], s.segmentations[index]
+                if strings is None:
+                    strings = _host_rle(out_mask, [i for i in job.all_obj_ids if i not in input_segments])
+                for oid in job.all_obj_ids:
+                    # (as executed: the object ids are ints, the keys of a json that was loaded from a file are strings, so the copy
+                    # only happens for an init_json whose keys are ints; everything else is encoded.  Keys turn into strings at json.dump)
+                    if oid in input_segments:
+                        frame_segments[oid] = input_segments[oid]
+                    elif oid in strings:
+                        frame_segments[oid] = {'rle': strings[oid]}
             rgb_mask = None
             if s.save_mask and job.egress is None:
                 if s.use_long_id:

@@ -896,6 +896,27 @@ class OpList:
         was written, 0).  scratch int32 [>= png_scratch_words(H, W)], 16-byte aligned.  cutie_amd/inference/utils/png.py wraps the stream."""
         return self.add(PROB_TO_ID, 8, [0, H, W, 0, 0, 0, 0, stream.numel(), scratch.numel()], [], [None, None, ids, stream, status, scratch])
 
+    RLE_MAX_OBJECTS = 255
+
+    @staticmethod
+    def rle_scratch_words(H, W, n_objects):
+        """int32 words of the scratch of rle_encode (csrc/rle.hip launch_rle_encode): 1024 words of per-object sums, one word per 1024
+        boundaries, the starts per (object, chunk) -- a chunk is <= 256 rows of one column -- and the boundary positions, at most two per
+        pixel and one sentinel per object."""
+        G = 2 * H * W + n_objects
+        return 1024 + -(-(-(-G // 1024)) // 4) * 4 + n_objects * W * -(-H // 256) + G
+
+    def rle_encode(self, ids, objects, stream, table, status, scratch, *, H, W, n_objects):
+        """PROB_TO_ID flags == 32 (ABI 9, include/cutie_hip.h): ids uint8 [H, W] (contiguous) -> the COCO compressed-RLE strings (the
+        bytes of inference/utils/coco_rle.py encode(ids == objects[k])) of the n_objects <= 255 ids in ``objects`` (int32 on the device,
+        distinct, 1 .. 255), back to back in ``stream`` (uint8 [capacity]); table int32 [n_objects, 4] = per object (byte offset, bytes,
+        counts, area), 16-byte aligned; status int32 [4] = (bytes of all strings, error bits: 1 = the capacity is too small and nothing
+        was written to the stream, counts of all strings, 0); scratch int32 [>= rle_scratch_words(H, W, n_objects)], 16-byte aligned."""
+        if not 0 <= n_objects <= self.RLE_MAX_OBJECTS:
+            raise ValueError(f'rle_encode: {n_objects} objects, 0 .. {self.RLE_MAX_OBJECTS}')
+        return self.add(PROB_TO_ID, 32, [0, H, W, 0, 0, 0, 0, stream.numel(), scratch.numel(), n_objects], [],
+                        [None, None, ids, stream, status, scratch, objects, table])
+
     def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
         """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32
         [OW + OH, K + 2]), scratch = f32 [C, H, OW].  src_u8: src is u8 [H, W, C] with row stride `ldrow` bytes (ToTensor on the fly;

@@ -336,7 +336,27 @@ enum {
      *    p0 = u64 [S] device table: the sources' first planes (f32, P planes each, last dimension contiguous), 8-byte aligned
      *    p6 = i32 [S, 4] device table, 16-byte aligned: per source H, W, plane stride, row stride (elements; H, W >= 1 -- a source that says
      *    otherwise is left out of the sum)       i9 = S, 1 <= S <= CUTIE_MERGE_MAX_SOURCES       i1 .. i4 unused.
-     *    The launcher checks what it can see (flags, S, null / misaligned tables, P, OH, OW); the tables' contents are the caller's. */
+     *    The launcher checks what it can see (flags, S, null / misaligned tables, P, OH, OW); the tables' contents are the caller's.
+     * ABI 9 -- BURST egress (results_utils.py:153-171 of the reference: per annotated frame and object, pycocotools' mask_util.encode of
+     *    (mask == id), its counts string into predictions.json; ResultSaver egress='device' with init_json):
+     *  flags == 32, a stage ON ITS OWN (32 combined with any other flag stays the "unknown flags" error): the COCO compressed-RLE strings of
+     *    the objects of an existing uint8 id plane p2 = [i1, i2] = [H, W], row-major and contiguous (kernels in rle.hip; the format and
+     *    its numpy model: cutie_amd/inference/utils/coco_rle.py -- the mask flattened column-major, run lengths from a run of zeros on,
+     *    count j > 2 as counts[j] - counts[j-2], 5-bit groups + 48).  i0, i3 .. i6 and p0, p1 unused.
+     *    p6 = object ids int32 [i9], 4-byte aligned, i9 = n <= 255: distinct ids 1 .. 255; ids of the plane that are not listed are
+     *    background for every listed object; an entry 0, above 255 or equal to an earlier entry is encoded as an absent object.
+     *    p3 = stream uint8 (any alignment), i7 = its capacity in bytes: the n strings back to back in the order of p6, no separators.
+     *    p7 = table int32 [n, 4], 16-byte aligned: per object byte offset, bytes, number of counts, area (an absent object: one count
+     *    H * W, area 0).  p4 = status int32 [4], 4-byte aligned: 0 bytes of all strings (saturating at 2^31 - 1), 1 error bits (1: the
+     *    strings do not fit the capacity; NOTHING is written to p3 then and the table's offsets are 0; bytes, counts and areas stay valid),
+     *    2 counts of all strings, 3 zero.  With n == 0 only the status is written (p6, p7 may be null).
+     *    p5 = int32 scratch of i8 words, 16-byte aligned, i8 >= 1024 + roundup4(ceil(G / 1024)) + n * W * ceil(H / 256) + G with
+     *    G = 2 H W + n (cutie_amd/ops.py OpList.rle_scratch_words): per-object sums, one word per 1024 run boundaries, the run starts
+     *    per (object, chunk of <= 256 rows of one column), and the boundary positions -- at most two per pixel, one sentinel per object.
+     *    H * W < 2^31.  One sweep over the plane finds the runs of all objects (the transposition happens in LDS tiles); every offset
+     *    comes from a scan in a fixed order, the per-object byte and area totals from integer atomics: the bytes depend on the plane and
+     *    the object list alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch:
+     *    H, W < 1, H * W >= 2^31, n outside 0 .. 255, a negative capacity, a null or misaligned pointer, a scratch that is too small. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).

@@ -13,6 +13,10 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
         [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
                                             no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
+        [--score [--gt DIR] [--score-all-frames]]      (DAVIS J&F of the run against the palette PNGs of DIR/<video>/ -- default: --masks --,
+                                            counted on the GPU from the id planes while the videos run (inference/utils/davis_metrics.py); writes
+                                            global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output;
+                                            the first and last ground-truth frame of a video are left out unless --score-all-frames)
 
 BURST (a --dataset name containing "burst", e.g. burst-val | burst-test; eval_vos.py:42-54,108,156-157,171-172 of the reference):
     python -m cutie_amd.eval_vos --dataset burst-val --images DIR/frames/val --json DIR/val/first_frame_annotations.json --output OUT
@@ -38,6 +42,7 @@ from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
 from .inference.utils.burst_utils import BURSTResultHandler
+from .inference.utils.davis_metrics import SequenceScorer, global_line, write_results
 from .inference.utils.results_utils import EGRESS_MODES, ResultSaver, make_zip
 
 log = logging.getLogger()
@@ -88,11 +93,17 @@ def _take(window, dev, lookahead):
 
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
-           score_output_root=None) -> ResultSaver:
+           score_output_root=None, score_gt=None, score_all_frames=False) -> ResultSaver:
+    """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer."""
+    scorer = None
+    if score_gt is not None:
+        if vid_reader.use_long_id:
+            raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) cannot be scored')
+        scorer = SequenceScorer(score_gt, vid_reader.vid_name, core.network.device, skip_first_last=not score_all_frames)
     return ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=core.object_manager,
                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
-                       score_output_root=score_output_root, egress=egress,
+                       score_output_root=score_output_root, egress=egress, scorer=scorer,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -101,9 +112,12 @@ def is_burst(dataset: str) -> bool:
 
 
 def _with_json(stats, saver):
-    """BURST: the sequence's json with the predicted segmentations (complete once the saver has ended) joins the video's stats."""
+    """BURST: the sequence's json with the predicted segmentations (complete once the saver has ended) joins the video's stats; so do the
+    scores of a scored run."""
     if saver.json_style == 'burst':
         stats['video_json'] = saver.video_json
+    if saver.scorer is not None:                 # a scored run: the video's counts and J / F per frame and object (None: nothing was scored)
+        stats['scores'] = saver.scores
     return stats
 
 
@@ -143,15 +157,16 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host') -> Dict:
+                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
-    egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams)."""
+    egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
+    score_gt: the root of the ground-truth PNGs -- the video is scored (J&F counts on the device, ``_saver``) and 'scores' joins the stats."""
     _check_ingest(ingest)
     from .inference import inference_core as IC
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, save_scores=save_scores, score_output_root=score_output_root)
+                   egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         feed = _feed(vid_reader, network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest)
@@ -164,7 +179,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host') -> Dict:
+                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -189,7 +204,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
         raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress)
+                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -203,7 +218,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
         _run_video([lambda s=s: members.clip(s) for s in range(S)], feeds, n, 0, stats, save, dev=network.device, lookahead=lookahead)
     finally:
         saver.end()
-    return stats
+    return _with_json(stats, saver)
 
 
 def lockstep_key(vid_reader):
@@ -218,7 +233,7 @@ def lockstep_key(vid_reader):
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None, egress='host') -> Dict[int, Dict]:
+                            ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
@@ -229,7 +244,8 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     ls = LockstepCores(network, cfg, C)
     dev = network.device
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                     egress=egress, save_scores=save_scores, score_output_root=score_output_root) for c, rd in enumerate(vid_readers)]
+                     egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
+                     score_all_frames=score_all_frames) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -291,7 +307,28 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES),
                     help='device: the GPU resamples + argmaxes the result in one kernel and writes the PNG zlib stream; the host copies a few '
                          'KB per frame without blocking and only wraps them in PNG chunks (cutie_amd/inference/utils/results_utils.py)')
+    ap.add_argument('--score', action='store_true',
+                    help='DAVIS J&F of the run, counted on the GPU while the videos run (cutie_amd/inference/utils/davis_metrics.py): writes '
+                         'global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output.  Not for BURST or long-id (RGB) masks: '
+                         'the first mask under --masks / --gt is peeked at for an early error, every video is checked when it starts')
+    ap.add_argument('--gt', help='--score: the root of the ground-truth palette PNGs, DIR/<video>/<frame>.png (default: --masks)')
+    ap.add_argument('--score-all-frames', action='store_true',
+                    help='--score: also score the first and the last ground-truth frame of a video (the DAVIS protocol leaves them out)')
     return ap
+
+
+def _long_id_masks(masks_dir) -> bool:
+    """Does the first mask of the first video under ``masks_dir`` hold long ids (an RGB PNG)?  A best-effort peek for an early
+    ``ap.error`` -- one file is looked at, False when nothing can be read; the guard that holds for every video is ``_saver``'s ValueError."""
+    from PIL import Image
+    try:
+        for vid in sorted(os.listdir(masks_dir)):
+            pngs = sorted(f for f in os.listdir(path.join(masks_dir, vid)) if f.lower().endswith('.png'))
+            if pngs:
+                return Image.open(path.join(masks_dir, vid, pngs[0])).mode == 'RGB'
+    except OSError:
+        pass
+    return False
 
 
 def check_args(ap: argparse.ArgumentParser, args) -> None:
@@ -303,6 +340,15 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error('--sizes: BURST has no multi-scale protocol')
     elif args.masks is None:
         ap.error('the following arguments are required: --masks')
+    if args.score:
+        if is_burst(args.dataset):
+            ap.error('--score: BURST is not scored with J&F (its predictions.json goes to the BURST benchmark tools)')
+        if args.gt is None:
+            args.gt = args.masks
+        if _long_id_masks(args.masks) or _long_id_masks(args.gt):
+            ap.error('--score: long-id datasets (RGB masks) cannot be scored: J&F is counted on uint8 id planes')
+    elif args.gt is not None or args.score_all_frames:
+        ap.error('--gt and --score-all-frames belong to --score')
     if args.sizes is not None:
         if len(set(args.sizes)) != len(args.sizes) or len(args.sizes) < 2:
             ap.error('--sizes takes at least two distinct values')
@@ -334,6 +380,9 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
     common = dict(dataset=args.dataset, visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
                   save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
                   egress=args.egress, save_all=not burst)     # (no ingest=: the readers carry the mode)
+    score = bool(getattr(args, 'score', False))
+    if score:
+        common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames))
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is
@@ -377,6 +426,18 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
                 handler.add_sequence(seqs[c])
             os.makedirs(args.output, exist_ok=True)
             handler.dump(args.output)
+    if score:                                                 # the videos' scores of all ranks -> the result files (rank 0)
+        seqs = {readers[c].vid_name: r.get('scores') for c, r in res.items()}
+        if world > 1:
+            import torch.distributed as dist
+            parts = [None] * world
+            dist.all_gather_object(parts, seqs)
+            seqs = {name: v for part in parts for name, v in part.items()}
+        if rank == 0 and not any(v is not None for v in seqs.values()):
+            log.warning('--score: no video had a scored frame; no result files are written')
+        elif rank == 0:
+            glob = write_results(args.output, args.dataset, seqs)
+            print(f'{args.dataset}: {global_line(glob)}   ({sum(v is not None for v in seqs.values())} sequences)')
     return res
 
 

@@ -104,7 +104,7 @@ class _Job:
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
-                 processor=None, egress='host'):
+                 processor=None, egress='host', scorer=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -112,7 +112,13 @@ class ResultSaver:
         runs -- with ``use_long_id`` (RGB masks), with ``visualize`` (the overlay needs the ids on the host) and without ``save_mask``;
         ``save_scores`` keeps its own copy of the probabilities next to the device-encoded mask: with it -- multi-scale runs -- ``process``
         still builds the full-size fp32 probabilities when the frame was resized and blocks on their copy, so 'device' saves only the
-        PNG encode there, not the stall."""
+        PNG encode there, not the stall.
+        ``scorer`` (not in the reference; utils/davis_metrics.py SequenceScorer): every frame's uint8 id plane is
+        handed to ``scorer.add`` while it is still on the device -- before the copy of the host path, behind the id stage of the device
+        path and of ``process_merged`` -- and ``end`` leaves ``scorer.finish()`` in ``self.scores``.  Long ids cannot be scored."""
+        if scorer is not None and use_long_id:
+            raise ValueError('scorer: J&F is counted on uint8 id planes; long ids (RGB masks) cannot be scored')
+        self.scorer, self.scores = scorer, None
         if egress not in EGRESS_MODES:
             raise ValueError(f'egress must be one of {EGRESS_MODES}, not {egress!r}')
         if egress == 'device' and processor is None:
@@ -162,6 +168,8 @@ class ResultSaver:
                 if tmp_id < lut.shape[0]:
                     lut[tmp_id] = obj.id
             mask = lut[idx].to(out_dtype)
+        if self.scorer is not None:
+            self.scorer.add(frame_name, mask)
         q = (prob * 255).to(torch.uint8).cpu() if self.save_scores else None       # == numpy astype(uint8) of prob*255
         self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, [o.id for o in self.object_manager.obj_to_tmp_id],
                             prob=q, last_frame=last_frame,
@@ -217,6 +225,8 @@ class ResultSaver:
                 self._rle_scratch = ((H, W, n), torch.empty(O.OpList.rle_scratch_words(H, W, n), dtype=torch.int32, device=dev))
             ol.rle_encode(b.ids, objs, b.rle_stream, b.rle_table, b.rle_status, self._rle_scratch[1], H=H, W=W, n_objects=n)
         ol.run()
+        if self.scorer is not None:              # (b.ids is not handed out again before the writer is done with the frame: same stream)
+            self.scorer.add(frame_name, b.ids)
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         if rle:
             b.rle_host.copy_(b.rle_dev, non_blocking=True)
@@ -275,6 +285,8 @@ class ResultSaver:
             ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=dev)
             ol.prob_to_id_merged(probs, lut_dev, ids, out_hw=(H, W))
             ol.run()
+            if self.scorer is not None:
+                self.scorer.add(frame_name, ids)
             self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame))
             return
         if self._scratch is None or self._scratch[0] != (H, W):
@@ -282,6 +294,8 @@ class ResultSaver:
         b = self._take(H, W, dev)
         ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W), png=(b.stream, b.status, self._scratch[1]))
         ol.run()
+        if self.scorer is not None:
+            self.scorer.add(frame_name, b.ids)
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         b.event.record()
         self.queue.put(_Job(self, None, frame_name, None, all_ids, last_frame=last_frame, egress=b))
@@ -330,6 +344,8 @@ class ResultSaver:
         self.queue.join()
         self.thread.join()
         self._free, self._allocated, self._scratch = Queue(), 0, None
+        if self.scorer is not None:
+            self.scores = self.scorer.finish()
 
 
 def _host_rle(ids: np.ndarray, all_obj_ids) -> dict:

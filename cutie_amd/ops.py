@@ -917,6 +917,58 @@ class OpList:
         return self.add(PROB_TO_ID, 32, [0, H, W, 0, 0, 0, 0, stream.numel(), scratch.numel(), n_objects], [],
                         [None, None, ids, stream, status, scratch, objects, table])
 
+    JF_MAX_RADIUS = 40        # CUTIE_JF_MAX_RADIUS (include/cutie_hip.h): covers 2160 x 3840, where the DAVIS radius is 36
+    JF_MAX_OBJECTS = 255
+
+    @staticmethod
+    def jf_scratch_words(H, W, n_objects):
+        """int32 words of the scratch of jf_counts (csrc/score.hip launch_jf_counts): the boundary bit planes of the prediction and of
+        the ground truth per object, one 64-bit word per 64 columns of a row."""
+        return 4 * n_objects * H * -(-W // 64)
+
+    def jf_counts(self, pred, gt, objects, counts, scratch=None, *, H, W, radius):
+        """PROB_TO_ID flags == 64 (ABI 10, include/cutie_hip.h): pred, gt uint8 [H, W] (contiguous) -> counts int32 [n, 8], WRITTEN by the
+        launch: per object of ``objects`` (a sequence of distinct ids 1 .. 254, or an int32 tensor of them on the device, which is not
+        inspected) |pred & gt|, |pred | gt|, boundary pixels of pred, of gt, pred boundary pixels within ``radius`` of a gt boundary
+        pixel, gt boundary pixels within ``radius`` of a pred one, area of pred, of gt -- the integers of DAVIS J and F
+        (inference/utils/davis_metrics.py).  scratch int32 [>= jf_scratch_words(H, W, n)], 16-byte aligned (allocated here when not
+        given); counts 16-byte aligned."""
+        H, W, radius = int(H), int(W), int(radius)
+        if torch.is_tensor(objects):
+            if objects.dtype != torch.int32 or objects.dim() != 1 or not objects.is_contiguous():
+                raise ValueError('jf_counts: objects on the device are a contiguous int32 [n]')
+            n, objs = int(objects.numel()), objects
+        else:
+            ids = [int(v) for v in objects]
+            n = len(ids)
+            if any(v < 1 or v >= 255 for v in ids):
+                raise ValueError(f'jf_counts: object ids are 1 .. 254 (0 is the background, 255 the void label), not {ids}')
+            if len(set(ids)) != n:
+                raise ValueError(f'jf_counts: duplicate object ids in {ids}')
+            objs = None
+        if not 1 <= n <= self.JF_MAX_OBJECTS:
+            raise ValueError(f'jf_counts: {n} objects, 1 .. {self.JF_MAX_OBJECTS}')
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f'jf_counts: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        if not 1 <= radius <= self.JF_MAX_RADIUS:
+            raise ValueError(f'jf_counts: radius {radius}, 1 .. {self.JF_MAX_RADIUS}')
+        for name, t in (('pred', pred), ('gt', gt)):
+            if t.dtype != torch.uint8 or tuple(t.shape) != (H, W) or not t.is_contiguous():
+                raise ValueError(f'jf_counts: {name} is a contiguous uint8 [{H}, {W}], not {t.dtype} {tuple(t.shape)}')
+        if counts.dtype != torch.int32 or counts.numel() != n * 8 or not counts.is_contiguous():
+            raise ValueError(f'jf_counts: counts is a contiguous int32 [{n}, 8]')
+        need = self.jf_scratch_words(H, W, n)
+        if scratch is None:
+            scratch = torch.empty(need, dtype=torch.int32, device=pred.device)
+            self.keep.append(scratch)
+        elif scratch.dtype != torch.int32 or scratch.numel() < need:
+            raise ValueError(f'jf_counts: scratch is int32 [>= {need}]')
+        if objs is None:
+            objs = torch.tensor(ids, dtype=torch.int32).to(pred.device)
+            self.keep.append(objs)
+        return self.add(PROB_TO_ID, 64, [0, H, W, 0, 0, radius, 0, 0, min(scratch.numel(), (1 << 31) - 1), n], [],
+                        [None, None, pred, gt, None, scratch, objs, counts])
+
     def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
         """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32
         [OW + OH, K + 2]), scratch = f32 [C, H, OW].  src_u8: src is u8 [H, W, C] with row stride `ldrow` bytes (ToTensor on the fly;

@@ -16,6 +16,8 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
 
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
+        [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
+                            has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
 
 ``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
 cutie_amd/inference/data/device_ingest.py).  ``--ingest device-decode``: JPEG frames of a directory are parsed on the host and
@@ -139,7 +141,10 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 
 
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
-                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host') -> Dict:
+                  mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
+                  gt_dir: Optional[str] = None) -> Dict:
+    """gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
+    joins the result."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -188,8 +193,12 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             processor.step(checked(upload(frame)), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
                            force_permanent=True)
         # 2. the whole video
+        scorer = None
+        if gt_dir is not None:
+            from .inference.utils.davis_metrics import SequenceScorer
+            scorer = SequenceScorer(gt_dir, '', dev, skip_first_last=False)
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
-                            palette=palette, processor=processor, egress=egress)
+                            palette=palette, processor=processor, egress=egress, scorer=scorer)
         total, n, cleanups = 0.0, 0, 0
         try:
             ahead = Window(src, upload, checked, 1)           # the next frame is on the device while this one is stepped
@@ -207,7 +216,10 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         finally:
             saver.end()
             src.close()
-    return {'frames': n, 'seconds': total, 'cleanups': cleanups, 'num_objects': num_objects, 'processor': processor}
+    out = {'frames': n, 'seconds': total, 'cleanups': cleanups, 'num_objects': num_objects, 'processor': processor}
+    if scorer is not None:
+        out['scores'] = saver.scores
+    return out
 
 
 def arg_parser() -> ArgumentParser:
@@ -223,6 +235,7 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU; device-decode: decode JPEG frames on the GPU too')
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES), help='device: the GPU writes the PNG streams of the masks (ResultSaver(egress=...))')
+    ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
     return ap
 
 
@@ -236,7 +249,10 @@ def main():
     else:
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
-                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress)
+                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt)
+    if args.gt is not None and r['scores'] is not None:
+        from .inference.utils.davis_metrics import global_line, summarize
+        print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))
     print(f'Total processing time: {r["seconds"]}\nTotal processed frames: {r["frames"]}\n'
           f'FPS: {r["frames"] / max(r["seconds"], 1e-9)}\nMax allocated memory (MB): {torch.cuda.max_memory_allocated() / 2 ** 20}')
 

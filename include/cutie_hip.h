@@ -28,6 +28,7 @@ extern "C" {
 #define CUTIE_OP_NF 6
 #define CUTIE_OP_NP 16
 #define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
+#define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
 
 typedef struct cutie_op {
     int32_t kind;               /* CUTIE_OP_* */
@@ -356,7 +357,29 @@ enum {
      *    H * W < 2^31.  One sweep over the plane finds the runs of all objects (the transposition happens in LDS tiles); every offset
      *    comes from a scan in a fixed order, the per-object byte and area totals from integer atomics: the bytes depend on the plane and
      *    the object list alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch:
-     *    H, W < 1, H * W >= 2^31, n outside 0 .. 255, a negative capacity, a null or misaligned pointer, a scratch that is too small. */
+     *    H, W < 1, H * W >= 2^31, n outside 0 .. 255, a negative capacity, a null or misaligned pointer, a scratch that is too small.
+     * ABI 10 -- DAVIS J&F on the device (not in the reference, whose docs/EVALUATION.md hands the PNG folder to davis2017-evaluation; here
+     *    eval_vos --score, cutie_amd/inference/utils/davis_metrics.py; the arithmetic is that package's metrics.py / utils.py seg2bmap):
+     *  flags == 64, a stage ON ITS OWN (64 combined with any other flag stays the "unknown flags" error): the integers of J and F of a
+     *    predicted id plane p2 against a ground-truth id plane p3, both uint8 [i1, i2] = [H, W], row-major and contiguous (kernels in
+     *    score.hip; the numpy / scipy model: tests/jf_ref.py).  i0, i3, i4, i6, i7 and p0, p1, p4 unused.
+     *    p6 = object ids int32 [i9], 4-byte aligned, i9 = n, 1 <= n <= 255: every entry is scored on its own as the binary masks
+     *    P = (p2 == id) and G = (p3 == id); values of the planes that are not listed are background for every listed object, in both
+     *    planes -- so ground-truth 255 (DAVIS void) never matches, as after davis2017's get_all_masks has zeroed it (the package also
+     *    takes the void pixels out of the prediction; this stage does not: a known difference).  Entries are 1 .. 254; any other
+     *    entry is scored as an absent object (all counts 0); an entry equal to an earlier one gets the same counts again.
+     *    i5 = r, the match radius, 1 <= r <= CUTIE_JF_MAX_RADIUS; the host computes ceil(0.008 * sqrt(H*H + W*W)) in float64.
+     *    p7 = counts int32 [n, 8], 16-byte aligned, WRITTEN by the launch (whatever it held before): per object 0 |P & G|, 1 |P | G|,
+     *    2 boundary pixels of P, 3 boundary pixels of G, 4 boundary pixels of P within r of a boundary pixel of G, 5 boundary pixels of G
+     *    within r of a boundary pixel of P, 6 |P|, 7 |G|.  Boundary map = seg2bmap at equal size: b = (s ^ e) | (s ^ so) | (s ^ se) over the
+     *    east, south and south-east neighbours; the last row uses s ^ e only, the last column s ^ so only, the bottom-right pixel is 0.
+     *    "Within r": B has a boundary pixel at (y + dy, x + dx) inside the image with dy*dy + dx*dx <= r*r -- dilation by disk(r) with
+     *    nothing outside the image.
+     *    p5 = int32 scratch of i8 words, 16-byte aligned, i8 >= 4 * n * H * ceil(W / 64) (cutie_amd/ops.py OpList.jf_scratch_words): the
+     *    boundary bit planes of both ids planes per object, one 64-bit word per 64 columns of a row.
+     *    H * W < 2^31, so every count fits.  All sums are integers gathered with integer atomics: the counts depend on the planes, the
+     *    object list and r alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch:
+     *    H, W < 1, H * W >= 2^31, n outside 1 .. 255, r outside 1 .. 40, a null or misaligned pointer, a scratch that is too small. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).

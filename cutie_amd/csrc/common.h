@@ -91,4 +91,5 @@ int launch_jpeg(const cutie_op* op, hipStream_t s);          // jpeg.hip: RESIZE
 int launch_png_deflate(const cutie_op* op, int H, int W, hipStream_t s);   // png.hip: PROB_TO_ID with flags&8 (ABI 7)
 int launch_rle_encode(const cutie_op* op, hipStream_t s);                  // rle.hip: PROB_TO_ID with flags == 32 (ABI 9)
 int launch_jf_counts(const cutie_op* op, hipStream_t s);                   // score.hip: PROB_TO_ID with flags == 64 (ABI 10)
+int launch_jpeg_encode(const cutie_op* op, hipStream_t s);                 // jpeg_enc.hip: PROB_TO_ID with flags == 128 (ABI 11)
 void cutie_set_error(const char* fmt, ...);

@@ -1566,6 +1566,7 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
         case CUTIE_OP_PROB_TO_ID: {
             if (op->flags == 32) return launch_rle_encode(op, s);                     // COCO RLE strings of an existing plane (ABI 9): a stage on its own
             if (op->flags == 64) return launch_jf_counts(op, s);                      // DAVIS J&F counts of two existing planes (ABI 10): a stage on its own
+            if (op->flags == 128) return launch_jpeg_encode(op, s);                   // JPEG entropy segment of a frame + overlay (ABI 11): a stage on its own
             if (op->flags & ~31) { cutie_set_error("prob_to_id: unknown flags %d", op->flags); return -2; }
             const bool resample = op->flags & 4, deflate = op->flags & 8;
             if (op->flags & 16) {                                                     // S sources merged (ABI 8): every check before any launch

@@ -9,7 +9,7 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
 
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
-        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device]      (multi-scale testing: one run per --size with --save-scores, then
+        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device] [--overlay device]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
         [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
                                             no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
@@ -43,7 +43,7 @@ from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
 from .inference.utils.burst_utils import BURSTResultHandler
 from .inference.utils.davis_metrics import SequenceScorer, global_line, write_results
-from .inference.utils.results_utils import EGRESS_MODES, ResultSaver, make_zip
+from .inference.utils.results_utils import EGRESS_MODES, OVERLAY_MODES, ResultSaver, make_zip
 
 log = logging.getLogger()
 
@@ -76,10 +76,11 @@ def _read_ahead(vid_reader, workers, ingest):
     return ReadAhead(vid_reader, workers=workers, getitem=lambda i: vid_reader.get(i, ingest=ingest))
 
 
-def _feed(vid_reader, dev, depth, read_workers, ingest) -> Window:
+def _feed(vid_reader, dev, depth, read_workers, ingest, keep_u8=False) -> Window:
     """The records of a video: decoded ahead on threads (eval_vos.py:92), then up to ``depth`` of them on the device ahead of the step
-    that takes them (uploaded as they enter the window, their deferred decode check made as they leave it)."""
-    return Window(_read_ahead(vid_reader, read_workers, ingest), lambda d: to_device(d, dev, defer_check=True), finish, depth)
+    that takes them (uploaded as they enter the window, their deferred decode check made as they leave it).  keep_u8: the device-ingest
+    records keep their uint8 frame on the device (``info['image_u8']``: the device overlay of ``--visualize`` reads it)."""
+    return Window(_read_ahead(vid_reader, read_workers, ingest), lambda d: to_device(d, dev, defer_check=True, keep_u8=keep_u8), finish, depth)
 
 
 def _take(window, dev, lookahead):
@@ -93,7 +94,7 @@ def _take(window, dev, lookahead):
 
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
-           score_output_root=None, score_gt=None, score_all_frames=False) -> ResultSaver:
+           score_output_root=None, score_gt=None, score_all_frames=False, overlay='host') -> ResultSaver:
     """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer."""
     scorer = None
     if score_gt is not None:
@@ -103,7 +104,7 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
     return ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=core.object_manager,
                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
-                       score_output_root=score_output_root, egress=egress, scorer=scorer,
+                       score_output_root=score_output_root, egress=egress, scorer=scorer, overlay=overlay,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -124,7 +125,12 @@ def _with_json(stats, saver):
 def _save(saver, prob, info, last_frame, save_all):
     if save_all or info['save']:
         saver.process(prob, info['frame'], resize_needed=info['resize_needed'], shape=info['shape'], last_frame=last_frame,
-                      path_to_image=info['path_to_image'])
+                      path_to_image=info['path_to_image'], **_frame_kw(saver, info))
+
+
+def _frame_kw(saver, info) -> Dict:
+    """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feed(keep_u8=True)``)."""
+    return {'image_u8': info.get('image_u8')} if saver.overlay == 'device' else {}
 
 
 def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
@@ -157,19 +163,22 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict:
+                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
+    overlay: 'host' | 'device' (``ResultSaver``'s ``overlay``: with ``visualize`` the GPU blends and writes the JPEGs' entropy-coded segments).
     score_gt: the root of the ground-truth PNGs -- the video is scored (J&F counts on the device, ``_saver``) and 'scores' joins the stats."""
     _check_ingest(ingest)
     from .inference import inference_core as IC
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames)
+                   egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames,
+                   overlay=overlay)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
-        feed = _feed(vid_reader, network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest)
+        feed = _feed(vid_reader, network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
+                     keep_u8=saver.overlay == 'device')
         _run_video([lambda: nullcontext(processor)], [feed], len(vid_reader), 0, stats,
                    lambda probs, info, last: _save(saver, probs[0], info, last, save_all), dev=network.device, lookahead=lookahead)
     finally:
@@ -179,7 +188,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict:
+                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -204,17 +213,19 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
         raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames)
+                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, overlay=overlay)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
             saver.process_merged(probs, info['frame'], info['shape'], last_frame=last_frame, path_to_image=info['path_to_image'],
-                                 id_maps=[{t: o.id for t, o in c.object_manager.tmp_id_to_obj.items()} for c in members.cores])
+                                 id_maps=[{t: o.id for t, o in c.object_manager.tmp_id_to_obj.items()} for c in members.cores],
+                                 **_frame_kw(saver, info))
 
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
-        feeds = [_feed(rd, network.device, depth, read_workers, ingest) for rd in vid_readers]
+        # (the first member's records carry the frame for the overlay: `save` gets its info)
+        feeds = [_feed(rd, network.device, depth, read_workers, ingest, keep_u8=(s == 0 and saver.overlay == 'device')) for s, rd in enumerate(vid_readers)]
         _run_video([lambda s=s: members.clip(s) for s in range(S)], feeds, n, 0, stats, save, dev=network.device, lookahead=lookahead)
     finally:
         saver.end()
@@ -233,7 +244,7 @@ def lockstep_key(vid_reader):
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None, egress='host', score_gt=None, score_all_frames=False) -> Dict[int, Dict]:
+                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
@@ -245,12 +256,12 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     dev = network.device
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
-                     score_all_frames=score_all_frames) for c, rd in enumerate(vid_readers)]
+                     score_all_frames=score_all_frames, overlay=overlay) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
     try:
-        feeds = [_feed(rd, dev, 16 if lookahead else 1, read_workers, ingest) for rd in vid_readers]
+        feeds = [_feed(rd, dev, 16 if lookahead else 1, read_workers, ingest, keep_u8=savers[c].overlay == 'device') for c, rd in enumerate(vid_readers)]
         for ti in range(T):
             data, masks, valid, hints = (list(v) for v in zip(*[_take(w, dev, lookahead) for w in feeds]))
             any_mask = any(m is not None for m in masks)
@@ -307,6 +318,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES),
                     help='device: the GPU resamples + argmaxes the result in one kernel and writes the PNG zlib stream; the host copies a few '
                          'KB per frame without blocking and only wraps them in PNG chunks (cutie_amd/inference/utils/results_utils.py)')
+    ap.add_argument('--overlay', default='host', choices=list(OVERLAY_MODES),
+                    help='--visualize: device = the GPU blends the object colours over the frame and writes the JPEG entropy-coded segment '
+                         '(the same files as the host overlay; keeps --egress device; best with --ingest device | device-decode, which '
+                         'leave the uint8 frame on the GPU -- with --ingest host every frame is decoded again and uploaded)')
     ap.add_argument('--score', action='store_true',
                     help='DAVIS J&F of the run, counted on the GPU while the videos run (cutie_amd/inference/utils/davis_metrics.py): writes '
                          'global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output.  Not for BURST or long-id (RGB) masks: '
@@ -379,7 +394,7 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
     mask_root = path.join(args.output, 'Annotations')
     common = dict(dataset=args.dataset, visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
                   save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
-                  egress=args.egress, save_all=not burst)     # (no ingest=: the readers carry the mode)
+                  egress=args.egress, save_all=not burst, overlay=getattr(args, 'overlay', 'host'))     # (no ingest=: the readers carry the mode)
     score = bool(getattr(args, 'score', False))
     if score:
         common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames))

@@ -86,12 +86,13 @@ class DecodeCheck:
             decode_stats['max_sync_rounds'] = max(decode_stats['max_sync_rounds'], rounds)
 
 
-def jpeg_to_device(pkt: J.Packet, device, size_hw=None, stream=None, name: Optional[str] = None, check: bool = True):
+def jpeg_to_device(pkt: J.Packet, device, size_hw=None, stream=None, name: Optional[str] = None, check: bool = True, keep_u8: bool = False):
     """A parsed JPEG -> f32 [3, h, w] contiguous on `device`, equal to ToTensor(+ antialiased resize) of PIL's decode.  One upload of
     the packet, then the three decode stages and the resize on `stream` (default: the current stream), into buffers of this call.
     check=True: wait for the error word and raise ValueError naming the frame (`name`, default the packet's file) if the data was bad.
     check=False: -> (frame, DecodeCheck); the caller must call the check before it uses the frame's result -- until then the frame may
-    hold garbage, after a passed check it is the decoded frame."""
+    hold garbage, after a passed check it is the decoded frame.
+    keep_u8=True: the decoded uint8 [H, W, 3] frame on the device joins the result: -> (frame, u8) | (frame, DecodeCheck, u8)."""
     dev = torch.device(device)
     on_gpu = dev.type == 'cuda'
     H, W = pkt.shape
@@ -110,14 +111,14 @@ def jpeg_to_device(pkt: J.Packet, device, size_hw=None, stream=None, name: Optio
         chk = DecodeCheck(b['status'], pkt.source if name is None else name)
     if check:
         chk()
-        return out
-    return out, chk
+        return (out, b['rgb']) if keep_u8 else out
+    return (out, chk, b['rgb']) if keep_u8 else (out, chk)
 
 
-def frame_to_device(rgb_u8, device, size_hw=None, stream=None) -> torch.Tensor:
+def frame_to_device(rgb_u8, device, size_hw=None, stream=None, keep_u8: bool = False):
     """uint8 [H, W, C] (numpy array or CPU tensor; rows may be padded, pixels packed) -> f32 [C, h, w] contiguous on `device`,
     (h, w) = size_hw (default (H, W): ToTensor only).  One synchronous uint8 copy, one RESIZE launch on `stream` (default: the
-    current stream)."""
+    current stream).  keep_u8=True: -> (frame, the uploaded uint8 [H, W, C] on the device)."""
     u8 = torch.from_numpy(rgb_u8) if isinstance(rgb_u8, np.ndarray) else rgb_u8
     if u8.dtype != torch.uint8 or u8.dim() != 3 or u8.stride(2) != 1 or u8.stride(1) != u8.shape[2]:
         raise ValueError(f'frame_to_device: expected packed uint8 [H, W, C], got {u8.dtype} {tuple(u8.shape)} strides {u8.stride()}')
@@ -130,22 +131,27 @@ def frame_to_device(rgb_u8, device, size_hw=None, stream=None) -> torch.Tensor:
         out = _resize(ol, src, H, W, C, h, w, src.stride(0), device)
         ol.finalize()
         ol.run()
-    return out
+    return (out, src) if keep_u8 else out
 
 
-def to_device(record: Dict, device, stream=None, defer_check: bool = False) -> Dict:
+def to_device(record: Dict, device, stream=None, defer_check: bool = False, keep_u8: bool = False) -> Dict:
     """Move a reader record to `device`: ``rgb_u8`` (VideoReader(ingest='device')) becomes ``rgb`` = f32 [3, h, w], h, w =
     ``info['rgb_shape']``, and both device-ingest keys are dropped, so the record equals the host-path one.  A host-path record
     (it holds ``rgb``) is moved as the drivers always did: ``rgb.to(device)``.  A 'device-decode' record (it holds ``jpeg``, a parsed
     packet) is decoded on the GPU on the current stream (jpeg_to_device); a corrupt frame raises ValueError with its file name --
     here, or with defer_check=True in ``finish(record)``, which the caller must call before it uses the record's result (the record
     holds ``decode_check`` until then: the drivers queue several frames ahead and check each when it leaves the look-ahead window,
-    so the host does not wait for every decode)."""
+    so the host does not wait for every decode).
+    keep_u8=True: the original-size uint8 [H, W, 3] frame that a 'device' record uploaded or a 'device-decode' record decoded stays on
+    the device as ``record['info']['image_u8']`` (what ``ResultSaver(overlay='device')`` blends the masks over: no second decode, no
+    upload; ``info`` is what the drivers hand to the saver).  A host-path record has no such frame and gets no key."""
     if 'jpeg' in record:
         pkt = record.pop('jpeg')
-        rgb, chk = jpeg_to_device(pkt, device, record['info'].pop('rgb_shape'), stream, record['info'].get('path_to_image') or pkt.source,
-                                  check=False)
+        rgb, chk, u8 = jpeg_to_device(pkt, device, record['info'].pop('rgb_shape'), stream, record['info'].get('path_to_image') or pkt.source,
+                                      check=False, keep_u8=True)
         record['rgb'] = rgb
+        if keep_u8:
+            record['info']['image_u8'] = u8
         if defer_check:
             record['decode_check'] = chk
         else:
@@ -155,7 +161,9 @@ def to_device(record: Dict, device, stream=None, defer_check: bool = False) -> D
         record['rgb'] = record['rgb'].to(device)
         return record
     u8 = record.pop('rgb_u8')
-    record['rgb'] = frame_to_device(u8, device, record['info'].pop('rgb_shape'), stream)
+    record['rgb'], src = frame_to_device(u8, device, record['info'].pop('rgb_shape'), stream, keep_u8=True)
+    if keep_u8 and src.shape[2] == 3:
+        record['info']['image_u8'] = src
     return record
 
 

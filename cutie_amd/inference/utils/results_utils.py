@@ -21,7 +21,15 @@ not wait; the writer thread waits on the event, checks the error word, wraps the
 hold the same mode, palette and pixels as the host path's; their bytes differ (other filter and Huffman codes, always 8 bits).
 With BURST the same op list carries the RLE stage (csrc/rle.hip) over the id plane on annotated frames: the objects' strings, their
 table and a status block ride a second pinned copy in front of the same event, and the writer thread slices the strings out; if the
-strings did not fit the device stream the writer encodes that frame on the host from a copy of the id plane."""
+strings did not fit the device stream the writer encodes that frame on the host from a copy of the id plane.
+
+``overlay='device'`` (not in the reference): the ``visualize`` JPEGs leave the GPU as finished entropy-coded
+segments.  While the id plane is still on the device -- behind the id stage of either egress mode -- one more op (PROB_TO_ID flags == 128,
+csrc/jpeg_enc.hip) blends the object colours over the uint8 frame and encodes the result exactly as libjpeg-turbo would; status and
+stream ride a pinned copy in front of the frame's event, and the writer thread wraps them (utils/jpeg_writer.py) into ``<frame>.jpg``:
+the bytes of the host overlay's file.  The frame comes as ``image_u8`` (device ingest keeps it: device_ingest.to_device(keep_u8=True));
+without it the saver decodes ``path_to_image`` with PIL and uploads it -- the slow pairing: the decode and a synchronous copy per frame on
+the stepping thread.  A frame whose stream does not fit the capacity is encoded by the host code, with one warning per saver."""
 import logging
 import os
 import shutil
@@ -38,6 +46,7 @@ from PIL import Image
 
 from ...utils.pano_utils import ID2RGBConverter
 from . import coco_rle
+from . import jpeg_writer
 from . import png as png_container
 
 log = logging.getLogger()
@@ -64,6 +73,8 @@ davis_palette = davis_palette_np.tobytes()
 EGRESS_MODES = ('host', 'device')
 EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
 RLE_TABLE = 16 + 255 * 16   # BURST: bytes of the status block and the table of up to 255 objects in front of the RLE strings
+OVERLAY_MODES = ('host', 'device')
+JPEG_SLAB = 256 * 1024      # overlay='device': bytes of the first device-to-host copy of a frame's JPEG: status + the head of the stream (a 480p overlay is 30-120 KB)
 RLE_SLAB = 256 * 1024       # ... and of the whole device-to-host copy: status, table and the strings (a frame that needs more is encoded on the host)
 
 
@@ -71,20 +82,36 @@ class _EgressBuffers:
     """What one frame in flight owns (egress='device'): the id plane, [status | stream] on the device, the pinned slab and the event
     recorded behind the copy.  Recycled through ResultSaver's pool once the writer thread is done with them."""
 
-    def __init__(self, H, W, device, rle=False):
+    def __init__(self, H, W, device, rle=False, png=True, jpeg=False):
         from ... import ops as O
-        self.H, self.W = H, W
+        self.H, self.W, self.kinds = H, W, (rle, png, jpeg)
+        on_gpu = torch.device(device).type == 'cuda'
+        staging = (lambda n: torch.empty(n, dtype=torch.uint8).pin_memory()) if on_gpu else (lambda n: torch.empty(n, dtype=torch.uint8))
         if rle:                                  # BURST: [status | table | strings] on the device and pinned
             self.rle_dev = torch.empty(RLE_SLAB, dtype=torch.uint8, device=device)
             self.rle_status, self.rle_table = self.rle_dev[:16].view(torch.int32), self.rle_dev[16:RLE_TABLE].view(torch.int32).view(-1, 4)
             self.rle_stream = self.rle_dev[RLE_TABLE:]
-            self.rle_host = torch.empty(RLE_SLAB, dtype=torch.uint8).pin_memory()
-        cap = O.OpList.png_capacity(H, W)
-        self.ids = torch.empty((H, W), dtype=torch.uint8, device=device)
-        self.dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
-        self.status, self.stream = self.dev[:16].view(torch.int32), self.dev[16:]
-        self.host = torch.empty(min(16 + cap, EGRESS_SLAB), dtype=torch.uint8).pin_memory()
-        self.event = torch.cuda.Event()
+            self.rle_host = staging(RLE_SLAB)
+        if png:
+            cap = O.OpList.png_capacity(H, W)
+            self.ids = torch.empty((H, W), dtype=torch.uint8, device=device)
+            self.dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
+            self.status, self.stream = self.dev[:16].view(torch.int32), self.dev[16:]
+            self.host = staging(min(16 + cap, EGRESS_SLAB))
+        if jpeg:                                 # overlay='device': [status | entropy-coded segment]
+            cap = O.OpList.jpeg_enc_capacity(H, W)
+            self.jpeg_dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
+            self.jpeg_status, self.jpeg_stream = self.jpeg_dev[:16].view(torch.int32), self.jpeg_dev[16:]
+            self.jpeg_host = staging(min(16 + cap, JPEG_SLAB))
+        self.event = torch.cuda.Event() if on_gpu else _NoEvent()      # (a CPU device: the interpreter of the tests, everything is synchronous)
+
+
+class _NoEvent:
+    def record(self):
+        pass
+
+    def synchronize(self):
+        pass
 
 
 @dataclass
@@ -99,23 +126,30 @@ class _Job:
     tmp_to_obj: Optional[dict] = None        # {tmp_id: object id} at the time of the frame
     egress: Optional[_EgressBuffers] = None  # egress='device': the mask arrives in these (mask is None)
     rle: bool = False                        # egress='device', BURST: the objects' RLE strings arrive in them as well
+    overlay: Optional[_EgressBuffers] = None  # overlay='device': the JPEG's entropy-coded segment arrives in these (the same set as `egress` when both are on)
+    frame: Optional[torch.Tensor] = None     # overlay='device': the uint8 frame the stage read (kept until the writer is done: see _queue_overlay)
+    ids: Optional[torch.Tensor] = None       # overlay='device': the id plane on the device (a frame whose stream overflowed is blended on the host)
 
 
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
-                 processor=None, egress='host', scorer=None):
+                 processor=None, egress='host', scorer=None, overlay='host'):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
         stream, see the module docstring; needs ``processor``).  A saver falls back to the host path -- ``self.egress`` says which one
-        runs -- with ``use_long_id`` (RGB masks), with ``visualize`` (the overlay needs the ids on the host) and without ``save_mask``;
+        runs -- with ``use_long_id`` (RGB masks), with ``visualize`` (the host overlay needs the ids on the host; not with
+        ``overlay='device'``) and without ``save_mask``;
         ``save_scores`` keeps its own copy of the probabilities next to the device-encoded mask: with it -- multi-scale runs -- ``process``
         still builds the full-size fp32 probabilities when the frame was resized and blocks on their copy, so 'device' saves only the
         PNG encode there, not the stall.
         ``scorer`` (not in the reference; utils/davis_metrics.py SequenceScorer): every frame's uint8 id plane is
         handed to ``scorer.add`` while it is still on the device -- before the copy of the host path, behind the id stage of the device
-        path and of ``process_merged`` -- and ``end`` leaves ``scorer.finish()`` in ``self.scores``.  Long ids cannot be scored."""
+        path and of ``process_merged`` -- and ``end`` leaves ``scorer.finish()`` in ``self.scores``.  Long ids cannot be scored.
+        ``overlay``: 'host' (default: the writer thread re-decodes the frame, blends in float and PIL encodes the JPEG) | 'device' (the
+        GPU blends and writes the JPEG's entropy-coded segment, see the module docstring; needs ``processor``; the files are the same
+        bytes).  It only matters with ``visualize``; ``use_long_id`` savers keep the host overlay -- ``self.overlay`` says which one runs."""
         if scorer is not None and use_long_id:
             raise ValueError('scorer: J&F is counted on uint8 id planes; long ids (RGB masks) cannot be scored')
         self.scorer, self.scores = scorer, None
@@ -123,6 +157,10 @@ class ResultSaver:
             raise ValueError(f'egress must be one of {EGRESS_MODES}, not {egress!r}')
         if egress == 'device' and processor is None:
             raise ValueError("egress='device' needs the processor (its device and object table)")
+        if overlay not in OVERLAY_MODES:
+            raise ValueError(f'overlay must be one of {OVERLAY_MODES}, not {overlay!r}')
+        if overlay == 'device' and processor is None:
+            raise ValueError("overlay='device' needs the processor (its device)")
         if save_scores and score_output_root is None:
             raise ValueError('save_scores needs score_output_root')
         self.save_scores, self.score_output_root = save_scores, score_output_root
@@ -141,7 +179,9 @@ class ResultSaver:
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
-        self.egress = 'device' if (egress == 'device' and not use_long_id and not visualize and save_mask) else 'host'
+        self.overlay = 'device' if (overlay == 'device' and visualize and not use_long_id) else 'host'
+        self.egress = 'device' if (egress == 'device' and not use_long_id and (not visualize or self.overlay == 'device') and save_mask) else 'host'
+        self._jpeg_scratch, self._jpeg_tables, self._jpeg_colors, self._jpeg_warned = None, None, {}, False
         self._free: Queue = Queue()              # recycled _EgressBuffers
         self._allocated, self._luts, self._scratch, self._wstream = 0, {}, None, None
         if self.visualize:
@@ -153,9 +193,11 @@ class ResultSaver:
         self.thread.start()
 
     def process(self, prob: torch.Tensor, frame_name: str, resize_needed: bool = False, shape: Optional[Tuple[int, int]] = None,
-                last_frame: bool = False, path_to_image: str = None):
+                last_frame: bool = False, path_to_image: str = None, image_u8: Optional[torch.Tensor] = None):
+        """``image_u8`` (overlay='device'): the frame as uint8 [H, W, 3] at the output size, on the device or on the host; without it
+        ``path_to_image`` is decoded with PIL and uploaded (slow: see the module docstring)."""
         if self.egress == 'device':
-            return self._process_device(prob, frame_name, resize_needed, shape, last_frame)
+            return self._process_device(prob, frame_name, resize_needed, shape, last_frame, path_to_image, image_u8)
         if resize_needed:
             prob = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0]
         out_dtype = torch.int32 if self.use_long_id else torch.uint8
@@ -171,12 +213,14 @@ class ResultSaver:
         if self.scorer is not None:
             self.scorer.add(frame_name, mask)
         q = (prob * 255).to(torch.uint8).cpu() if self.save_scores else None       # == numpy astype(uint8) of prob*255
-        self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, [o.id for o in self.object_manager.obj_to_tmp_id],
+        all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
+        ov = self._queue_overlay(None, mask, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, all_ids,
                             prob=q, last_frame=last_frame,
-                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None))
+                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, **ov))
 
     # ---- egress='device' --------------------------------------------------------------------------------------------------------
-    def _take(self, H, W, device) -> _EgressBuffers:
+    def _take(self, H, W, device, png=True) -> _EgressBuffers:
         """Buffers for one frame: a recycled set, a new one while fewer than the queue can hold (+ the one in the writer's hands and
         this one) exist, else the next set the writer gives back."""
         while True:
@@ -185,13 +229,78 @@ class ResultSaver:
             except Empty:
                 if self._allocated < self.queue.maxsize + 2:
                     self._allocated += 1
-                    return _EgressBuffers(H, W, device, rle=self.json_style == 'burst')
+                    return _EgressBuffers(H, W, device, rle=self.json_style == 'burst' and png, png=png, jpeg=self.overlay == 'device')
                 b = self._free.get()
-            if (b.H, b.W) == (H, W):
+            if (b.H, b.W) == (H, W) and b.kinds[1] == png:
                 return b
             self._allocated -= 1                 # another geometry: dropped
 
-    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame):
+    # ---- overlay='device' -------------------------------------------------------------------------------------------------------
+    def _queue_overlay(self, b, ids, all_ids, path_to_image, image_u8) -> dict:
+        """Queue the blend + JPEG stage of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), and the pinned copy of its status and stream head.  ``b``: the frame's buffers (egress='device'; its event is recorded
+        by the caller behind everything) or None: a set of its own is taken and its event recorded here.  -> the _Job fields.
+        The frame tensor: the op list holds it while the stage is being queued, and the job holds it (and the id plane) until the
+        writer thread is done with the frame -- so it outlives the launch that reads it on the stream that owns it, whoever made it."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        if image_u8 is None:
+            if path_to_image is None:
+                raise ValueError('Cannot visualize without path_to_image or image_u8')
+            image_u8 = torch.from_numpy(np.array(Image.open(path_to_image).convert('RGB')))
+        if image_u8.dtype != torch.uint8 or tuple(image_u8.shape) != (H, W, 3):
+            raise ValueError(f'image_u8 is uint8 [{H}, {W}, 3] (the output size), not {image_u8.dtype} {tuple(image_u8.shape)}')
+        if image_u8.device != dev or image_u8.stride(2) != 1 or image_u8.stride(1) != 3:
+            image_u8 = image_u8.to(dev).contiguous()
+        if self._jpeg_tables is None:
+            qt = jpeg_writer.quant_tables(jpeg_writer.QUALITY)
+            self._jpeg_tables = (qt, torch.from_numpy(qt.view(np.int16)).to(dev))
+        colors = self._jpeg_colors.get(tuple(all_ids))
+        if colors is None:                       # (changes when objects come or go, not per frame)
+            colors = self._jpeg_colors[tuple(all_ids)] = torch.from_numpy(jpeg_writer.color_table(self.colors, all_ids)).to(dev)
+        if self._jpeg_scratch is None or self._jpeg_scratch[0] != (H, W):
+            self._jpeg_scratch = ((H, W), torch.empty(O.OpList.jpeg_enc_scratch_words(H, W), dtype=torch.int32, device=dev))
+        own = b is None
+        if own:
+            b = self._take(H, W, dev, png=False)
+        ol = O.OpList()
+        ol.jpeg_encode(image_u8, ids, colors, self._jpeg_tables[1], b.jpeg_stream, b.jpeg_status, self._jpeg_scratch[1], H=H, W=W)
+        ol.run()
+        b.jpeg_host.copy_(b.jpeg_dev[:b.jpeg_host.numel()], non_blocking=True)
+        if own:
+            b.event.record()
+        return dict(overlay=b, frame=image_u8, ids=ids)
+
+    def _fetch_jpeg(self, b: _EgressBuffers):
+        """Writer thread: the frame's entropy-coded segment once its copy has landed, or None when it did not fit the device stream."""
+        b.event.synchronize()
+        length, _, err, _ = (int(v) for v in b.jpeg_host[:16].view(torch.int32))
+        if err != 0:
+            if not self._jpeg_warned:
+                self._jpeg_warned = True
+                log.warning(f'device JPEG encoder: a frame of {self.video_name} needs {length} bytes, the stream holds {b.jpeg_stream.numel()}; '
+                            f'such frames are encoded on the host')
+            return None
+        have = b.jpeg_host.numel() - 16
+        head = b.jpeg_host[16:16 + min(length, have)].numpy().tobytes()
+        if length <= have:
+            return head
+        return head + self._rest(b.jpeg_stream[have:length])
+
+    def _rest(self, tail: torch.Tensor) -> bytes:
+        """Writer thread: the part of a long stream behind the first slab, on a stream of the writer's own."""
+        if tail.device.type != 'cuda':
+            return tail.numpy().tobytes()
+        if self._wstream is None:
+            self._wstream = torch.cuda.Stream(device=tail.device)
+        rest = torch.empty(tail.numel(), dtype=torch.uint8).pin_memory()
+        with torch.cuda.stream(self._wstream):
+            rest.copy_(tail, non_blocking=True)
+        self._wstream.synchronize()
+        return rest.numpy().tobytes()
+
+    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame, path_to_image=None, image_u8=None):
         from ... import ops as O
         core = self.processor
         dev = core.network.device
@@ -227,6 +336,7 @@ class ResultSaver:
         ol.run()
         if self.scorer is not None:              # (b.ids is not handed out again before the writer is done with the frame: same stream)
             self.scorer.add(frame_name, b.ids)
+        ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         if rle:
             b.rle_host.copy_(b.rle_dev, non_blocking=True)
@@ -235,12 +345,12 @@ class ResultSaver:
         if self.save_scores:                     # as the host path: the scores of the output size
             full = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
             q = (full * 255).to(torch.uint8).cpu()
-        self.queue.put(_Job(self, None, frame_name, None, all_ids, prob=q, last_frame=last_frame,
-                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b, rle=rle))
+        self.queue.put(_Job(self, None, frame_name, path_to_image if ov else None, all_ids, prob=q, last_frame=last_frame,
+                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b, rle=rle, **ov))
 
     # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
     def process_merged(self, probs, frame_name: str, shape: Tuple[int, int], last_frame: bool = False, path_to_image: str = None, *,
-                       id_maps=None):
+                       id_maps=None, image_u8: Optional[torch.Tensor] = None):
         """One frame of a multi-scale run (not in the reference, whose protocol is one run per size with ``save_scores`` and
         scripts/merge_multi_scale.py afterwards): ``probs`` = the members' [K+1, h_s, w_s] probabilities of the frame,
         every one resampled to ``shape``, quantised to uint8 and summed as the file route does, argmax + remap -- ONE kernel (PROB_TO_ID
@@ -287,7 +397,8 @@ class ResultSaver:
             ol.run()
             if self.scorer is not None:
                 self.scorer.add(frame_name, ids)
-            self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame))
+            ov = self._queue_overlay(None, ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+            self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame, **ov))
             return
         if self._scratch is None or self._scratch[0] != (H, W):
             self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
@@ -296,9 +407,10 @@ class ResultSaver:
         ol.run()
         if self.scorer is not None:
             self.scorer.add(frame_name, b.ids)
+        ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         b.event.record()
-        self.queue.put(_Job(self, None, frame_name, None, all_ids, last_frame=last_frame, egress=b))
+        self.queue.put(_Job(self, None, frame_name, path_to_image if ov else None, all_ids, last_frame=last_frame, egress=b, **ov))
 
     def _fetch(self, b: _EgressBuffers) -> bytes:
         """Writer thread: the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
@@ -310,13 +422,7 @@ class ResultSaver:
         head = b.host[16:16 + min(length, have)].numpy().tobytes()
         if length <= have:
             return head
-        if self._wstream is None:                # the rare long stream: the rest, on a stream of the writer's own
-            self._wstream = torch.cuda.Stream(device=b.dev.device)
-        rest = torch.empty(length - have, dtype=torch.uint8).pin_memory()
-        with torch.cuda.stream(self._wstream):
-            rest.copy_(b.stream[have:length], non_blocking=True)
-        self._wstream.synchronize()
-        return head + rest.numpy().tobytes()
+        return head + self._rest(b.stream[have:length])      # the rare long stream
 
     def _fetch_rle(self, b: _EgressBuffers, all_obj_ids) -> dict:
         """Writer thread, BURST: {object id: RLE string} of the frame's non-empty objects from the device encoder (its copy has
@@ -369,12 +475,9 @@ def _writer(queue: Queue):
             strings = None
             if job.egress is not None:                             # egress='device': wrap the finished stream, no PIL
                 b = job.egress
-                try:
-                    if job.rle:
-                        strings = s._fetch_rle(b, job.all_obj_ids)
-                    data = png_container.assemble(s._fetch(b), b.H, b.W, s.palette)
-                finally:
-                    s._free.put(b)
+                if job.rle:
+                    strings = s._fetch_rle(b, job.all_obj_ids)
+                data = png_container.assemble(s._fetch(b), b.H, b.W, s.palette)
                 out_dir = path.join(s.output_root, s.video_name)
                 os.makedirs(out_dir, exist_ok=True)
                 with open(path.join(out_dir, job.frame_name[:-4] + '.png'), 'wb') as f:
@@ -415,10 +518,21 @@ def _writer(queue: Queue):
                     np.savez(path.join(sc_dir, 'backward.npz'), obj_ids=np.array([o for _, o in ids], dtype=np.int64),
                              tmp_ids=np.array([t for t, _ in ids], dtype=np.int64))
                 np.savez_compressed(path.join(sc_dir, job.frame_name[:-4] + '.npz'), prob=job.prob.numpy())
-            if s.visualize:
-                if job.path_to_image is None:
+            segment = s._fetch_jpeg(job.overlay) if job.overlay is not None else None
+            if segment is not None:                                # overlay='device': wrap the finished segment, no PIL
+                vis_dir = path.join(s.visualize_output_root, s.video_name)
+                os.makedirs(vis_dir, exist_ok=True)
+                with open(path.join(vis_dir, job.frame_name[:-4] + '.jpg'), 'wb') as f:
+                    f.write(jpeg_writer.wrap(segment, job.overlay.H, job.overlay.W, s._jpeg_tables[0]))
+            elif s.visualize:
+                if job.overlay is not None:                        # the segment did not fit the device stream: this frame on the host
+                    if out_mask is None:
+                        out_mask = job.ids.cpu().numpy()
+                    image_np = np.array(Image.open(job.path_to_image).convert('RGB')) if job.path_to_image is not None else job.frame.cpu().numpy()
+                elif job.path_to_image is None:
                     raise ValueError('Cannot visualize without path_to_image')
-                image_np = np.array(Image.open(job.path_to_image).convert('RGB'))
+                else:
+                    image_np = np.array(Image.open(job.path_to_image).convert('RGB'))
                 if rgb_mask is None:
                     rgb_mask = np.zeros((*out_mask.shape, 3), dtype=np.uint8)
                     for oid in job.all_obj_ids:
@@ -430,6 +544,10 @@ def _writer(queue: Queue):
                 Image.fromarray(blend).save(path.join(vis_dir, job.frame_name[:-4] + '.jpg'))
         except Exception as e:                                 # keep the queue draining; surface the problem
             log.error(f'result writer failed on {job.frame_name}: {e}')
+        finally:
+            b = job.egress if job.egress is not None else job.overlay
+            if b is not None:                                  # the frame's buffers go back to the pool
+                job.saver._free.put(b)
         queue.task_done()
 
 

@@ -969,6 +969,53 @@ class OpList:
         return self.add(PROB_TO_ID, 64, [0, H, W, 0, 0, radius, 0, 0, min(scratch.numel(), (1 << 31) - 1), n], [],
                         [None, None, pred, gt, None, scratch, objs, counts])
 
+    JPEG_ENC_BLOCK_WORDS = 52     # JPG_BLOCK_WORDS (csrc/jpeg_enc.hip): a coded block is at most 22 + 63 * 26 = 1660 bits
+
+    @staticmethod
+    def jpeg_enc_blocks(H, W):
+        """Coded blocks of a 4:2:0 frame: six (Y00 Y01 Y10 Y11 Cb Cr) per 16 x 16 MCU."""
+        return 6 * -(-H // 16) * -(-W // 16)
+
+    @classmethod
+    def jpeg_enc_scratch_words(cls, H, W):
+        """int32 words of the scratch of jpeg_encode (csrc/jpeg_enc.hip jpg_scratch_words; include/cutie_hip.h ABI 11): 16 words of
+        header, per coded block 32 words of coefficients, 4 of offsets and bit counts and 52 of the unstuffed stream (+ 16), and 4 words
+        per 16-word chunk of that stream."""
+        B = cls.jpeg_enc_blocks(H, W)
+        U = cls.JPEG_ENC_BLOCK_WORDS * B + 16
+        return 16 + 32 * B + 4 * B + U + 4 * -(-U // 16)
+
+    @classmethod
+    def jpeg_enc_capacity(cls, H, W, worst=False):
+        """Bytes of the stream buffer of jpeg_encode.  worst=True: what holds the segment of ANY frame -- every coded block at its 1660
+        bits and every byte a stuffed 0xFF: 2 * ceil(1660 blocks / 8) bytes, ~10 bytes per pixel, which no picture comes near.  The
+        default is the practical size the saver allocates: 1024 + 1.5 bytes per pixel, capped by the worst case (quality-75 overlays of
+        video frames take 0.05 .. 0.3 bytes per pixel, uniform noise 0.6); a frame that needs more sets the overflow bit and says what
+        it needs."""
+        full = 2 * -(-1660 * cls.jpeg_enc_blocks(H, W) // 8)
+        return full if worst else min(full, -(-(1024 + 3 * H * W // 2) // 4) * 4)
+
+    def jpeg_encode(self, frame, ids, colors, qtables, stream, status, scratch, *, H, W, ldrow=None):
+        """PROB_TO_ID flags == 128 (ABI 11, include/cutie_hip.h): frame uint8 [H, W, 3] (row stride ``ldrow`` bytes, default the
+        tensor's; pixels packed) with the colours of ``colors`` (uint8 [256, 4]) blended over it where ``ids`` (uint8 [H, W] contiguous,
+        or None: the frame as it is) is not 0 -> ``stream`` uint8 [capacity] = the entropy-coded segment of the baseline 4:2:0 JPEG
+        that libjpeg-turbo writes for the blended frame with the quantisation tables ``qtables`` (uint16 [2, 64], natural order, 1 .. 255).
+        status int32 [4] = (stream bytes, 0, error bits: 1 = the capacity is too small and nothing was written, 0); scratch int32
+        [>= jpeg_enc_scratch_words(H, W)], 16-byte aligned.  inference/utils/jpeg_writer.py wraps the stream into a file."""
+        H, W = int(H), int(W)
+        if frame.dtype != torch.uint8 or frame.dim() != 3 or tuple(frame.shape) != (H, W, 3) or frame.stride(2) != 1 or frame.stride(1) != 3:
+            raise ValueError(f'jpeg_encode: frame is uint8 [{H}, {W}, 3] with packed pixels, not {frame.dtype} {tuple(frame.shape)} strides {frame.stride()}')
+        ldrow = int(frame.stride(0) if ldrow is None else ldrow)
+        if ids is not None:
+            if ids.dtype != torch.uint8 or tuple(ids.shape) != (H, W) or not ids.is_contiguous():
+                raise ValueError(f'jpeg_encode: ids is a contiguous uint8 [{H}, {W}]')
+            if colors is None or colors.dtype != torch.uint8 or colors.numel() != 1024 or not colors.is_contiguous():
+                raise ValueError('jpeg_encode: colors is a contiguous uint8 [256, 4]')
+        if qtables.dtype not in (torch.uint16, torch.int16) or qtables.numel() != 128 or not qtables.is_contiguous():
+            raise ValueError('jpeg_encode: qtables is a contiguous 16-bit [2, 64]')
+        return self.add(PROB_TO_ID, 128, [0, H, W, 0, ldrow, 0, 0, stream.numel(), min(scratch.numel(), (1 << 31) - 1)], [],
+                        [frame, None, ids, stream, status, scratch, colors if ids is not None else None, qtables])
+
     def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
         """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32
         [OW + OH, K + 2]), scratch = f32 [C, H, OW].  src_u8: src is u8 [H, W, C] with row stride `ldrow` bytes (ToTensor on the fly;

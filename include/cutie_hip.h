@@ -379,7 +379,48 @@ enum {
      *    boundary bit planes of both ids planes per object, one 64-bit word per 64 columns of a row.
      *    H * W < 2^31, so every count fits.  All sums are integers gathered with integer atomics: the counts depend on the planes, the
      *    object list and r alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch:
-     *    H, W < 1, H * W >= 2^31, n outside 1 .. 255, r outside 1 .. 40, a null or misaligned pointer, a scratch that is too small. */
+     *    H, W < 1, H * W >= 2^31, n outside 1 .. 255, r outside 1 .. 40, a null or misaligned pointer, a scratch that is too small.
+     * ABI 11 -- the --visualize overlays on the device (results_utils.py:173-192 of the reference: per frame the image is decoded again, the
+     *    object colours are blended over it in float and PIL writes <frame>.jpg; ResultSaver overlay='device', eval_vos --overlay device):
+     *  flags == 128, a stage ON ITS OWN (128 combined with any other flag stays the "unknown flags" error): the entropy-coded segment of
+     *    the baseline JPEG (4:2:0, standard Huffman tables, no restart markers) of a frame with the colours of an id plane blended over
+     *    it -- the bytes libjpeg-turbo's encoder (PIL's Image.save) writes for the blended frame (kernels in jpeg_enc.hip; the numpy model:
+     *    tests/jpeg_enc_ref.py; header and EOI: cutie_amd/inference/utils/jpeg_writer.py).  i0, i3, i5, i6 and p1 unused.
+     *    p0 = frame uint8 [i1, i2, 3] = [H, W, 3], pixels packed, row stride i4 BYTES (>= 3 W), any alignment.
+     *    p2 = id plane uint8 [H, W], row-major and contiguous, or 0: the frame is encoded as it is (p6 unused then).
+     *    p6 = colour table uint8 [256][4] (R, G, B, unused), 4-byte aligned: one colour per id; entry 0 is never read; an id that is
+     *    not an object gets the colour 0 and is still halved, as on the host.
+     *    p7 = quantisation tables uint16 [2][64] (luminance, chrominance), NATURAL (row-major) order, 2-byte aligned, values 1 .. 255.
+     *    p3 = stream uint8 (any alignment), i7 = its capacity in bytes: the segment, byte-stuffed and padded to a byte with 1-bits.
+     *    p4 = status int32 [4], 4-byte aligned, written by the launch: 0 stream bytes (saturating at 2^31 - 1), 1 zero, 2 error bits (1:
+     *    the stream does not fit the capacity; NOTHING is written to p3 then -- with i7 == 0 it may be null --, [0] still says what it
+     *    needs), 3 zero: the PNG stage's convention.
+     *    p5 = int32 scratch of i8 words, 16-byte aligned, i8 >= 16 + 36 B + (52 B + 16) + 4 ceil((52 B + 16) / 16) with B = 6 ceil(W / 16)
+     *    ceil(H / 16) coded blocks (cutie_amd/ops.py OpList.jpeg_enc_scratch_words): a header, per block 64 int16 coefficients, a 64-bit
+     *    bit offset and a bit count, the unstuffed stream at the worst case of 1660 bits per block (22 of DC, 63 x 26 of AC), and per
+     *    64-byte chunk of it the 0xFF count and its scan.  2 ceil(1660 B / 8) bytes hold any stream (OpList.jpeg_enc_capacity).
+     *    The rules (libjpeg-turbo's encoder path, each checked against PIL by tests/test_jpeg_encode_cpu.py through the model):
+     *    - blend: id == 0: the frame's pixel; else (frame + colour[id]) >> 1 per channel (= the host's float blend, truncated).
+     *    - colour (SCALEBITS 16): Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+     *      Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+     *    - geometry: Y has ceil(W / 8) x ceil(H / 8) blocks, Cb and Cr ceil(ceil(W / 2) / 8) x ceil(ceil(H / 2) / 8); ceil(W / 16) x
+     *      ceil(H / 16) MCUs, coded row by row, each Y00 Y01 Y10 Y11 Cb Cr.
+     *    - edges: Y replicates its last column and row out to whole blocks.  Chroma replicates the INPUT's last column as far as needed and
+     *      its last row once if H is odd, averages 2 x 2 as (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... along the output
+     *      columns, and then replicates the last DOWNSAMPLED row out to whole blocks.
+     *    - dummy blocks: a Y block of an MCU beyond the component's block grid (ceil(W / 8) or ceil(H / 8) odd) has all AC zero and the DC
+     *      of the block coded just before it: DC difference 0 + EOB, and the DC prediction passes over it.
+     *    - FDCT: jfdctint (ISLOW) on sample - 128: CONST_BITS 13, PASS1_BITS 2, rows then columns, DESCALE with rounding.  32-BIT
+     *      INTERMEDIATES SUFFICE: pass-1 outputs are <= 4096 in magnitude, so no pass-2 sum of products exceeds 1.13e9 (the bound is
+     *      worked out in jpeg_enc.hip; the model computes in 64 bits and asserts the 32-bit range on everything it encodes).
+     *    - quantisation: divisor d = q << 3, sign(c) * ((|c| + (d >> 1)) / d).
+     *    - coding: tables K.3 - K.6; DC = the difference to the component's previous block in coded order (0 at the start); AC with ZRL
+     *      for runs above 15 and EOB unless the last coefficient is nonzero; bits MSB first, every 0xFF byte followed by 0x00, the last
+     *      byte filled with 1-bits (and stuffed like any other).
+     *    Every offset comes from a scan in a fixed order and bits shared by two blocks are merged with an integer OR: the bytes depend on
+     *    the inputs alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch: H, W < 1,
+     *    H, W > 65535, H * W >= 2^31, a negative capacity, a null pointer (p0, p3 with i7 > 0, p4, p5, p7, p6 with p2), a misaligned
+     *    pointer (p4, p5, p6, p7), a frame row stride < 3 W, a scratch that is too small. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).

@@ -92,4 +92,6 @@ int launch_png_deflate(const cutie_op* op, int H, int W, hipStream_t s);   // pn
 int launch_rle_encode(const cutie_op* op, hipStream_t s);                  // rle.hip: PROB_TO_ID with flags == 32 (ABI 9)
 int launch_jf_counts(const cutie_op* op, hipStream_t s);                   // score.hip: PROB_TO_ID with flags == 64 (ABI 10)
 int launch_jpeg_encode(const cutie_op* op, hipStream_t s);                 // jpeg_enc.hip: PROB_TO_ID with flags == 128 (ABI 11)
+int launch_matte_composite(const cutie_op* op, hipStream_t s);             // matte.hip: PROB_TO_ID with flags == 256 (ABI 11, forms added)
+int launch_matte_soft(const cutie_op* op, hipStream_t s);                  // matte.hip: PROB_TO_ID with flags == 512 (ABI 11, forms added)
 void cutie_set_error(const char* fmt, ...);

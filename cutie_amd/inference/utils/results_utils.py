@@ -29,7 +29,15 @@ csrc/jpeg_enc.hip) blends the object colours over the uint8 frame and encodes th
 stream ride a pinned copy in front of the frame's event, and the writer thread wraps them (utils/jpeg_writer.py) into ``<frame>.jpg``:
 the bytes of the host overlay's file.  The frame comes as ``image_u8`` (device ingest keeps it: device_ingest.to_device(keep_u8=True));
 without it the saver decodes ``path_to_image`` with PIL and uploads it -- the slow pairing: the decode and a synchronous copy per frame on
-the stepping thread.  A frame whose stream does not fit the capacity is encoded by the host code, with one warning per saver."""
+the stepping thread.  A frame whose stream does not fit the capacity is encoded by the host code, with one warning per saver.
+
+``vis_modes`` / ``soft_masks`` / ``alpha_matte`` (the outputs of the reference's interactive tool, gui/interactive_utils.py:79-229 and
+gui/resource_manager.py:154-173): behind the id stage one launch per mode (PROB_TO_ID flags == 256, csrc/matte.hip)
+composes the frame from the probability planes, the uint8 frame and the id plane -- the reference's float arithmetic, its bytes -- and
+the JPEG stage above encodes the composed frame (no id plane); the soft masks (flags == 512) and the alpha matte are uint8 planes that
+go through the PNG stage and leave as greyscale PNGs.  Files: ``<output_root>/<video>/visualization/<mode>/<frame>.jpg``,
+``.../soft_masks/<object id>/<frame>.png``, ``.../alpha/<frame>.png``.  Status blocks and stream heads ride pinned copies in front of
+one event per frame; the writer thread wraps and writes.  The full-size float planes never leave the device."""
 import logging
 import os
 import shutil
@@ -75,6 +83,7 @@ EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame:
 RLE_TABLE = 16 + 255 * 16   # BURST: bytes of the status block and the table of up to 255 objects in front of the RLE strings
 OVERLAY_MODES = ('host', 'device')
 JPEG_SLAB = 256 * 1024      # overlay='device': bytes of the first device-to-host copy of a frame's JPEG: status + the head of the stream (a 480p overlay is 30-120 KB)
+VIS_MODES = ('davis', 'light', 'fade', 'popup', 'layer')     # gui/interactive_utils.py get_visualization_torch ('mask', 'image': trivial; 'rgba': alpha_matte)
 RLE_SLAB = 256 * 1024       # ... and of the whole device-to-host copy: status, table and the strings (a frame that needs more is encoded on the host)
 
 
@@ -106,6 +115,30 @@ class _EgressBuffers:
         self.event = torch.cuda.Event() if on_gpu else _NoEvent()      # (a CPU device: the interpreter of the tests, everything is synchronous)
 
 
+class _MatteBuffers:
+    """What one frame in flight owns of the vis_modes / soft_masks / alpha_matte outputs: per mode the composed frame and its
+    [status | JPEG segment], the quantised planes (K soft masks, then the matte) and per plane its [status | zlib stream]; one pinned
+    slab per stream and one event behind all copies."""
+
+    def __init__(self, H, W, K, modes, alpha, device):
+        from ... import ops as O
+        self.H, self.W, self.K, self.modes, self.alpha = H, W, K, tuple(modes), alpha
+        on_gpu = torch.device(device).type == 'cuda'
+        staging = (lambda n: torch.empty(n, dtype=torch.uint8).pin_memory()) if on_gpu else (lambda n: torch.empty(n, dtype=torch.uint8))
+        cap = O.OpList.jpeg_enc_capacity(H, W)
+        # (one tensor per mode: the composite's dword stores need a 16-byte aligned frame, and H * W * 3 is rarely a multiple of 16)
+        self.frames = [torch.empty((H, W, 3), dtype=torch.uint8, device=device) for _ in self.modes]
+        self.jpeg_dev = [torch.empty(16 + cap, dtype=torch.uint8, device=device) for _ in self.modes]
+        self.jpeg_host = [staging(min(16 + cap, JPEG_SLAB)) for _ in self.modes]
+        n = K + (1 if alpha else 0)
+        cap = O.OpList.png_capacity(H, W)
+        self.planes = torch.empty((K, H, W), dtype=torch.uint8, device=device)               # the soft masks
+        self.matte = torch.empty((H, W), dtype=torch.uint8, device=device) if alpha else None # (a tensor of its own: 16-byte aligned)
+        self.png_dev = [torch.empty(16 + cap, dtype=torch.uint8, device=device) for _ in range(n)]
+        self.png_host = [staging(min(16 + cap, EGRESS_SLAB)) for _ in range(n)]
+        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
+
+
 class _NoEvent:
     def record(self):
         pass
@@ -129,12 +162,16 @@ class _Job:
     overlay: Optional[_EgressBuffers] = None  # overlay='device': the JPEG's entropy-coded segment arrives in these (the same set as `egress` when both are on)
     frame: Optional[torch.Tensor] = None     # overlay='device': the uint8 frame the stage read (kept until the writer is done: see _queue_overlay)
     ids: Optional[torch.Tensor] = None       # overlay='device': the id plane on the device (a frame whose stream overflowed is blended on the host)
+    matte: Optional[_MatteBuffers] = None    # vis_modes / soft_masks / alpha_matte: the frame's composed outputs arrive in these
+    matte_objects: Tuple = ()                # ... the object id of every soft-mask plane, in plane order
+    matte_keep: Tuple = ()                   # ... what the launches read (planes, frame, tables), kept until the writer is done with the frame
 
 
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
-                 processor=None, egress='host', scorer=None, overlay='host'):
+                 processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
+                 target_objects=None, layer=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -149,7 +186,30 @@ class ResultSaver:
         path and of ``process_merged`` -- and ``end`` leaves ``scorer.finish()`` in ``self.scores``.  Long ids cannot be scored.
         ``overlay``: 'host' (default: the writer thread re-decodes the frame, blends in float and PIL encodes the JPEG) | 'device' (the
         GPU blends and writes the JPEG's entropy-coded segment, see the module docstring; needs ``processor``; the files are the same
-        bytes).  It only matters with ``visualize``; ``use_long_id`` savers keep the host overlay -- ``self.overlay`` says which one runs."""
+        bytes).  It only matters with ``visualize``; ``use_long_id`` savers keep the host overlay -- ``self.overlay`` says which one runs.
+        ``vis_modes`` (a subset of VIS_MODES), ``soft_masks``, ``alpha_matte`` (not in the reference's batch tools; its interactive
+        tool writes them, see the module docstring): composed on the GPU per frame; they need ``processor`` and, for the modes, the
+        frame (``image_u8`` or ``path_to_image`` of ``process``); a ``use_long_id`` saver refuses them.  ``target_objects``: the object
+        ids that 'popup', 'layer' and the matte keep (default: all objects of the frame; ids that are not -- yet, or any more -- objects
+        are left out).  ``layer``: the RGBA image of mode 'layer' (a PIL image, a uint8 [h, w, 4] array or a file name), resized once
+        to the output size with PIL and uploaded once."""
+        vis_modes = tuple(vis_modes)
+        unknown = [m for m in vis_modes if m not in VIS_MODES]
+        if unknown or len(set(vis_modes)) != len(vis_modes):
+            raise ValueError(f'vis_modes is a subset of {VIS_MODES}, not {vis_modes}')
+        self.vis_modes, self.soft_masks, self.alpha_matte = vis_modes, bool(soft_masks), bool(alpha_matte)
+        self._matte_on = bool(vis_modes or soft_masks or alpha_matte)
+        if self._matte_on and use_long_id:
+            raise ValueError('vis_modes / soft_masks / alpha_matte are composed from uint8 id planes and object planes on the device: '
+                             'a use_long_id saver (RGB masks) cannot write them')
+        if self._matte_on and processor is None:
+            raise ValueError('vis_modes / soft_masks / alpha_matte need the processor (its device)')
+        if 'layer' in vis_modes and layer is None:
+            raise ValueError("vis mode 'layer' needs layer (an RGBA image)")
+        self.target_objects = None if target_objects is None else [int(v) for v in target_objects]
+        self._layer_src, self._layer_dev = layer, None
+        self._matte_free: Queue = Queue()
+        self._matte_allocated, self._matte_png_scratch, self._matte_colors = 0, None, {}
         if scorer is not None and use_long_id:
             raise ValueError('scorer: J&F is counted on uint8 id planes; long ids (RGB masks) cannot be scored')
         self.scorer, self.scores = scorer, None
@@ -215,6 +275,8 @@ class ResultSaver:
         q = (prob * 255).to(torch.uint8).cpu() if self.save_scores else None       # == numpy astype(uint8) of prob*255
         all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
         ov = self._queue_overlay(None, mask, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        if self._matte_on:
+            ov.update(self._queue_matte(prob, tuple(prob.shape[1:]), mask, all_ids, path_to_image, image_u8))
         self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, all_ids,
                             prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, **ov))
@@ -245,22 +307,11 @@ class ResultSaver:
         from ... import ops as O
         dev = self.processor.network.device
         H, W = int(ids.shape[0]), int(ids.shape[1])
-        if image_u8 is None:
-            if path_to_image is None:
-                raise ValueError('Cannot visualize without path_to_image or image_u8')
-            image_u8 = torch.from_numpy(np.array(Image.open(path_to_image).convert('RGB')))
-        if image_u8.dtype != torch.uint8 or tuple(image_u8.shape) != (H, W, 3):
-            raise ValueError(f'image_u8 is uint8 [{H}, {W}, 3] (the output size), not {image_u8.dtype} {tuple(image_u8.shape)}')
-        if image_u8.device != dev or image_u8.stride(2) != 1 or image_u8.stride(1) != 3:
-            image_u8 = image_u8.to(dev).contiguous()
-        if self._jpeg_tables is None:
-            qt = jpeg_writer.quant_tables(jpeg_writer.QUALITY)
-            self._jpeg_tables = (qt, torch.from_numpy(qt.view(np.int16)).to(dev))
+        image_u8 = self._frame_u8(H, W, dev, path_to_image, image_u8)
+        self._jpeg_setup(H, W, dev)
         colors = self._jpeg_colors.get(tuple(all_ids))
         if colors is None:                       # (changes when objects come or go, not per frame)
             colors = self._jpeg_colors[tuple(all_ids)] = torch.from_numpy(jpeg_writer.color_table(self.colors, all_ids)).to(dev)
-        if self._jpeg_scratch is None or self._jpeg_scratch[0] != (H, W):
-            self._jpeg_scratch = ((H, W), torch.empty(O.OpList.jpeg_enc_scratch_words(H, W), dtype=torch.int32, device=dev))
         own = b is None
         if own:
             b = self._take(H, W, dev, png=False)
@@ -274,19 +325,161 @@ class ResultSaver:
 
     def _fetch_jpeg(self, b: _EgressBuffers):
         """Writer thread: the frame's entropy-coded segment once its copy has landed, or None when it did not fit the device stream."""
-        b.event.synchronize()
-        length, _, err, _ = (int(v) for v in b.jpeg_host[:16].view(torch.int32))
+        return self._fetch_segment(b.event, b.jpeg_host, b.jpeg_stream)
+
+    def _fetch_segment(self, event, host, stream):
+        event.synchronize()
+        length, _, err, _ = (int(v) for v in host[:16].view(torch.int32))
         if err != 0:
             if not self._jpeg_warned:
                 self._jpeg_warned = True
-                log.warning(f'device JPEG encoder: a frame of {self.video_name} needs {length} bytes, the stream holds {b.jpeg_stream.numel()}; '
+                log.warning(f'device JPEG encoder: a frame of {self.video_name} needs {length} bytes, the stream holds {stream.numel()}; '
                             f'such frames are encoded on the host')
             return None
-        have = b.jpeg_host.numel() - 16
-        head = b.jpeg_host[16:16 + min(length, have)].numpy().tobytes()
+        have = host.numel() - 16
+        head = host[16:16 + min(length, have)].numpy().tobytes()
         if length <= have:
             return head
-        return head + self._rest(b.jpeg_stream[have:length])
+        return head + self._rest(stream[have:length])
+
+    # ---- vis_modes / soft_masks / alpha_matte -------------------------------------------------------------------------------------
+    def _frame_u8(self, H, W, dev, path_to_image, image_u8):
+        """The frame as packed uint8 [H, W, 3] on the device (overlay='device' and the vis modes read it)."""
+        if image_u8 is None:
+            if path_to_image is None:
+                raise ValueError('Cannot visualize without path_to_image or image_u8')
+            image_u8 = torch.from_numpy(np.array(Image.open(path_to_image).convert('RGB')))
+        if image_u8.dtype != torch.uint8 or tuple(image_u8.shape) != (H, W, 3):
+            raise ValueError(f'image_u8 is uint8 [{H}, {W}, 3] (the output size), not {image_u8.dtype} {tuple(image_u8.shape)}')
+        if image_u8.device != dev or image_u8.stride(2) != 1 or image_u8.stride(1) != 3:
+            image_u8 = image_u8.to(dev).contiguous()
+        return image_u8
+
+    def _jpeg_setup(self, H, W, dev):
+        from ... import ops as O
+        if self._jpeg_tables is None:
+            qt = jpeg_writer.quant_tables(jpeg_writer.QUALITY)
+            self._jpeg_tables = (qt, torch.from_numpy(qt.view(np.int16)).to(dev))
+        if self._jpeg_scratch is None or self._jpeg_scratch[0] != (H, W):
+            self._jpeg_scratch = ((H, W), torch.empty(O.OpList.jpeg_enc_scratch_words(H, W), dtype=torch.int32, device=dev))
+
+    def _take_matte(self, H, W, K, dev) -> _MatteBuffers:
+        """As _take: a recycled set of the same geometry and plane count, a new one while few exist, else the next one given back."""
+        while True:
+            try:
+                b = self._matte_free.get_nowait()
+            except Empty:
+                if self._matte_allocated < self.queue.maxsize + 2:
+                    self._matte_allocated += 1
+                    return _MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev)
+                b = self._matte_free.get()
+            if (b.H, b.W, b.K) == (H, W, K):
+                return b
+            self._matte_allocated -= 1               # another geometry or object count: dropped
+
+    def _layer(self, H, W, dev):
+        """The RGBA layer at the output size on the device: resized with PIL and uploaded once per geometry."""
+        if self._layer_dev is None or self._layer_dev[0] != (H, W):
+            src = self._layer_src
+            if isinstance(src, (str, os.PathLike)):
+                src = Image.open(src)
+            if not isinstance(src, Image.Image):
+                src = Image.fromarray(np.asarray(src, dtype=np.uint8))
+            rgba = np.ascontiguousarray(np.array(src.convert('RGBA').resize((W, H))))
+            self._layer_dev = ((H, W), torch.from_numpy(rgba).to(dev))
+        return self._layer_dev[1]
+
+    def _queue_matte(self, prob, out_hw, ids, all_ids, path_to_image, image_u8) -> dict:
+        """Queue the composite launches of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), each followed by the JPEG stage on the composed frame, the soft-mask launch and the PNG stage per plane, the pinned
+        copies of every status block and stream head, and one event.  ``prob``: f32 [P, h, w] as ``step`` returned it, sampled at
+        ``out_hw`` inside the launches.  -> the _Job fields.  Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(out_hw[0]), int(out_hw[1])
+        P = int(prob.shape[0])
+        if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
+            prob = prob.to(device=dev, dtype=torch.float32).contiguous()
+        tmp_to_obj = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items() if int(t) < P}
+        K = P - 1 if self.soft_masks else 0
+        b = self._take_matte(H, W, K, dev)
+        wanted = all_ids if self.target_objects is None else self.target_objects
+        obj_to_tmp = {o: t for t, o in tmp_to_obj.items()}
+        targets = [obj_to_tmp[o] for o in wanted if o in obj_to_tmp]
+        ol = O.OpList()
+        if self.vis_modes:
+            frame = self._frame_u8(H, W, dev, path_to_image, image_u8)
+            self._jpeg_setup(H, W, dev)
+            colors = None
+            if any(m in ('davis', 'light', 'fade') for m in self.vis_modes):
+                colors = self._matte_colors.get(tuple(all_ids))
+                if colors is None:                   # the reference's colour map: the palette scaled by 1.5 (gui/interactive_utils.py:42-44)
+                    pal = np.array(self.palette, dtype=np.uint8).reshape(-1, 3) if self.palette is not None else davis_palette_np
+                    pal = (pal.astype(np.float32) * 1.5).clip(0, 255).astype(np.uint8)
+                    colors = self._matte_colors[tuple(all_ids)] = torch.from_numpy(jpeg_writer.color_table(pal, all_ids)).to(dev)
+            for k, mode in enumerate(self.vis_modes):
+                soft = mode in ('popup', 'layer')
+                with_matte = self.alpha_matte and soft and not any(m in ('popup', 'layer') for m in self.vis_modes[:k])
+                ol.matte_composite(mode, b.frames[k], out_hw=(H, W), frame=frame, planes=prob if soft else None, targets=targets,
+                                   ids=None if soft else ids, colors=None if soft else colors,
+                                   layer=self._layer(H, W, dev) if mode == 'layer' else None, matte=b.matte if with_matte else None)
+                ol.jpeg_encode(b.frames[k], None, None, self._jpeg_tables[1], b.jpeg_dev[k][16:], b.jpeg_dev[k][:16].view(torch.int32),
+                               self._jpeg_scratch[1], H=H, W=W)
+        if self.alpha_matte and not any(m in ('popup', 'layer') for m in self.vis_modes):
+            ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=targets, matte=b.matte)
+        if K > 0:
+            ol.matte_soft(prob, b.planes[:K], out_hw=(H, W))
+        if self._matte_png_scratch is None or self._matte_png_scratch[0] != (H, W):
+            self._matte_png_scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+        for k in range(len(b.png_dev)):
+            ol.png_deflate(b.planes[k] if k < K else b.matte, b.png_dev[k][16:], b.png_dev[k][:16].view(torch.int32), self._matte_png_scratch[1], H=H, W=W)
+        ol.run()
+        for d, h in zip(b.jpeg_dev + b.png_dev, b.jpeg_host + b.png_host):
+            h.copy_(d[:h.numel()], non_blocking=True)
+        b.event.record()
+        return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep))
+
+    def _write_matte(self, job):
+        """Writer thread: the files of one frame's vis modes, soft masks and matte."""
+        b, base, stem = job.matte, path.join(self.output_root, self.video_name), job.frame_name[:-4]
+
+        def put(folder, name, data):
+            os.makedirs(path.join(base, folder), exist_ok=True)
+            with open(path.join(base, folder, name), 'wb') as f:
+                f.write(data)
+        for k, mode in enumerate(b.modes):
+            segment = self._fetch_segment(b.event, b.jpeg_host[k], b.jpeg_dev[k][16:])
+            if segment is not None:
+                put(path.join('visualization', mode), stem + '.jpg', jpeg_writer.wrap(segment, b.H, b.W, self._jpeg_tables[0]))
+            else:                                    # the segment did not fit the device stream: the composed frame through PIL
+                os.makedirs(path.join(base, 'visualization', mode), exist_ok=True)
+                Image.fromarray(self._to_host(b.frames[k])).save(path.join(base, 'visualization', mode, stem + '.jpg'))
+        for k in range(len(b.png_dev)):
+            b.event.synchronize()
+            host = b.png_host[k]
+            length, _, err, _ = (int(v) for v in host[:16].view(torch.int32))
+            if err != 0:
+                raise RuntimeError(f'device PNG encoder: error bits {err} (stream of {length} bytes, capacity {b.png_dev[k].numel() - 16})')
+            have = host.numel() - 16
+            stream = host[16:16 + min(length, have)].numpy().tobytes()
+            if length > have:
+                stream += self._rest(b.png_dev[k][16 + have:16 + length])
+            data = png_container.assemble(stream, b.H, b.W, None)
+            if k < b.K:
+                if job.matte_objects[k] is not None:
+                    put(path.join('soft_masks', str(job.matte_objects[k])), stem + '.png', data)
+            else:
+                put('alpha', stem + '.png', data)
+
+    def _to_host(self, t: torch.Tensor) -> np.ndarray:
+        """Writer thread: a device tensor as a numpy array, copied on a stream of the writer's own."""
+        if t.device.type != 'cuda':
+            return t.numpy()
+        if self._wstream is None:
+            self._wstream = torch.cuda.Stream(device=t.device)
+        with torch.cuda.stream(self._wstream):
+            out = t.to('cpu', non_blocking=False)
+        return out.numpy()
 
     def _rest(self, tail: torch.Tensor) -> bytes:
         """Writer thread: the part of a long stream behind the first slab, on a stream of the writer's own."""
@@ -337,6 +530,8 @@ class ResultSaver:
         if self.scorer is not None:              # (b.ids is not handed out again before the writer is done with the frame: same stream)
             self.scorer.add(frame_name, b.ids)
         ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        if self._matte_on:
+            ov.update(self._queue_matte(prob, (H, W), b.ids, all_ids, path_to_image, image_u8))
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         if rle:
             b.rle_host.copy_(b.rle_dev, non_blocking=True)
@@ -345,7 +540,7 @@ class ResultSaver:
         if self.save_scores:                     # as the host path: the scores of the output size
             full = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
             q = (full * 255).to(torch.uint8).cpu()
-        self.queue.put(_Job(self, None, frame_name, path_to_image if ov else None, all_ids, prob=q, last_frame=last_frame,
+        self.queue.put(_Job(self, None, frame_name, path_to_image if 'overlay' in ov else None, all_ids, prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b, rle=rle, **ov))
 
     # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
@@ -363,6 +558,8 @@ class ResultSaver:
             raise ValueError('process_merged: BURST has no multi-scale protocol (no json is written from merged scales)')
         if self.save_scores:
             raise ValueError('process_merged writes no scores: save_scores and the merge exclude each other')
+        if self._matte_on:
+            raise ValueError('process_merged has no probability planes of its own: vis_modes / soft_masks / alpha_matte need process')
         if self.processor is None:
             raise ValueError('process_merged needs the processor (its device; the merge has no host implementation)')
         own = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items()}
@@ -450,6 +647,7 @@ class ResultSaver:
         self.queue.join()
         self.thread.join()
         self._free, self._allocated, self._scratch = Queue(), 0, None
+        self._matte_free, self._matte_allocated, self._matte_png_scratch = Queue(), 0, None
         if self.scorer is not None:
             self.scores = self.scorer.finish()
 
@@ -518,6 +716,8 @@ def _writer(queue: Queue):
                     np.savez(path.join(sc_dir, 'backward.npz'), obj_ids=np.array([o for _, o in ids], dtype=np.int64),
                              tmp_ids=np.array([t for t, _ in ids], dtype=np.int64))
                 np.savez_compressed(path.join(sc_dir, job.frame_name[:-4] + '.npz'), prob=job.prob.numpy())
+            if job.matte is not None:
+                s._write_matte(job)
             segment = s._fetch_jpeg(job.overlay) if job.overlay is not None else None
             if segment is not None:                                # overlay='device': wrap the finished segment, no PIL
                 vis_dir = path.join(s.visualize_output_root, s.video_name)
@@ -548,6 +748,8 @@ def _writer(queue: Queue):
             b = job.egress if job.egress is not None else job.overlay
             if b is not None:                                  # the frame's buffers go back to the pool
                 job.saver._free.put(b)
+            if job.matte is not None:
+                job.saver._matte_free.put(job.matte)
         queue.task_done()
 
 

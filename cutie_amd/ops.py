@@ -1016,6 +1016,84 @@ class OpList:
         return self.add(PROB_TO_ID, 128, [0, H, W, 0, ldrow, 0, 0, stream.numel(), min(scratch.numel(), (1 << 31) - 1)], [],
                         [frame, None, ids, stream, status, scratch, colors if ids is not None else None, qtables])
 
+    MATTE_MODES = {'davis': 0, 'light': 1, 'fade': 2, 'popup': 3, 'layer': 4, 'alpha': 5}    # i8 of PROB_TO_ID flags == 256 (csrc/matte.hip)
+    MATTE_MAX_TARGETS = 255
+
+    @staticmethod
+    def _matte_planes(who, planes):
+        if planes.dim() != 3 or planes.dtype != torch.float32 or planes.stride(2) != 1 or min(planes.shape) < 1:
+            raise ValueError(f'{who}: planes are f32 [P, h, w] with a contiguous last dimension, not {planes.dtype} {tuple(planes.shape)} strides {planes.stride()}')
+        if max(planes.stride(0), planes.stride(1)) >= 1 << 31:
+            raise ValueError(f'{who}: strides are 32-bit')
+        return [int(planes.shape[0]), int(planes.shape[1]), int(planes.shape[2]), int(planes.stride(0)), int(planes.stride(1))]
+
+    def matte_composite(self, mode, out, *, out_hw, frame=None, planes=None, targets=(), ids=None, colors=None, layer=None, matte=None, ldrow=None):
+        """PROB_TO_ID flags == 256 (ABI 11, forms added, include/cutie_hip.h): one visualisation mode of the reference's interactive tool
+        (gui/interactive_utils.py:152-229) -> ``out`` uint8 [OH, OW, 3] packed and contiguous, 16-byte aligned, composed in float32 in the
+        reference's operation order and quantised as ``(x * 255).byte()``: the reference's bytes.  ``frame`` uint8 [OH, OW, 3] (row stride
+        ``ldrow`` bytes, default the tensor's; pixels packed, any alignment).
+        Hard modes 'davis' | 'light' | 'fade': ``ids`` uint8 [OH, OW] contiguous and ``colors`` uint8 [256, 4] (R, G, B, unused) -- the
+        colour of every id is blended over the frame (alpha 0.5, 0.9, 0.5), 'fade' darkens the background to 0.6.
+        Soft modes 'popup' | 'layer': ``planes`` f32 [P, h, w] (any plane / row strides: the view ``step`` returns is read in place;
+        resampled bilinearly to (OH, OW) inside the launch exactly as prob_to_id(out_hw=...) samples them) and ``targets``, the plane
+        indices whose sum -- in list order -- is the matte m: 'popup' keeps the targets in colour over a grey background, 'layer' puts
+        ``layer`` (uint8 [OH, OW, 4] RGBA contiguous, 16-byte aligned) between the background and the targets.  ``matte`` (optional,
+        soft modes): uint8 [OH, OW] contiguous, 16-byte aligned = clamp(m, 0, 1) quantised -- the fourth channel of the reference's
+        'rgba' mode; mode 'alpha' writes the matte alone (``out``, ``frame`` unused, may be None).
+        The target list is read by the launcher when the list runs (it checks every index); it is kept alive here."""
+        code = self.MATTE_MODES.get(mode)
+        if code is None:
+            raise ValueError(f'matte_composite: mode is one of {tuple(self.MATTE_MODES)}, not {mode!r}')
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        soft = code >= 3
+        ints = [0] * 10
+        ints[5], ints[6], ints[8] = OH, OW, code
+        tg = None
+        if soft:
+            if planes is None:
+                raise ValueError(f'matte_composite: mode {mode!r} needs planes')
+            ints[:5] = self._matte_planes('matte_composite', planes)
+            tg = np.array([int(q) for q in targets], dtype=np.int32)
+            if len(tg) > self.MATTE_MAX_TARGETS or (len(tg) and (tg.min() < 0 or tg.max() >= ints[0])):
+                raise ValueError(f'matte_composite: at most {self.MATTE_MAX_TARGETS} targets, each a plane index 0 .. {ints[0] - 1}, not {tg.tolist()}')
+            ints[9] = len(tg)
+            self.keep.append(tg)
+            if matte is not None and (matte.dtype != torch.uint8 or tuple(matte.shape) != (OH, OW) or not matte.is_contiguous()):
+                raise ValueError(f'matte_composite: matte is a contiguous uint8 [{OH}, {OW}]')
+            if code == 5 and matte is None:
+                raise ValueError("matte_composite: mode 'alpha' needs matte")
+        elif matte is not None:
+            raise ValueError(f'matte_composite: mode {mode!r} has no matte (popup, layer, alpha)')
+        if code != 5:
+            if frame is None or frame.dtype != torch.uint8 or tuple(frame.shape) != (OH, OW, 3) or frame.stride(2) != 1 or frame.stride(1) != 3:
+                raise ValueError(f'matte_composite: frame is uint8 [{OH}, {OW}, 3] with packed pixels')
+            if out is None or out.dtype != torch.uint8 or tuple(out.shape) != (OH, OW, 3) or not out.is_contiguous():
+                raise ValueError(f'matte_composite: out is a contiguous uint8 [{OH}, {OW}, 3]')
+            ints[7] = int(frame.stride(0) if ldrow is None else ldrow)
+            if not soft:
+                if ids is None or ids.dtype != torch.uint8 or tuple(ids.shape) != (OH, OW) or not ids.is_contiguous():
+                    raise ValueError(f'matte_composite: mode {mode!r} needs ids, a contiguous uint8 [{OH}, {OW}]')
+                if colors is None or colors.dtype != torch.uint8 or colors.numel() != 1024 or not colors.is_contiguous():
+                    raise ValueError('matte_composite: colors is a contiguous uint8 [256, 4]')
+            if code == 4 and (layer is None or layer.dtype != torch.uint8 or tuple(layer.shape) != (OH, OW, 4) or not layer.is_contiguous()):
+                raise ValueError(f'matte_composite: mode layer needs layer, a contiguous uint8 [{OH}, {OW}, 4]')
+        else:
+            frame = out = None
+        return self.add(PROB_TO_ID, 256, ints, [],
+                        [planes if soft else None, int(tg.ctypes.data) if (tg is not None and len(tg)) else None, frame, out, matte,
+                         None if soft else ids, None if soft else colors, layer if code == 4 else None])
+
+    def matte_soft(self, planes, out, *, out_hw):
+        """PROB_TO_ID flags == 512 (ABI 11, forms added, include/cutie_hip.h): the soft masks of the reference's interactive tool
+        (gui/resource_manager.py:166-173) -- ``planes`` f32 [P, h, w] (strides as in matte_composite), every object plane q >= 1 sampled at
+        (OH, OW) as prob_to_id(out_hw=...) samples it and quantised as ``(p * 255).astype(uint8)`` -> ``out`` uint8 [P - 1, OH, OW]
+        contiguous, 16-byte aligned.  P == 1 writes nothing."""
+        OH, OW = int(out_hw[0]), int(out_hw[1])
+        ints = self._matte_planes('matte_soft', planes) + [OH, OW]
+        if out.dtype != torch.uint8 or tuple(out.shape) != (ints[0] - 1, OH, OW) or not out.is_contiguous():
+            raise ValueError(f'matte_soft: out is a contiguous uint8 [{ints[0] - 1}, {OH}, {OW}]')
+        return self.add(PROB_TO_ID, 512, ints, [], [planes, None, out])
+
     def resize(self, src, dst, *, C, H, W, OH, OW, plane, ldrow, nearest=False, antialias=False, src_u8=False, taps=None, scratch=None):
         """RESIZE.  antialias: F.interpolate(bilinear, antialias=True) -- taps = resize_aa_table(H, W, OH, OW) on the device (int32
         [OW + OH, K + 2]), scratch = f32 [C, H, OW].  src_u8: src is u8 [H, W, C] with row stride `ldrow` bytes (ToTensor on the fly;

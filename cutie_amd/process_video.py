@@ -16,8 +16,16 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
 
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
+        [--vis MODE [MODE ...]] [--soft-masks] [--alpha] [--target-objects ID [ID ...]] [--layer FILE]
         [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
                             has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
+
+``--vis`` (davis | light | fade | popup | layer), ``--soft-masks``, ``--alpha``: the visualisations, per-object soft masks and the alpha
+matte of the reference's interactive tool (gui/interactive_utils.py:79-229, gui/resource_manager.py:154-173), composed and encoded on
+the GPU (ResultSaver vis_modes / soft_masks / alpha_matte) into OUT/visualization/<mode>/*.jpg, OUT/soft_masks/<object id>/*.png and
+OUT/alpha/*.png.  ``--target-objects``: the objects that popup, layer and the matte keep (default all); ``--layer``: the RGBA image of
+mode layer.  The uint8 frame the modes read is the one device ingest uploaded or decoded; with ``--ingest host`` it is made from the
+float frame on the device, once per frame.
 
 ``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
 cutie_amd/inference/data/device_ingest.py).  ``--ingest device-decode``: JPEG frames of a directory are parsed on the host and
@@ -40,7 +48,7 @@ from .inference.data.device_ingest import frame_to_device, jpeg_to_device
 from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
-from .inference.utils.results_utils import EGRESS_MODES, ResultSaver
+from .inference.utils.results_utils import EGRESS_MODES, VIS_MODES, ResultSaver
 
 IMAGE_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
 
@@ -142,25 +150,40 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
-                  gt_dir: Optional[str] = None) -> Dict:
+                  gt_dir: Optional[str] = None, vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
+                  layer=None) -> Dict:
     """gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
-    joins the result."""
+    joins the result.  vis_modes / soft_masks / alpha_matte / target_objects / layer: ResultSaver's (the module docstring); 'folders' of
+    the result names the folders they wrote."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
+    vis_modes = tuple(vis_modes)
+    want_u8 = bool(vis_modes)                                   # the modes read the uint8 frame; soft masks and the matte do not
     src = FrameSource(video, u8=(ingest == 'device'), packets=(ingest == 'device-decode'))
 
     def upload(f):
-        """-> (frame on the device, its deferred decode check or None)"""
+        """-> (frame on the device, its deferred decode check or None[, the uint8 frame on the device: with want_u8])"""
         if isinstance(f, jpeg.Packet):
-            return jpeg_to_device(f, dev, check=False)              # (a bad frame raises, naming its file, when it is checked)
-        return (f.to(dev) if ingest == 'host' else frame_to_device(f, dev)), None
+            return jpeg_to_device(f, dev, check=False, keep_u8=want_u8)      # (a bad frame raises, naming its file, when it is checked)
+        if ingest == 'host' or not want_u8:
+            return (f.to(dev) if ingest == 'host' else frame_to_device(f, dev)), None
+        frame, u8 = frame_to_device(f, dev, keep_u8=True)
+        return frame, None, u8
 
-    def checked(pair):
-        frame, chk = pair
+    def checked(item):
+        """-> (frame, its uint8 twin on the device or None)"""
+        frame, chk = item[0], item[1]
         if chk is not None:
             chk()
-        return frame
+        return frame, (item[2] if len(item) > 2 else None)
+
+    def frame_u8(frame, u8):
+        """The uint8 [H, W, 3] frame on the device: the one ingest kept, or -- host ingest -- the float frame quantised on the device
+        (v * 255 + 0.5 truncated: the byte that ToTensor divided by 255)."""
+        if u8 is None:
+            u8 = (frame * 255 + 0.5).clamp_(0, 255).to(torch.uint8).permute(1, 2, 0).contiguous()
+        return u8
     mask_names = sorted(n for n in os.listdir(mask_dir) if n.lower().endswith('.png'))
     if not mask_names:
         raise RuntimeError('No mask frames found!')
@@ -190,7 +213,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             frame = src.read(int(name[:-4]))
             if frame is None:
                 break
-            processor.step(checked(upload(frame)), one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
+            processor.step(checked(upload(frame))[0], one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
                            force_permanent=True)
         # 2. the whole video
         scorer = None
@@ -198,19 +221,21 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             from .inference.utils.davis_metrics import SequenceScorer
             scorer = SequenceScorer(gt_dir, '', dev, skip_first_last=False)
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
-                            palette=palette, processor=processor, egress=egress, scorer=scorer)
+                            palette=palette, processor=processor, egress=egress, scorer=scorer, vis_modes=vis_modes, soft_masks=soft_masks,
+                            alpha_matte=alpha_matte, target_objects=target_objects, layer=layer)
         total, n, cleanups = 0.0, 0, 0
         try:
             ahead = Window(src, upload, checked, 1)           # the next frame is on the device while this one is stepped
             while ahead.queued:
-                frame = ahead.pop()
+                frame, u8 = ahead.pop()
                 name = f'{n:07d}.png'
                 mask = one_hot_planes(index_mask(name), num_objects, dev) if path.exists(path.join(mask_dir, name)) else None
                 hint = ahead.queued[0][0] if (lookahead and ahead.queued) else None
                 prob, secs = timed_step(lambda: processor.step(frame, mask, idx_mask=False, next_image=hint) if mask is not None
                                         else processor.step(frame, next_image=hint), dev.type == 'cuda')
                 total += secs
-                saver.process(prob, name, resize_needed=False, shape=None, last_frame=(n == len(src) - 1), path_to_image=None)
+                saver.process(prob, name, resize_needed=False, shape=None, last_frame=(n == len(src) - 1), path_to_image=None,
+                              image_u8=frame_u8(frame, u8) if want_u8 else None)
                 cleanups += check_to_clear_non_permanent_memory(processor, mem_cleanup_ratio, mem_get_info)
                 n += 1
         finally:
@@ -219,6 +244,9 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     out = {'frames': n, 'seconds': total, 'cleanups': cleanups, 'num_objects': num_objects, 'processor': processor}
     if scorer is not None:
         out['scores'] = saver.scores
+    if vis_modes or soft_masks or alpha_matte:
+        out['folders'] = ([path.join(output_dir, 'visualization', m) for m in vis_modes] + ([path.join(output_dir, 'soft_masks')] if soft_masks else []) +
+                          ([path.join(output_dir, 'alpha')] if alpha_matte else []))
     return out
 
 
@@ -235,12 +263,21 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU; device-decode: decode JPEG frames on the GPU too')
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES), help='device: the GPU writes the PNG streams of the masks (ResultSaver(egress=...))')
+    ap.add_argument('--vis', nargs='+', default=[], choices=list(VIS_MODES), metavar='MODE',
+                    help=f'visualisations written as OUT/visualization/MODE/*.jpg, composed and encoded on the GPU: {", ".join(VIS_MODES)}')
+    ap.add_argument('--soft-masks', action='store_true', help='one 8-bit grey PNG per object and frame: OUT/soft_masks/<object id>/*.png')
+    ap.add_argument('--alpha', action='store_true', help='the alpha matte of the target objects: OUT/alpha/*.png')
+    ap.add_argument('--target-objects', nargs='+', type=int, metavar='ID', help='the objects popup, layer and the matte keep (default: all)')
+    ap.add_argument('--layer', metavar='FILE', help='the RGBA image of --vis layer (resized to the frames)')
     ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
     return ap
 
 
 def main():
-    args = arg_parser().parse_args()
+    ap = arg_parser()
+    args = ap.parse_args()
+    if 'layer' in args.vis and not args.layer:
+        ap.error('--vis layer needs --layer FILE')
     from .model.cutie import CUTIE
     cfg = video_config(model=args.model, mem_every=args.mem_every, max_internal_size=args.max_internal_size)
     net = CUTIE(cfg).cuda().eval()
@@ -249,7 +286,8 @@ def main():
     else:
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
-                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt)
+                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt,
+                      vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

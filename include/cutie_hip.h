@@ -420,7 +420,41 @@ enum {
      *    Every offset comes from a scan in a fixed order and bits shared by two blocks are merged with an integer OR: the bytes depend on
      *    the inputs alone, not on launch shape or timing.  The launcher refuses, each with its own message and before any launch: H, W < 1,
      *    H, W > 65535, H * W >= 2^31, a negative capacity, a null pointer (p0, p3 with i7 > 0, p4, p5, p7, p6 with p2), a misaligned
-     *    pointer (p4, p5, p6, p7), a frame row stride < 3 W, a scratch that is too small. */
+     *    pointer (p4, p5, p6, p7), a frame row stride < 3 W, a scratch that is too small.
+     * ABI 11, forms added (the version number stays 11: both flag values were the "unknown flags" error before, so a library without them
+     *    refuses such a descriptor by message instead of misreading it, and no existing descriptor changes meaning) -- the visualisation modes, the alpha matte and the soft masks of the reference's interactive tool on the device
+     *    (gui/interactive_utils.py:79-229 get_visualization_torch, gui/resource_manager.py:154-173; ResultSaver vis_modes / soft_masks /
+     *    alpha_matte, process_video --vis / --soft-masks / --alpha; kernels in matte.hip; the numpy model: tests/matte_ref.py; the
+     *    reference's bytes: tests/golden/matte/).  Two stages, each ON ITS OWN (256 or 512 combined with any other flag stays the
+     *    "unknown flags" error).  The arithmetic of both: float32, every multiply and add rounded on its own (no contraction).
+     *    im[c] = (float)frame[c] / 255.0f, correctly rounded (RESIZE flags&4).  p_q = plane q at the output pixel: the plane itself when
+     *    (H, W) == (OH, OW), else exactly the flags&4 (= RESIZE flags == 0) sample -- the same source index, lambdas and order of operations.
+     *    m = the sum of p_q over the target planes, added in list order starting from the first; 0 for an empty list.
+     *    Every output byte is (uint8)(x * 255.0f) with the product clamped to [0, 255] (NaN: 0) -- truncation, torch's .byte().
+     *  flags == 256, composite: ONE mode of one frame.
+     *    i0 = P, i1 = H, i2 = W, i3 = plane stride, i4 = row stride (elements) of p0 = planes f32, 4-byte aligned (the un-padded view
+     *    that `step` returns is read in place); soft modes only -- the hard modes ignore them.  i5 = OH, i6 = OW: the output size.
+     *    i8 = mode: 0 davis, 1 light, 2 fade (hard modes), 3 popup, 4 layer (soft modes), 5 alpha (the matte plane alone).
+     *    p2 = frame uint8 [OH, OW, 3], pixels packed, row stride i7 BYTES (>= 3 OW), any alignment (modes 0 .. 4).
+     *    p3 = out uint8 [OH, OW, 3], packed and contiguous, 16-byte aligned (modes 0 .. 4).
+     *    p1 = target list int32 [i9] in HOST memory, 4-byte aligned, i9 <= 255 plane indices 0 .. P - 1 (soft modes): the launcher reads
+     *    and checks it during the call and hands the kernel a copy, so it may change or go away afterwards.
+     *    p4 = matte uint8 [OH, OW], contiguous, 16-byte aligned: clamp(m, 0, 1) quantised -- the fourth channel of the reference's
+     *    'rgba' mode.  Optional with popup and layer (the launch then writes both), required with alpha, an error with a hard mode.
+     *    Hard modes: p5 = id plane uint8 [OH, OW], contiguous, 4-byte aligned; p6 = colour table uint8 [256][4] (R, G, B, unused), 4-byte
+     *    aligned.  col = table[id] / 255.0f;  id != 0: x = im * a + b * col with a = (float)alpha, b = (float)(1.0 - alpha) (the
+     *    subtraction in double), alpha = 0.5 (davis, fade) | 0.9 (light);  id == 0: x = im, for fade x = im * 0.6f.  An id that is not
+     *    an object blends whatever the table holds for it.
+     *    popup: g = (im[0] * 0.3f + im[1] * 0.59f) + im[2] * 0.11f;  x = m * im + (1.0f - m) * g.
+     *    layer: p7 = layer uint8 [OH, OW, 4] RGBA, contiguous, 16-byte aligned; la = L[3] / 255.0f, lr = L[0..2] / 255.0f;
+     *    x = clamp((im * ((1 - m) * (1 - la)) + (lr * (1 - m)) * la) + im * m, 0, 1).
+     *  flags == 512, soft masks: p0, i0 .. i6 as above; p2 = out uint8 [P - 1, OH, OW], contiguous, 16-byte aligned: plane q - 1 =
+     *    (uint8)(p_q * 255.0f) for q = 1 .. P - 1 -- the truncation of the merge (flags&16).  P == 1 writes nothing (p2 may be null).
+     *  Both are streaming passes without atomics or order-dependent sums: the bytes depend on the inputs alone, not on the launch shape.
+     *  The launcher refuses, each with its own message and before any launch: OH, OW < 1 (and H, W < 1 where planes are read),
+     *    H * W, 3 * OH * OW or P * OH * OW >= 2^31, P outside 1 .. 256, more than 255 targets or one outside 0 .. P - 1, an unknown
+     *    mode, a null or misaligned pointer, a row stride below the row (planes: W elements, frame: 3 OW bytes), the id plane and
+     *    colour table missing for a hard mode, the layer for mode layer, the matte plane for mode alpha -- or given with a hard mode. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).

@@ -62,6 +62,12 @@ def has_diag_kernels():
     return bool(load().cutie_hip_build_flags() & 1)
 
 
+def has_png_decode():
+    """Does the loaded library know RESIZE flags 64 / 128, the PNG decode stages?  They were added without a new ABI number; a library from
+    before would run such a descriptor as a plain RESIZE, so the callers ask first (inference/data/device_ingest.py png_to_device)."""
+    return bool(load().cutie_hip_build_flags() & 2)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

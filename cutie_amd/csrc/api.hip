@@ -131,10 +131,11 @@ const char* cutie_hip_last_error(void) { return g_err; }
 int cutie_hip_abi_version(void) { return 11; }
 int cutie_op_struct_size(void) { return (int)sizeof(cutie_op); }
 int cutie_hip_build_flags(void) {
+    const int forms = 2;             // bit 1: RESIZE flags 64 / 128, the PNG decode stages (ABI 11, forms added)
 #ifdef CUTIE_DIAG
-    return 1;
+    return forms | 1;
 #else
-    return 0;
+    return forms;
 #endif
 }
 

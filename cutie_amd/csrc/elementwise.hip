@@ -1555,6 +1555,7 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
                                op->f[0], op->f[1]);
             break;
         case CUTIE_OP_RESIZE: {
+            if (op->flags & 192) return launch_png_decode(op, s);           // PNG decode stages: png_dec.hip
             if (op->flags & 56) return launch_jpeg(op, s);                  // JPEG decode stages: jpeg.hip
             if (op->flags & 6) return launch_resize_ingest(op, s);          // antialias / u8 source: ingest.hip
             const long n = (long)i[0] * i[3] * i[4];

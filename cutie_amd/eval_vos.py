@@ -13,7 +13,7 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
         [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
                                             no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
-        [--score [--gt DIR] [--score-all-frames]]      (DAVIS J&F of the run against the palette PNGs of DIR/<video>/ -- default: --masks --,
+        [--score [--gt DIR] [--score-all-frames] [--gt-decode host|device]]      (DAVIS J&F of the run against the palette PNGs of DIR/<video>/ -- default: --masks --,
                                             counted on the GPU from the id planes while the videos run (inference/utils/davis_metrics.py); writes
                                             global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output;
                                             the first and last ground-truth frame of a video are left out unless --score-all-frames)
@@ -94,13 +94,13 @@ def _take(window, dev, lookahead):
 
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
-           score_output_root=None, score_gt=None, score_all_frames=False, overlay='host') -> ResultSaver:
+           score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> ResultSaver:
     """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer."""
     scorer = None
     if score_gt is not None:
         if vid_reader.use_long_id:
             raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) cannot be scored')
-        scorer = SequenceScorer(score_gt, vid_reader.vid_name, core.network.device, skip_first_last=not score_all_frames)
+        scorer = SequenceScorer(score_gt, vid_reader.vid_name, core.network.device, skip_first_last=not score_all_frames, gt_decode=gt_decode)
     return ResultSaver(mask_output_root, vid_reader.vid_name, dataset=dataset, object_manager=core.object_manager,
                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
@@ -163,7 +163,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict:
+                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -173,7 +173,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     from .inference import inference_core as IC
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames,
+                   egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode,
                    overlay=overlay)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
@@ -188,7 +188,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict:
+                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -213,7 +213,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
         raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, overlay=overlay)
+                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -244,7 +244,7 @@ def lockstep_key(vid_reader):
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host') -> Dict[int, Dict]:
+                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
@@ -256,7 +256,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     dev = network.device
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
-                     score_all_frames=score_all_frames, overlay=overlay) for c, rd in enumerate(vid_readers)]
+                     score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -327,6 +327,9 @@ def arg_parser() -> argparse.ArgumentParser:
                          'global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output.  Not for BURST or long-id (RGB) masks: '
                          'the first mask under --masks / --gt is peeked at for an early error, every video is checked when it starts')
     ap.add_argument('--gt', help='--score: the root of the ground-truth palette PNGs, DIR/<video>/<frame>.png (default: --masks)')
+    ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
+                    help='--score: device = the ground-truth PNGs are inflated and unfiltered on the GPU in front of the J&F stage '
+                         '(inference/data/png_packet.py; a file the parser declines is decoded by PIL); default host: PIL on the issuing thread')
     ap.add_argument('--score-all-frames', action='store_true',
                     help='--score: also score the first and the last ground-truth frame of a video (the DAVIS protocol leaves them out)')
     return ap
@@ -397,7 +400,7 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
                   egress=args.egress, save_all=not burst, overlay=getattr(args, 'overlay', 'host'))     # (no ingest=: the readers carry the mode)
     score = bool(getattr(args, 'score', False))
     if score:
-        common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames))
+        common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames), gt_decode=args.gt_decode)
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is

@@ -5,16 +5,21 @@ host.  ``VideoReader(ingest='device')`` produces the records this module finishe
 
 ``ingest='device-decode'`` goes one step further: the record carries the parsed JPEG (inference/data/jpeg.py Packet), only its
 compressed bytes are uploaded, and the decode runs on the GPU as three more RESIZE stages (ABI 6, flags 8 / 16 / 32) in front of
-the same resize.  The uint8 frame equals PIL's, so the record equals the other modes' records."""
+the same resize.  The uint8 frame equals PIL's, so the record equals the other modes' records.
+
+``png_to_device`` does the same for mask PNGs (inference/data/png_packet.py; RESIZE flags 64 / 128, ABI 11, forms added): a batch of parsed files is
+uploaded in one copy and inflated and unfiltered in one launch per stage, one wave per image -- what the scorer's ``gt_decode='device'``
+and ``score_masks --decode device`` use.  The arrays equal ``np.array(Image.open(f))``."""
 import threading
 from contextlib import nullcontext
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from ... import ops as O
 from . import jpeg as J
+from . import png_packet as P
 
 F32 = torch.float32
 _tables: Dict[Tuple, torch.Tensor] = {}
@@ -113,6 +118,138 @@ def jpeg_to_device(pkt: J.Packet, device, size_hw=None, stream=None, name: Optio
         chk()
         return (out, b['rgb']) if keep_u8 else out
     return (out, chk, b['rgb']) if keep_u8 else (out, chk)
+
+
+png_stats = {'images': 0, 'tokens': 0, 'blocks': 0}     # GPU-decoded PNGs (checked), summed over the process
+
+
+class PngCheck:
+    """The status blocks of one PNG decode launch (int32 [N, 4]: error bits, bytes produced, blocks, tokens), copied to host memory behind
+    the launch on its stream.  Calling it waits for that copy only, then raises ValueError naming the first file whose error word is
+    nonzero; later calls do nothing.  ``status`` keeps the host copy."""
+    __slots__ = ('status', 'event', 'names', 'done')
+
+    def __init__(self, status_dev: torch.Tensor, names: Sequence[str]):
+        self.names, self.done = list(names), False
+        if status_dev.device.type == 'cuda':
+            self.status = torch.empty(status_dev.shape, dtype=torch.int32, pin_memory=True)
+            self.status.copy_(status_dev, non_blocking=True)
+            self.event = torch.cuda.Event()
+            self.event.record()
+        else:
+            self.status, self.event = status_dev.clone(), None
+
+    def __call__(self):
+        if self.done:
+            return
+        if self.event is not None:
+            self.event.synchronize()
+        self.done = True
+        st = self.status.numpy()
+        bad = np.flatnonzero(st[:, 0])
+        if len(bad):
+            k = int(bad[0])
+            raise ValueError(f'{self.names[k] or "mask"}: corrupt or truncated PNG data (GPU decode error bits {int(st[k, 0]):#x})')
+        with _stats_lock:
+            png_stats['images'] += len(st)
+            png_stats['blocks'] += int(st[:, 2].sum())
+            png_stats['tokens'] += int(st[:, 3].sum())
+
+
+class PngStaging:
+    """A few pinned upload buffers taken in turn (as SequenceScorer._upload's): a slot is reused only once its own upload has run -- its
+    event -- and the decode check that went with it is resolved then at the latest."""
+
+    def __init__(self, slots: int = 4):
+        self.slots, self.turn, self.ring = slots, 0, []
+        self.pending = []                    # checks of decodes that used no slot (a device without pinned staging)
+
+    def take(self, nbytes: int):
+        """-> (pinned uint8 [>= nbytes], slot): record the upload with ``slot['event'].record()`` and leave the check in ``slot['check']``."""
+        if len(self.ring) < self.slots:
+            self.ring.append({'host': None, 'event': torch.cuda.Event(), 'check': None})
+            slot = self.ring[-1]
+        else:
+            slot = self.ring[self.turn % self.slots]
+            slot['event'].synchronize()
+            chk, slot['check'] = slot['check'], None
+            if chk is not None:
+                chk()
+        self.turn += 1
+        if slot['host'] is None or slot['host'].numel() < nbytes:
+            slot['host'] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8).pin_memory()
+        return slot['host'], slot
+
+    def finish(self):
+        """Resolve every check that is still open."""
+        pending, self.pending = self.pending, []
+        for chk in pending:
+            chk()
+        for slot in self.ring:
+            chk, slot['check'] = slot['check'], None
+            if chk is not None:
+                chk()
+
+
+def png_to_device(packets: Sequence[P.Packet], device, stream=None, names: Optional[Sequence[str]] = None, check: bool = True,
+                  staging: Optional[PngStaging] = None, guard: int = 0):
+    """Parsed mask PNGs -> a list of uint8 device tensors, [H, W] (palette index / grey value) or [H, W, 3] each, equal to
+    ``np.array(Image.open(f))``.  ONE upload -- the offset table and the packets in one buffer, through pinned staging with a non-blocking
+    copy -- then one inflate and one unfilter launch over all images on `stream` (default: the current stream), one wave per image.
+    check=True: wait for the status blocks and raise ValueError naming the file (`names`, default the packets' files) if any was bad.
+    check=False: -> (tensors, PngCheck); the caller must call the check before it uses the results -- until then a tensor may hold garbage.
+    staging: a PngStaging whose buffers are used in turn (the check is then also left in the slot and resolved when the slot comes round
+    again or by ``staging.finish()``).  guard: that many bytes (a multiple of 16) of 0xA5 in front of and behind every image (tests)."""
+    from ... import _lib
+    dev = torch.device(device)
+    on_gpu = dev.type == 'cuda'
+    if on_gpu and not _lib.has_png_decode():
+        raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no PNG decode stages); rebuild it.')
+    n = len(packets)
+    if n == 0:
+        raise ValueError('png_to_device: no packet')
+    if guard % 16:
+        raise ValueError('png_to_device: guard is a multiple of 16')
+    names = [pk.source for pk in packets] if names is None else list(names)
+    table, pbytes, ibytes, obytes = O.OpList.png_layout(packets, guard)
+    head = 16 * n
+    total = head + pbytes
+    ctx = torch.cuda.stream(stream) if (on_gpu and stream is not None) else nullcontext()
+    with ctx:
+        slot = None
+        if on_gpu and staging is not None:
+            host, slot = staging.take(total)
+        elif on_gpu:
+            host = torch.empty(total, dtype=torch.uint8).pin_memory()
+        else:
+            host = torch.empty(total, dtype=torch.uint8)
+        hv = host.numpy()
+        hv[:head] = table.reshape(-1).view(np.uint8)
+        for k, pk in enumerate(packets):
+            o = head + int(table[k, 0])
+            hv[o:o + pk.buf.nbytes] = pk.buf
+        blob = host[:total].to(dev, non_blocking=True)
+        if slot is not None:
+            slot['event'].record()
+        infl = torch.empty(ibytes, dtype=torch.uint8, device=dev)
+        out = torch.full((obytes + guard,), 0xA5, dtype=torch.uint8, device=dev) if guard else torch.empty(obytes, dtype=torch.uint8, device=dev)
+        status = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        tab_dev = blob[:head].view(torch.int32)
+        ol = O.OpList(prio=False)
+        ol.png_inflate(blob[head:], tab_dev, infl, status, n=n, packet_bytes=pbytes)
+        ol.png_unfilter(blob[head:], tab_dev, infl, out, status, n=n, packet_bytes=pbytes)
+        ol.finalize()
+        ol.run()
+        chk = PngCheck(status, names)
+        if slot is not None:
+            slot['check'] = chk
+        elif staging is not None:
+            staging.pending.append(chk)
+    res = [out[int(table[k, 2]):int(table[k, 2]) + pk.nbytes_out].view(pk.shape) for k, pk in enumerate(packets)]
+    if check:
+        chk()
+        return res
+    return res, chk
 
 
 def frame_to_device(rgb_u8, device, size_hw=None, stream=None, keep_u8: bool = False):

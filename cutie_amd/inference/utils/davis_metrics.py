@@ -83,11 +83,21 @@ class SequenceScorer:
     objects are 1 .. max id of the FIRST ground-truth frame (255, the void label, aside), as in davis2017.  ``add`` loads the frame's
     ground truth, uploads it and enqueues the stage into row t of an int32 [T, K, 8] device table on the caller's stream -- no
     synchronisation, nothing comes back; ``finish`` makes the one copy of the table.  ``skip_first_last``: the first and the last
-    ground-truth frame of the sequence are not scored (the DAVIS semi-supervised protocol: the first is given, the last is left out)."""
+    ground-truth frame of the sequence are not scored (the DAVIS semi-supervised protocol: the first is given, the last is left out).
+    ``gt_decode='device'`` (default 'host': PIL): ``add`` parses the ground-truth file (inference/data/png_packet.py), uploads the few KB of
+    its compressed bytes and enqueues the two PNG decode stages (RESIZE flags 64 / 128) in front of the J&F stage on the caller's stream.
+    ``add`` itself adds no synchronisation for the frame it enqueues, but the decode's error word is looked at when its staging slot comes
+    round again, four frames later: that is a WAIT on the status copy behind that frame's decode launch (about 7 ms of GPU work for a 480p
+    mask alone in a launch), so from the fifth frame on ``add`` can block the issuing thread where the host route only waits for an upload.
+    The check, there or in ``finish``, raises ValueError naming a corrupt file.  A file the parser declines is decoded by PIL as before and counted in ``gt_fallbacks`` by reason.
+    The first ground-truth frame, which fixes the objects, is read on the host either way."""
 
-    def __init__(self, gt_dir, video_name, device, *, skip_first_last=True):
+    def __init__(self, gt_dir, video_name, device, *, skip_first_last=True, gt_decode='host'):
         from ... import ops as O
+        if gt_decode not in ('host', 'device'):
+            raise ValueError(f"score: gt_decode is 'host' or 'device', not {gt_decode!r}")
         self.video_name, self.device, self.skip_first_last = video_name, torch.device(device), skip_first_last
+        self.gt_decode, self.gt_fallbacks, self.gt_device_frames, self._png_staging = gt_decode, {}, 0, None
         self.dir = path.join(gt_dir, video_name) if video_name else gt_dir
         if not path.isdir(self.dir):
             raise ValueError(f'score: no ground-truth folder {self.dir}')
@@ -130,22 +140,57 @@ class SequenceScorer:
         ev.record()
         return dev
 
-    def add(self, frame_name, ids_dev):
-        """One frame: ``ids_dev`` = its predicted ids, uint8 [H, W] on the scorer's device.  A frame without ground truth is skipped."""
+    def _parse(self, gt_path):
+        """gt_decode='device': the file's packet, or None -- counted by reason -- when it goes the host way (a format the parser declines,
+        or a mode that load_ids refuses: its error is PIL's route's to raise)."""
+        from ..data import png_packet as P
+        pkt, why = P.parse_file(gt_path)
+        if pkt is not None and len(pkt.shape) != 2:
+            pkt, why = None, 'not a palette or grey mask'
+        if pkt is None:
+            self.gt_fallbacks[why] = self.gt_fallbacks.get(why, 0) + 1
+            P.count_fallback(why)
+        return pkt
+
+    def _decode(self, pkt):
+        """The ground-truth plane decoded on the device, on the caller's stream (device_ingest.png_to_device: one upload through a pinned
+        slot, two launches); the check stays with the slot."""
+        from ..data import device_ingest as DI
+        if self._png_staging is None:
+            self._png_staging = DI.PngStaging(self.STAGING)
+        (gt_dev,), _ = DI.png_to_device([pkt], self.device, check=False, staging=self._png_staging)
+        self.gt_device_frames += 1
+        return gt_dev
+
+    def gt_path(self, frame_name):
+        """The ground-truth file of a frame, or None."""
+        t = self.index.get(_stem(frame_name))
+        return None if t is None else path.join(self.dir, self.names[t])
+
+    def add(self, frame_name, ids_dev, gt_dev=None):
+        """One frame: ``ids_dev`` = its predicted ids, uint8 [H, W] on the scorer's device.  A frame without ground truth is skipped.
+        ``gt_dev``: the frame's ground truth, already a uint8 [H, W] plane on the device (score_masks decodes whole batches) -- nothing
+        is loaded then."""
         from ... import ops as O
         t = self.index.get(_stem(frame_name))
         if t is None or not self.objects:
             return
-        gt = load_ids(path.join(self.dir, self.names[t]))
+        gt_path = path.join(self.dir, self.names[t])
+        pkt = self._parse(gt_path) if (self.gt_decode == 'device' and gt_dev is None) else None
+        gt = load_ids(gt_path) if (pkt is None and gt_dev is None) else None
         H, W = int(ids_dev.shape[-2]), int(ids_dev.shape[-1])
-        if gt.shape != (H, W):
-            raise ValueError(f'score: {self.video_name}/{self.names[t]} is {gt.shape[0]} x {gt.shape[1]}, the prediction {H} x {W}')
+        gt_shape = tuple(gt_dev.shape) if gt_dev is not None else (tuple(gt.shape) if pkt is None else pkt.shape)
+        if gt_shape != (H, W):
+            raise ValueError(f'score: {self.video_name}/{self.names[t]} is {gt_shape[0]} x {gt_shape[1]}, the prediction {H} x {W}')
         if ids_dev.dtype != torch.uint8:
             raise ValueError(f'score: predicted ids are uint8, not {ids_dev.dtype}')
         pred = ids_dev.reshape(H, W)
         if not pred.is_contiguous():
             pred = pred.contiguous()
-        gt_dev = self._upload(gt)
+        if gt_dev is None:
+            gt_dev = self._upload(gt) if pkt is None else self._decode(pkt)
+        elif gt_dev.dtype != torch.uint8 or not gt_dev.is_contiguous():
+            raise ValueError('score: the ground-truth plane is a contiguous uint8 [H, W]')
         K = len(self.objects)
         if self._scratch is None or self._scratch[0] != (H, W):
             self._scratch = ((H, W), torch.empty(O.OpList.jf_scratch_words(H, W, K), dtype=torch.int32, device=self.device))
@@ -158,6 +203,8 @@ class SequenceScorer:
         """-> {'objects': [ids], 'frames': [names], 'counts': [t][k][8] ints, 'J': [t][k], 'F': [t][k]} of the scored frames, or None
         (reported) when there is none."""
         T = len(self.names)
+        if self._png_staging is not None:
+            self._png_staging.finish()                           # a corrupt ground-truth file raises here at the latest
         scored = [t for t in sorted(self.seen) if not (self.skip_first_last and t in (0, T - 1))]
         if not scored or not self.objects:
             log.warning(f'score: {self.video_name or self.dir} has no scored frame ({len(self.objects)} objects, {len(self.seen)} frames with '

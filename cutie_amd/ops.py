@@ -1133,6 +1133,55 @@ class OpList:
         """Stage 3: fancy upsampling + YCbCr -> RGB -> rgb uint8 [H, W, 3] packed."""
         return self._jpeg(32, pkt, planes=planes, rgb=rgb)
 
+    @staticmethod
+    def png_layout(packets, guard=0):
+        """The buffers of one PNG decode launch over ``packets`` (inference/data/png_packet.py Packet) -> (table int32 [N, 4] = per image the
+        byte offset of its packet, of its inflated rows and of its pixels, 0; packet bytes, inflate bytes, output bytes).  Packets and
+        inflated rows start at multiples of 16; pixels at multiples of 16 too, with ``guard`` bytes in front of and behind every image."""
+        table = np.zeros((len(packets), 4), dtype=np.int32)
+        po = io = oo = 0
+        for k, pkt in enumerate(packets):
+            oo += guard
+            table[k, :3] = po, io, oo
+            po += -(-pkt.buf.nbytes // 16) * 16
+            io += -(-pkt.inflated // 16) * 16
+            oo += -(-(pkt.nbytes_out + guard) // 16) * 16
+            if max(po, io, oo) >= 1 << 31:
+                raise ValueError('png decode: the buffers of one launch stay below 2^31 bytes')
+        return table, po, io, oo
+
+    def _png(self, flags, packets, table, inflate, out, status, *, n, packet_bytes=None):
+        # the forms came without a new ABI number: a library from before would run the descriptor as a plain RESIZE, so ask it first
+        # (an injected interpreter of the tests has no library; a missing library fails when the list runs)
+        if not getattr(_lib._executor, 'is_mock', False):
+            try:
+                known = _lib.has_png_decode()
+            except _lib.HipLibraryError:
+                known = True
+            if not known:
+                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no PNG decode stages, RESIZE flags 64 / 128); rebuild it.')
+        if table.dtype != torch.int32 or table.numel() < 4 * n or status.dtype != torch.int32 or status.numel() < 4 * n:
+            raise ValueError(f'png decode: table and status are int32 [{n}, 4]')
+        for name, t in (('packets', packets), ('inflate', inflate)) + ((('out', out),) if out is not None else ()):
+            if t.dtype != torch.uint8 or not t.is_contiguous():
+                raise ValueError(f'png decode: {name} is a contiguous uint8 buffer')
+        if not 1 <= n <= 65535:
+            raise ValueError(f'png decode: {n} images, 1 .. 65535')
+        return self.add(RESIZE, flags, [n, packets.numel() if packet_bytes is None else packet_bytes, inflate.numel(), 0 if out is None else out.numel()], [],
+                        [packets, table, inflate, out, status])
+
+    def png_inflate(self, packets, table, inflate, status, *, n, packet_bytes=None):
+        """RESIZE flags 64 (ABI 11, forms added, include/cutie_hip.h): the zlib streams of ``n`` PNG packets (uint8 buffer ``packets``, laid out by
+        ``table`` int32 [n, 4] -- png_layout) inflated into ``inflate`` (uint8, the filtered rows), one wave per image.  ``status`` int32
+        [n, 4], cleared by the launch: error bits, bytes produced, blocks, tokens.  All buffers 16-byte aligned."""
+        return self._png(64, packets, table, inflate, None, status, n=n, packet_bytes=packet_bytes)
+
+    def png_unfilter(self, packets, table, inflate, out, status, *, n, packet_bytes=None):
+        """RESIZE flags 128 (ABI 11, forms added): the filtered rows of png_inflate -> ``out`` uint8: per image [H, W] (palette index or grey value,
+        pixels of 1 / 2 / 4 bits unpacked) or [H, W, 3] at its table offset.  An image whose status has an error bit is left alone; a
+        filter byte above 4 sets one."""
+        return self._png(128, packets, table, inflate, out, status, n=n, packet_bytes=packet_bytes)
+
     def flip_w(self, src, dst, *, rows, W, slds=None, dlds=None, alpha=1.0, beta=0.0):
         return self.add(FLIP_W, 0, [rows, W, W if slds is None else slds, W if dlds is None else dlds], [alpha, beta], [src, dst])
 

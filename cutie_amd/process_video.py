@@ -150,7 +150,7 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
-                  gt_dir: Optional[str] = None, vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
+                  gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None) -> Dict:
     """gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
     joins the result.  vis_modes / soft_masks / alpha_matte / target_objects / layer: ResultSaver's (the module docstring); 'folders' of
@@ -219,7 +219,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         scorer = None
         if gt_dir is not None:
             from .inference.utils.davis_metrics import SequenceScorer
-            scorer = SequenceScorer(gt_dir, '', dev, skip_first_last=False)
+            scorer = SequenceScorer(gt_dir, '', dev, skip_first_last=False, gt_decode=gt_decode)
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
                             palette=palette, processor=processor, egress=egress, scorer=scorer, vis_modes=vis_modes, soft_masks=soft_masks,
                             alpha_matte=alpha_matte, target_objects=target_objects, layer=layer)
@@ -269,6 +269,8 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--alpha', action='store_true', help='the alpha matte of the target objects: OUT/alpha/*.png')
     ap.add_argument('--target-objects', nargs='+', type=int, metavar='ID', help='the objects popup, layer and the matte keep (default: all)')
     ap.add_argument('--layer', metavar='FILE', help='the RGBA image of --vis layer (resized to the frames)')
+    ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
+                    help='--gt: device = the ground-truth PNGs are decoded on the GPU (default host: PIL)')
     ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
     return ap
 
@@ -286,7 +288,7 @@ def main():
     else:
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
-                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt,
+                      mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize

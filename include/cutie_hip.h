@@ -486,7 +486,30 @@ enum {
      *    component blocks_w * 8 wide, whole blocks.
      *  flags&32 colour: libjpeg's fancy upsampling (h2v1 / h2v2 where the chroma width is > 2, h1v2 always; else replication) and its
      *    fixed-point YCbCr -> RGB tables (SCALEBITS 16); one component is replicated -> p5 = uint8 [H, W, 3], row stride i11 bytes:
-     *    the source of RESIZE flags 4 / 6. */
+     *    the source of RESIZE flags 4 / 6.
+     * ABI 11, forms added (the number stays 11; cutie_hip_build_flags() bit 1 says the forms are present -- a library from before would run
+     *    such a descriptor as a plain RESIZE, so the callers ask first) -- mask PNGs decoded on the GPU (SequenceScorer gt_decode='device',
+     *    score_masks --decode device; kernels in png_dec.hip, their serial core in png_inflate_core.h; the Python model: tests/png_dec_ref.py):
+     *    flags 64 / 128 are the two stages and may be set together (they run in that order); with either of them every other flag is an
+     *    error and the RESIZE fields above do not apply.  ONE launch takes i0 = N images (1 .. 65535), one wave64 per image.
+     *    p0 = packets uint8 (i1 bytes), built by cutie_amd/inference/data/png_packet.py: per image 8 little-endian int32 words -- magic
+     *    'PNGD', W, H, bit depth (1 | 2 | 4 | 8), channels (1; 3 = RGB at 8 bits), bytes per filtered row (<= 16384), stream bytes, inflated
+     *    bytes = H * (rowbytes + 1) -- then the zlib stream (all IDAT chunks joined).  p1 = table int32 [N][4]: per image the byte offset of
+     *    its packet in p0, of its inflated rows in p2 and of its pixels in p3 (the first two multiples of 16), 0.  p2 = inflate buffer
+     *    uint8 (i2 bytes), p3 = output uint8 (i3 bytes; flags&128 only), p4 = status int32 [N][4].  p0, p1, p2, p4 16-byte aligned.
+     *    Header and table are device data: both kernels check them against i1 .. i3 before they read anything else.
+     *  flags&64 inflate (RFC 1950 / 1951): stored, fixed and dynamic blocks, any number of them; code tables per block in LDS; one lane
+     *    decodes up to 64 tokens into an LDS queue, the wave executes it (literals scattered, a match copied by all lanes as
+     *    out[pos + i] = out[pos - dist + i % dist], the window being the output itself); Adler-32 of the output against the trailer.
+     *    status, cleared by the launch: 0 error bits -- 1 reserved block type, 2 over-subscribed / incomplete code lengths, 4 invalid
+     *    symbol, 8 distance beyond the bytes produced, 16 stream ends early, 32 output exceeds or falls short of the inflated length,
+     *    64 stored LEN != ~NLEN, 128 Adler-32 mismatch, 256 filter byte above 4 (set by flags&128), 512 bad packet header / table entry /
+     *    zlib header; 1 bytes produced, 2 blocks, 3 tokens.  The first error ends the image's decode; the other images are not affected.
+     *    Every stream read, output write and match source is bounds-checked when the token is decoded; the work is bounded by
+     *    8 * stream bytes + inflated bytes whatever the bytes are (png_inflate_core.h has the argument).
+     *  flags&128 unfilter + unpack: images without an error bit; rows in order, two rows in LDS; filters 0 / 2 lane-parallel, 1 a wave prefix
+     *    sum mod 256 per channel (filter unit 1 byte, 3 for RGB; packed depths on the packed bytes), 3 / 4 one serial lane; pixels of
+     *    1 / 2 / 4 bits unpacked MSB first -> uint8 [H, W], RGB -> uint8 [H, W, 3], at the image's offset in p3: np.array(Image.open(f)). */
     CUTIE_OP_RESIZE = 37,
     /* FLIP_W: dst = f0 * flip_last_dim(src) + f1 * dst   -- torch.flip(x, dims=[-1]) of the flip_aug path and the averaging
      * of the two passes (inference_core.py:162-165,234-235,303-305).  src and dst must not overlap.

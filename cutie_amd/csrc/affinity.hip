@@ -7,11 +7,18 @@
 //   KEY_PREP     memory side (once per memorised frame): A_i = [k_i^2 | k_i] split into bf16 hi/lo, scale_i
 //                query side  (per frame):                B_j = [-e_j | 2 k_j e_j] hi/lo, c_j = sum e_j k_j^2
 //                so that S_ij = scale_i * (A_i . B_j - c_j) is ONE K=128 contraction.
-//   AFF_SCORE/0  S tiles on MFMA (v_mfma_f32_16x16x32_bf16, 3 split terms hi*hi + hi*lo + lo*hi ~ fp32
-//                accuracy), reduced to per-(16-token tile, query) maxima.
+//   AFF_SCORE/0  S tiles on MFMA (v_mfma_f32_16x16x32_bf16, 3 split terms hi*hi + hi*lo + lo*hi), reduced to per-(16-token tile,
+//                query) maxima.  Accuracy: NOT that of an fp32 evaluation.  The operands are stored to 2^-16 and the lo*lo term is
+//                dropped, so a score is within ~7e-5 of its MAGNITUDE SUM scale (|A|.|B| + |c|), which does not cancel where the score
+//                does (a memory key close to the query key: every good match).  Measured against float64 (tests/test_gpu_aff_ref64.py,
+//                table in DESIGN.md section 5): worst logit error 2.7e-5 for keys ~ randn * 0.8, 2.6e-3 for randn * 3 and 2.3e-2 for randn * 8
+//                with near matches -- about ten times the error of the reference's own fp32 evaluation on the same inputs (2.3e-6, 3.3e-4,
+//                2.4e-3), i.e. softmax weights off by up to 3 % relative in the last regime.  Every stage is held to its derived
+//                per-element bound there (tests/aff_ref64.py).
 //   AFF_SELECT   tau_j = top_k-th largest tile maximum: a lower bound of the top_k-th largest score with
 //                only ~top_k..1.2*top_k scores above it (radix select, exact).
-//   AFF_SCORE/1  S tiles again (cheap: 3*2*128 flop per score), append the few scores >= tau_j.
+//   AFF_SCORE/1  S tiles again (cheap: 3*2*128 flop per score), append the few scores >= tau_j (tau_j itself: both passes compute
+//                the same bits for the same score in every kernel form, tests/test_gpu_aff_ref64.py test_score_passes).
 //   AFF_READOUT  exact top-k of the candidates (ties -> lower slot), softmax, usage, sparse V gather.
 //
 // Memory tokens are addressed by *physical bank slot*; the bank is contiguous per bucket (keys) and per
@@ -365,8 +372,11 @@ __global__ __launch_bounds__(256) void aff_score_kernel(ScoreParams p) {
 #pragma unroll
     for (int u = 0; u < AFF_NQ; ++u) {
         ncj[u] = jvalid[u] ? -craw[u] : 0.f;
-        const float tcut = traw[u] - fabsf(traw[u]) * 1e-6f - 1e-30f;   // never lose the k-th element to 1 ulp
-        thr[u] = (mode == 1 && jvalid[u]) ? tcut : INFINITY;
+        // the threshold is tau itself: pass 1 computes every score with the instructions of pass 0 in the same order, whatever the form of
+        // either pass, so the token that made a tile's maximum is found again bit for bit (tests/test_gpu_aff_ref64.py holds every pairing
+        // of forms to it).  (The cut used to sit 1e-6 |tau| lower, "never lose the k-th element to 1 ulp": all it did was let scores BELOW tau
+        // into the lists -- which the read-out never selects, >= top_k entries >= tau being there -- against the `S >= tau_j` of cutie_hip.h.)
+        thr[u] = (mode == 1 && jvalid[u]) ? traw[u] : INFINITY;
     }
 #pragma unroll
     for (int u = 0; u < AFF_NQ; ++u) gcur[u] = gq[u];
@@ -645,7 +655,7 @@ __global__ __launch_bounds__(256) void aff_score4_kernel(ScoreParams p) {
             thr[u] = INFINITY;
             if (mode == 1) {
                 const float tau = tau_p[min(jq[u], p.HWp - 1)];
-                thr[u] = jvalid[u] ? tau - fabsf(tau) * 1e-6f - 1e-30f : INFINITY;     // never lose the k-th element to 1 ulp
+                thr[u] = jvalid[u] ? tau : INFINITY;                                   // tau itself (see aff_score_kernel)
             }
         }
     }

@@ -313,7 +313,7 @@ class MemoryManager:
             ol = O.OpList()
             ops_ = dict(clear=[])
             common = dict(HW=HW, HWp=HWp, ranges=ranges, cap=CAND_CAP, frames=F)
-            # kernel forms by the number of stacked frames (same bits whatever the form, tests/test_gpu_kernels.py; isolated stage
+            # kernel forms by the number of stacked frames (same bits whatever the form and whichever form ran the other pass: tests/test_gpu_aff_ref64.py test_score_passes; isolated stage
             # times at 12.2 k tokens, tools/aff_batch_ab.py, profiles/r05_affinity.md): from three frames on the score pass runs 64 queries
             # per wave on the LDS-DMA kernel (its longer prologue is amortised: 70.6 against 80.0 us at F = 5, MFMA utilisation 0.44
             # against 0.39) and the candidate pass stages its memory tiles by LDS-DMA (94 against 103 us)

@@ -225,7 +225,7 @@ enum {
      * flags&2 (query side): c summed by one lane per row in a 64-step loop (A/B switch; default: the row's lanes hand the running sum on --
      *      the same additions in the same order) */
     CUTIE_OP_KEY_PREP = 23,
-    /* AFF_SCORE: S = scale_i*(A_i.B_j - c_j) tiles on MFMA (3-term split bf16, fp32-class accuracy)
+    /* AFF_SCORE: S = scale_i*(A_i.B_j - c_j) tiles on MFMA (3-term split bf16: within ~7e-5 of the magnitude sum, see affinity.hip)
      * mode 0: per-(16-token tile, query) maxima -> gmax f32 [HWp, Gld] (query-major, Gld = G rounded up to 64)
      * mode 1: append (S,token) with S >= tau_j to cand lists (f32,i32) [HW,cap], count i32 [HW*32] (counter of query j at [32*j]: one 128-B line each)
      * memory_utils.py:7-46 get_similarity + the candidate pre-filter of top-k (:58)

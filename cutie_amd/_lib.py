@@ -68,6 +68,12 @@ def has_png_decode():
     return bool(load().cutie_hip_build_flags() & 2)
 
 
+def has_jpeg_batch():
+    """Does the loaded library know RESIZE flags 256, the batch forms of the JPEG decode stages?  Added without a new ABI number as well; a
+    library from before would read such a descriptor as a one-frame decode (inference/data/device_ingest.py jpegs_to_device)."""
+    return bool(load().cutie_hip_build_flags() & 4)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

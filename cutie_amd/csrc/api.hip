@@ -131,7 +131,8 @@ const char* cutie_hip_last_error(void) { return g_err; }
 int cutie_hip_abi_version(void) { return 11; }
 int cutie_op_struct_size(void) { return (int)sizeof(cutie_op); }
 int cutie_hip_build_flags(void) {
-    const int forms = 2;             // bit 1: RESIZE flags 64 / 128, the PNG decode stages (ABI 11, forms added)
+    // bit 1: RESIZE flags 64 / 128, the PNG decode stages; bit 2: RESIZE flags 256, the batch forms of the JPEG decode (ABI 11, forms added)
+    const int forms = 2 | 4;
 #ifdef CUTIE_DIAG
     return forms | 1;
 #else

@@ -87,7 +87,7 @@ int launch_qchain(const cutie_op* op, hipStream_t s);        // qchain.hip: atte
 int launch_affinity(const cutie_op* op, hipStream_t s);      // affinity.hip
 int launch_bank(const cutie_op* op, hipStream_t s);          // bank.hip
 int launch_resize_ingest(const cutie_op* op, hipStream_t s); // ingest.hip: RESIZE with flags&2 / flags&4 (ABI 5)
-int launch_jpeg(const cutie_op* op, hipStream_t s);          // jpeg.hip: RESIZE with flags&8 / 16 / 32 (ABI 6)
+int launch_jpeg(const cutie_op* op, hipStream_t s);          // jpeg.hip: RESIZE with flags&8 / 16 / 32 (ABI 6; with 256: N images, ABI 11, forms added)
 int launch_png_decode(const cutie_op* op, hipStream_t s);     // png_dec.hip: RESIZE with flags&64 / 128 (ABI 11, forms added)
 int launch_png_deflate(const cutie_op* op, int H, int W, hipStream_t s);   // png.hip: PROB_TO_ID with flags&8 (ABI 7)
 int launch_rle_encode(const cutie_op* op, hipStream_t s);                  // rle.hip: PROB_TO_ID with flags == 32 (ABI 9)

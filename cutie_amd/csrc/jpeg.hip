@@ -209,8 +209,9 @@ __device__ __forceinline__ int run_chunk(const Geo& g, Chunk& c, Sym& s) {
 
 constexpr int HUFF_BS = 256;
 
-__global__ __launch_bounds__(HUFF_BS) void jpeg_spec_kernel(const uint8_t* __restrict__ pkt, Work wk, int nchunk, int chunk_bits) {
-    __shared__ Lds l;
+// The bodies of the stages are device functions of (packet, work area, ...) so that the one-frame entry points below and the batch
+// entry points further down (one image per blockIdx.y) run the same code.
+__device__ __forceinline__ void spec_body(Lds& l, const uint8_t* __restrict__ pkt, Work wk, int nchunk, int chunk_bits) {
     const Geo g = load_geo((const int*)pkt, l);
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nchunk) return;
@@ -220,13 +221,16 @@ __global__ __launch_bounds__(HUFF_BS) void jpeg_spec_kernel(const uint8_t* __res
     wk.exits[j] = pack_exit(s);
 }
 
+__global__ __launch_bounds__(HUFF_BS) void jpeg_spec_kernel(const uint8_t* __restrict__ pkt, Work wk, int nchunk, int chunk_bits) {
+    __shared__ Lds l;
+    spec_body(l, pkt, wk, nchunk, chunk_bits);
+}
+
 // sync round r: the chunks of segments that changed in round r - 1 (round 0: all) decode again from their predecessor's exit;
 // a changed exit sets flags[r][segment] and the thread continues into the next chunks while their stored exits differ.  Exits are
 // read and written as whole 64-bit words; a thread racing with a continuation may store a stale exit, which the next round sees.
 constexpr int SYNC_AHEAD = 32;
-__global__ __launch_bounds__(HUFF_BS) void jpeg_sync_kernel(const uint8_t* __restrict__ pkt, Work wk, int nchunk, int nseg, int chunk_bits,
-                                                            int r) {
-    __shared__ Lds l;
+__device__ __forceinline__ void sync_body(Lds& l, const uint8_t* __restrict__ pkt, Work wk, int nchunk, int nseg, int chunk_bits, int r) {
     const Geo g = load_geo((const int*)pkt, l);
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nchunk) return;
@@ -250,11 +254,16 @@ __global__ __launch_bounds__(HUFF_BS) void jpeg_sync_kernel(const uint8_t* __res
     }
 }
 
+__global__ __launch_bounds__(HUFF_BS) void jpeg_sync_kernel(const uint8_t* __restrict__ pkt, Work wk, int nchunk, int nseg, int chunk_bits,
+                                                            int r) {
+    __shared__ Lds l;
+    sync_body(l, pkt, wk, nchunk, nseg, chunk_bits, r);
+}
+
 // status[1] = max over segments of the rounds until no change (rounds + 1: serial); a segment that still changed in the last round
 // is decoded by one thread from its start (status[2] counts them)
-__global__ __launch_bounds__(64) void jpeg_serial_kernel(const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nseg,
-                                                         int chunk_bits, int rounds) {
-    __shared__ Lds l;
+__device__ __forceinline__ void serial_body(Lds& l, const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nseg,
+                                            int chunk_bits, int rounds) {
     const Geo g = load_geo((const int*)pkt, l);
     const int si = blockIdx.x * blockDim.x + threadIdx.x;
     if (si >= nseg) return;
@@ -271,6 +280,12 @@ __global__ __launch_bounds__(64) void jpeg_serial_kernel(const uint8_t* __restri
         wk.put(j, run_chunk(g, c, s), s);
         wk.exits[j] = pack_exit(s);
     }
+}
+
+__global__ __launch_bounds__(64) void jpeg_serial_kernel(const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nseg,
+                                                         int chunk_bits, int rounds) {
+    __shared__ Lds l;
+    serial_body(l, pkt, wk, status, nseg, chunk_bits, rounds);
 }
 
 constexpr int SCAN_BS = 1024;
@@ -292,8 +307,7 @@ __device__ __forceinline__ int block_scan(int* part, int v) {
 
 // one workgroup: offs / dcoffs = exclusive scans of the chunk block counts / DC sums (over all chunks; a segment subtracts the value
 // at its first chunk); every segment must end at least the blocks of its MCUs
-__global__ __launch_bounds__(SCAN_BS) void jpeg_scan_kernel(const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nchunk) {
-    __shared__ int part[SCAN_BS];
+__device__ __forceinline__ void scan_body(int* part, const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nchunk) {
     const int* w = (const int*)pkt;
     const int t = threadIdx.x, per = (nchunk + SCAN_BS - 1) / SCAN_BS;
     const int lo = min(t * per, nchunk), hi = min(lo + per, nchunk);
@@ -315,6 +329,11 @@ __global__ __launch_bounds__(SCAN_BS) void jpeg_scan_kernel(const uint8_t* __res
     }
 }
 
+__global__ __launch_bounds__(SCAN_BS) void jpeg_scan_kernel(const uint8_t* __restrict__ pkt, Work wk, int* __restrict__ status, int nchunk) {
+    __shared__ int part[SCAN_BS];
+    scan_body(part, pkt, wk, status, nchunk);
+}
+
 // block ordinal in scan order -> coefficient block index
 __device__ __forceinline__ int block_index(const Geo& g, int mcus_x, int ordinal) {
     const int m = ordinal / g.bpm, b = ordinal - m * g.bpm;
@@ -324,9 +343,8 @@ __device__ __forceinline__ int block_index(const Geo& g, int mcus_x, int ordinal
     return cw[C_BLK_OFF] + (my * cw[C_V] + mb[2]) * cw[C_BW] + mx * cw[C_H] + mb[1];
 }
 
-__global__ __launch_bounds__(HUFF_BS) void jpeg_write_kernel(const uint8_t* __restrict__ pkt, Work wk, int16_t* __restrict__ coef,
-                                                             int* __restrict__ status, int nchunk, int chunk_bits, int nblock) {
-    __shared__ Lds l;
+__device__ __forceinline__ void write_body(Lds& l, const uint8_t* __restrict__ pkt, Work wk, int16_t* __restrict__ coef,
+                                           int* __restrict__ status, int nchunk, int chunk_bits, int nblock) {
     const Geo g = load_geo((const int*)pkt, l);
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nchunk) return;
@@ -345,6 +363,12 @@ __global__ __launch_bounds__(HUFF_BS) void jpeg_write_kernel(const uint8_t* __re
         if (s.p > nbits) s.err |= ERR_TRUNC;
     }
     if (s.err) atomicOr(status, s.err);
+}
+
+__global__ __launch_bounds__(HUFF_BS) void jpeg_write_kernel(const uint8_t* __restrict__ pkt, Work wk, int16_t* __restrict__ coef,
+                                                             int* __restrict__ status, int nchunk, int chunk_bits, int nblock) {
+    __shared__ Lds l;
+    write_body(l, pkt, wk, coef, status, nchunk, chunk_bits, nblock);
 }
 
 // ---- IDCT: libjpeg's jpeg_idct_islow (jidctint.c) in its JLONG (64-bit) arithmetic; 8 threads per block ---------------------------
@@ -376,9 +400,8 @@ __device__ __forceinline__ uint32_t range_limit(int x) {         // sample_range
 }
 
 constexpr int IDCT_BS = 256;
-__global__ __launch_bounds__(IDCT_BS) void jpeg_idct_kernel(const uint8_t* __restrict__ pkt, const int16_t* __restrict__ coef,
-                                                            uint8_t* __restrict__ planes, int nblock, long plane_bytes) {
-    __shared__ int ws[IDCT_BS / 8][65];
+__device__ __forceinline__ void idct_body(int (*ws)[65], const uint8_t* __restrict__ pkt, const int16_t* __restrict__ coef,
+                                          uint8_t* __restrict__ planes, int nblock, long plane_bytes) {
     const int* w = (const int*)pkt;
     const int lb = threadIdx.x >> 3, t = threadIdx.x & 7;
     const int g = blockIdx.x * (IDCT_BS / 8) + lb;
@@ -421,6 +444,12 @@ __global__ __launch_bounds__(IDCT_BS) void jpeg_idct_kernel(const uint8_t* __res
     }
 }
 
+__global__ __launch_bounds__(IDCT_BS) void jpeg_idct_kernel(const uint8_t* __restrict__ pkt, const int16_t* __restrict__ coef,
+                                                            uint8_t* __restrict__ planes, int nblock, long plane_bytes) {
+    __shared__ int ws[IDCT_BS / 8][65];
+    idct_body(ws, pkt, coef, planes, nblock, plane_bytes);
+}
+
 // ---- upsampling (jdsample.c) + YCbCr -> RGB (jdcolor.c, SCALEBITS 16) ------------------------------------------------------------
 __device__ __forceinline__ int px(const uint8_t* p, int pw, int y, int x) { return p[(long)y * pw + x]; }
 
@@ -444,8 +473,8 @@ __device__ __forceinline__ int chroma(const uint8_t* p, int pw, int dw, int dh, 
 
 __device__ __forceinline__ uint8_t clamp255(int v) { return (uint8_t)min(max(v, 0), 255); }
 
-__global__ void jpeg_color_kernel(const uint8_t* __restrict__ pkt, const uint8_t* __restrict__ planes, uint8_t* __restrict__ rgb,
-                                  int H, int W, long ld) {
+__device__ __forceinline__ void color_body(const uint8_t* __restrict__ pkt, const uint8_t* __restrict__ planes, uint8_t* __restrict__ rgb,
+                                           int H, int W, long ld) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (long)H * W) return;
     const int y = (int)(idx / W), x = (int)(idx - (long)y * W);
@@ -464,12 +493,208 @@ __global__ void jpeg_color_kernel(const uint8_t* __restrict__ pkt, const uint8_t
     o[2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
 }
 
+__global__ void jpeg_color_kernel(const uint8_t* __restrict__ pkt, const uint8_t* __restrict__ planes, uint8_t* __restrict__ rgb,
+                                  int H, int W, long ld) {
+    color_body(pkt, planes, rgb, H, W, ld);
+}
+
+// ---- batch forms (flags & 256; include/cutie_hip.h, ABI 11, forms added): N images through one chain of launches ---------------------
+// The image index is blockIdx.y (blockIdx.x for the scan, one workgroup per image); the grids are sized for the largest image of the
+// batch and the workgroups past an image's own count return.  Table and packet headers are device data: every entry point checks the
+// image's row and header against the totals of the descriptor (load_img) before it touches anything else of the image, and skips an
+// image that fails (error bit 4).  The check is a pure function of data that no stage writes, so every stage decides alike.
+constexpr int ERR_TABLE = 4, MAGIC = 0x3147504A, HDR_WORDS = 64;
+enum { R_PKT, R_WORK, R_COEF, R_PLANES, R_RGB, R_PKT_BYTES, R_LD, R_RESERVED, ROW_WORDS };
+
+struct Batch {                     // the descriptor: buffer bases, their extents, the grid bounds
+    const uint8_t* pkts;
+    const int* tab;
+    int* work;
+    int16_t* coef;
+    uint8_t *planes, *rgb;
+    int* status;
+    long pkt_bytes, work_words, coef_elems, plane_bytes, rgb_bytes, max_pix;
+    int n, rounds, max_chunk, max_seg, max_block;
+};
+
+struct Img {                       // one image of the batch: what the one-frame launcher passes to the kernels
+    const uint8_t* pkt;
+    Work wk;
+    int16_t* coef;
+    uint8_t *planes, *rgb;
+    int* status;
+    long plane_bytes, ld;
+    int nchunk, nseg, nblock, chunk_bits, H, W;
+};
+
+__device__ __forceinline__ bool section(long off, long n, long words) { return off >= HDR_WORDS && off + n <= words; }
+
+// row k and its packet header against the descriptor -> the image's pointers; false: bad table or header, nothing of the image is used
+__device__ __forceinline__ bool load_img(const Batch& b, int k, Img& m) {
+    const int* r = b.tab + (long)k * ROW_WORDS;
+    m.status = b.status + 4L * k;
+    const long po = r[R_PKT], pb = r[R_PKT_BYTES];
+    if (po < 0 || (po & 15) || pb < 4 * HDR_WORDS || (pb & 3) || po + pb > b.pkt_bytes) return false;
+    const int* h = (const int*)(b.pkts + po);
+    if (h[H_MAGIC] != MAGIC || h[H_BYTES] != pb) return false;
+    const long words = pb >> 2, nchunk = h[H_NCHUNK], nseg = h[H_NSEG], nblock = h[H_NBLOCK], ncomp = h[H_NCOMP], H = h[H_H], W = h[H_W];
+    if (nchunk < 1 || nchunk > b.max_chunk || nseg < 1 || nseg > b.max_seg || nblock < 1 || nblock > b.max_block) return false;
+    if (H < 1 || W < 1 || H * W > b.max_pix || (ncomp != 1 && ncomp != 3) || h[H_CHUNK_BITS] < 64) return false;
+    if (h[H_BPM] < 1 || h[H_BPM] > MAX_BPM || h[H_NTAB] < 1 || h[H_NTAB] > MAX_TAB || h[H_MCUS_X] < 1 || h[H_NMCU] < 1 || h[H_RI] < 1 ||
+        h[H_HMAX] < 1 || h[H_HMAX] > 2 || h[H_VMAX] < 1 || h[H_VMAX] > 2)
+        return false;
+    if (!section(h[H_OFF_SEG], 4 * nseg, words) || !section(h[H_OFF_C2S], nchunk, words) || !section(h[H_OFF_COMP], 3 * COMP_WORDS, words) ||
+        !section(h[H_OFF_MB], 4 * MAX_BPM, words) || !section(h[H_OFF_Q], 64 * ncomp, words) ||
+        !section(h[H_OFF_HUFF], (long)h[H_NTAB] * TABW, words) || h[H_OFF_DATA] < 4 * HDR_WORDS || h[H_OFF_DATA] > pb)
+        return false;
+    // the work area ends where the next image's begins: the chunks and segments of the header must fit what the host laid out
+    const long wo = r[R_WORK], wend = k + 1 < b.n ? (long)b.tab[(long)(k + 1) * ROW_WORDS + R_WORK] : b.work_words;
+    if (wo < 0 || (wo & 1) || wend < wo || wend > b.work_words || 10 * nchunk + (b.rounds + 1) * nseg > wend - wo) return false;
+    const long co = r[R_COEF], plo = r[R_PLANES], ro = r[R_RGB], ld = r[R_LD], plane_bytes = h[H_PLANE_BYTES];
+    if (co < 0 || (co & 7) || co + 64 * nblock > b.coef_elems) return false;
+    if (plo < 0 || (plo & 7) || plane_bytes < 64 * nblock || plo + plane_bytes > b.plane_bytes) return false;
+    if (ro < 0 || (ro & 15) || ld < 3 * W || ro + (H - 1) * ld + 3 * W > b.rgb_bytes) return false;
+    m.pkt = b.pkts + po;
+    int* wk = b.work + wo;
+    m.wk.exits = (uint64_t*)wk;
+    m.wk.counts = wk + 2 * nchunk;
+    m.wk.offs = m.wk.counts + nchunk;
+    m.wk.dcs = m.wk.offs + nchunk;
+    m.wk.dcoffs = m.wk.dcs + 3 * nchunk;
+    m.wk.flags = m.wk.dcoffs + 3 * nchunk;
+    m.coef = b.coef + co;
+    m.planes = b.planes + plo;
+    m.rgb = b.rgb + ro;
+    m.plane_bytes = plane_bytes;
+    m.ld = ld;
+    m.nchunk = (int)nchunk; m.nseg = (int)nseg; m.nblock = (int)nblock; m.chunk_bits = h[H_CHUNK_BITS]; m.H = (int)H; m.W = (int)W;
+    return true;
+}
+
+// the whole workgroup takes the same branch (the image is per workgroup), so a return here is in front of every barrier
+#define JPEG_BATCH_IMAGE(b, k, m, live)                                                   \
+    Img m;                                                                                \
+    if (!load_img(b, k, m)) {                                                             \
+        if (threadIdx.x == 0 && (live)) atomicOr(m.status, ERR_TABLE);                    \
+        return;                                                                           \
+    }
+
+// per-round flags and coefficients of every image to 0.  A kernel and not memsets: the images' regions are apart (other rows' data,
+// guard bytes of the tests lie between them), so memsets would be one per image and buffer; this is one launch whatever N is.
+__global__ __launch_bounds__(256) void jpeg_clear_batch_kernel(Batch b) {
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, blockIdx.x == 0)
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < (long)(b.rounds + 1) * m.nseg) m.wk.flags[t] = 0;
+    if (t < 8L * m.nblock) ((uint4*)m.coef)[t] = uint4{0, 0, 0, 0};         // (16-byte aligned: base and offset are)
+}
+
+__global__ __launch_bounds__(HUFF_BS) void jpeg_spec_batch_kernel(Batch b) {
+    __shared__ Lds l;
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, false)
+    if ((int)(blockIdx.x * HUFF_BS) >= m.nchunk) return;                      // (before the table copy: a small image beside a large one)
+    spec_body(l, m.pkt, m.wk, m.nchunk, m.chunk_bits);
+}
+
+__global__ __launch_bounds__(HUFF_BS) void jpeg_sync_batch_kernel(Batch b, int r) {
+    __shared__ Lds l;
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, false)
+    if ((int)(blockIdx.x * HUFF_BS) >= m.nchunk) return;
+    sync_body(l, m.pkt, m.wk, m.nchunk, m.nseg, m.chunk_bits, r);
+}
+
+__global__ __launch_bounds__(64) void jpeg_serial_batch_kernel(Batch b) {
+    __shared__ Lds l;
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, false)
+    if ((int)(blockIdx.x * 64) >= m.nseg) return;
+    serial_body(l, m.pkt, m.wk, m.status, m.nseg, m.chunk_bits, b.rounds);
+}
+
+__global__ __launch_bounds__(SCAN_BS) void jpeg_scan_batch_kernel(Batch b) {
+    __shared__ int part[SCAN_BS];
+    JPEG_BATCH_IMAGE(b, blockIdx.x, m, false)
+    scan_body(part, m.pkt, m.wk, m.status, m.nchunk);
+}
+
+__global__ __launch_bounds__(HUFF_BS) void jpeg_write_batch_kernel(Batch b) {
+    __shared__ Lds l;
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, false)
+    if ((int)(blockIdx.x * HUFF_BS) >= m.nchunk) return;
+    write_body(l, m.pkt, m.wk, m.coef, m.status, m.nchunk, m.chunk_bits, m.nblock);
+}
+
+// (the IDCT and colour stages may be launched on their own, so they set the error bit too)
+__global__ __launch_bounds__(IDCT_BS) void jpeg_idct_batch_kernel(Batch b) {
+    __shared__ int ws[IDCT_BS / 8][65];
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, blockIdx.x == 0)
+    if ((int)(blockIdx.x * (IDCT_BS / 8)) >= m.nblock) return;
+    idct_body(ws, m.pkt, m.coef, m.planes, m.nblock, m.plane_bytes);
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_batch_kernel(Batch b) {
+    JPEG_BATCH_IMAGE(b, blockIdx.y, m, blockIdx.x == 0)
+    color_body(m.pkt, m.planes, m.rgb, m.H, m.W, m.ld);
+}
+
 }  // namespace
 
 #define GRID1D(n, bs) dim3((unsigned)(((long)(n) + (bs) - 1) / (bs)))
 
+// RESIZE flags 8 / 16 / 32 with flags & 256 (include/cutie_hip.h, ABI 11, forms added): the stages over i0 images, one launch each
+static int launch_jpeg_batch(const cutie_op* op, hipStream_t s) {
+    const int32_t* i = op->i;
+    const uint64_t* p = op->p;
+    if (op->flags & ~(256 | 56)) { cutie_set_error("jpeg batch: flags 8 / 16 / 32 with 256, nothing else"); return -2; }
+    Batch b;
+    b.pkts = (const uint8_t*)p[0]; b.tab = (const int*)p[1]; b.work = (int*)p[2]; b.coef = (int16_t*)p[3];
+    b.planes = (uint8_t*)p[4]; b.rgb = (uint8_t*)p[5]; b.status = (int*)p[6];
+    b.n = i[0]; b.pkt_bytes = i[1]; b.work_words = i[2]; b.coef_elems = i[3]; b.plane_bytes = i[4]; b.rgb_bytes = i[5];
+    b.rounds = i[6]; b.max_chunk = i[7]; b.max_seg = i[8]; b.max_block = i[9]; b.max_pix = i[10];
+    if (b.n < 1 || b.n > 65535) { cutie_set_error("jpeg batch: %d images (1 .. 65535)", b.n); return -2; }
+    if (!p[0] || !p[1] || !p[6] || ((p[0] | p[1] | p[6]) & 15) || b.pkt_bytes < 256) {
+        cutie_set_error("jpeg batch: packets (p0, i1 bytes), table (p1) and status (p6), 16-byte aligned");
+        return -2;
+    }
+    if (b.rounds < 0 || b.rounds > 64 || b.max_chunk < 1 || b.max_seg < 1 || b.max_block < 1 || b.max_pix < 1) {
+        cutie_set_error("jpeg batch: bad bounds (rounds %d, chunks %d, segments %d, blocks %d, pixels %ld)", b.rounds, b.max_chunk, b.max_seg,
+                        b.max_block, b.max_pix);
+        return -2;
+    }
+    const unsigned N = (unsigned)b.n;
+    if (op->flags & 8) {
+        if (!p[2] || !p[3] || (p[2] & 7) || (p[3] & 15) || b.work_words < 1 || b.coef_elems < 64) {
+            cutie_set_error("jpeg batch: the Huffman stage needs work (p2, 8-byte aligned, i2 words) and coef (p3, 16-byte aligned, i3 elements)");
+            return -2;
+        }
+        const long clear = std::max(8L * b.max_block, (long)(b.rounds + 1) * b.max_seg);
+        const dim3 huff(GRID1D(b.max_chunk, HUFF_BS).x, N);
+        hipMemsetAsync(b.status, 0, sizeof(int) * 4 * (size_t)b.n, s);
+        hipLaunchKernelGGL(jpeg_clear_batch_kernel, dim3(GRID1D(clear, 256).x, N), dim3(256), 0, s, b);
+        hipLaunchKernelGGL(jpeg_spec_batch_kernel, huff, dim3(HUFF_BS), 0, s, b);
+        for (int r = 0; r < b.rounds; ++r) hipLaunchKernelGGL(jpeg_sync_batch_kernel, huff, dim3(HUFF_BS), 0, s, b, r);
+        hipLaunchKernelGGL(jpeg_serial_batch_kernel, dim3(GRID1D(b.max_seg, 64).x, N), dim3(64), 0, s, b);
+        hipLaunchKernelGGL(jpeg_scan_batch_kernel, dim3(N), dim3(SCAN_BS), 0, s, b);
+        hipLaunchKernelGGL(jpeg_write_batch_kernel, huff, dim3(HUFF_BS), 0, s, b);
+    }
+    if (op->flags & 16) {
+        if (!p[3] || !p[4] || (p[3] & 15) || (p[4] & 7) || b.plane_bytes < 64) {
+            cutie_set_error("jpeg batch: the IDCT stage needs coef (p3, 16-byte aligned) and planes (p4, 8-byte aligned, i4 bytes)");
+            return -2;
+        }
+        hipLaunchKernelGGL(jpeg_idct_batch_kernel, dim3(GRID1D(b.max_block, IDCT_BS / 8).x, N), dim3(IDCT_BS), 0, s, b);
+    }
+    if (op->flags & 32) {
+        if (!p[4] || !p[5] || (p[4] & 7) || (p[5] & 15) || b.rgb_bytes < 3) {
+            cutie_set_error("jpeg batch: the colour stage needs planes (p4, 8-byte aligned) and rgb (p5, 16-byte aligned, i5 bytes)");
+            return -2;
+        }
+        hipLaunchKernelGGL(jpeg_color_batch_kernel, dim3(GRID1D(b.max_pix, 256).x, N), dim3(256), 0, s, b);
+    }
+    return (int)hipGetLastError();
+}
+
 // RESIZE flags 8 / 16 / 32 (include/cutie_hip.h, ABI 6): the stages whose flag is set, in order
 int launch_jpeg(const cutie_op* op, hipStream_t s) {
+    if (op->flags & 256) return launch_jpeg_batch(op, s);
     const int32_t* i = op->i;
     const uint64_t* p = op->p;
     const int nchunk = i[0], nseg = i[1], nblock = i[2], chunk_bits = i[3], rounds = i[4], H = i[7], W = i[8], ncomp = i[10];

@@ -9,7 +9,7 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
 
     python -m cutie_amd.eval_vos --images DIR/JPEGImages --masks DIR/Annotations --output OUT [--weights ckpt.pth]
         [--size 480] [--use-all-masks] [--long-term] [--dataset d17-val] [--visualize] [--clips-in-flight 2] [--lockstep 4]
-        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode] [--egress device] [--overlay device]      (multi-scale testing: one run per --size with --save-scores, then
+        [--model small] [--flip-aug] [--save-scores] [--ingest device|device-decode [--decode-batch 8]] [--egress device] [--overlay device]      (multi-scale testing: one run per --size with --save-scores, then
                                            python -m cutie_amd.merge_multi_scale --list OUT_a OUT_b --output MERGED)
         [--sizes 480 600 720]              (multi-scale testing in ONE run: the scales of a video advance side by side and are merged on the GPU,
                                             no score files -- process_video_multiscale; excludes --size, --save-scores and --lockstep > 1)
@@ -30,14 +30,14 @@ import os
 import time
 from contextlib import nullcontext
 from os import path
-from typing import Dict
+from typing import Dict, List
 
 import torch
 
 from .config import default_config
-from .inference.data.device_ingest import finish, to_device
+from .inference.data.device_ingest import PngStaging, finish, to_device, to_device_many
 from .inference.data.burst_test_dataset import BURSTTestDataset
-from .inference.data.prefetch import ReadAhead, Window
+from .inference.data.prefetch import ReadAhead, Window, fill_together, pop_together
 from .inference.data.video_reader import INGEST_MODES
 from .inference.data.vos_test_dataset import VOSTestDataset
 from .inference.inference_core import InferenceCore
@@ -76,21 +76,45 @@ def _read_ahead(vid_reader, workers, ingest):
     return ReadAhead(vid_reader, workers=workers, getitem=lambda i: vid_reader.get(i, ingest=ingest))
 
 
-def _feed(vid_reader, dev, depth, read_workers, ingest, keep_u8=False) -> Window:
-    """The records of a video: decoded ahead on threads (eval_vos.py:92), then up to ``depth`` of them on the device ahead of the step
-    that takes them (uploaded as they enter the window, their deferred decode check made as they leave it).  keep_u8: the device-ingest
-    records keep their uint8 frame on the device (``info['image_u8']``: the device overlay of ``--visualize`` reads it)."""
-    return Window(_read_ahead(vid_reader, read_workers, ingest), lambda d: to_device(d, dev, defer_check=True, keep_u8=keep_u8), finish, depth)
+def _check_decode_batch(decode_batch, ingest_modes):
+    """decode_batch > 1 is the batch JPEG decode of 'device-decode'; in every other mode it is ignored (-> 1; the command line says so once)."""
+    decode_batch = int(decode_batch)
+    if decode_batch < 1:
+        raise ValueError(f'decode_batch must be at least 1, not {decode_batch}')
+    return decode_batch if all(m == 'device-decode' for m in ingest_modes) else 1
 
 
-def _take(window, dev, lookahead):
-    """The next frame of a feed -> (record, its mask on the device or None, its valid labels or None, hints or None).  The hints are
-    the frames of the following steps, already on the device: step(next_images=...) runs the image encoder over a window of them
-    (InferenceCore.prefetch_window); the SAME tensors come with the later records (the look-ahead matches frames by storage)."""
-    d = window.pop()
-    mask, valid = d.get('mask'), d.get('valid_labels')
-    hints = [x['rgb'] for x in window.queued] if (lookahead and window.queued) else None
-    return d, (mask.to(dev) if mask is not None else None), (valid.tolist() if valid is not None else None), hints
+def _feeds(vid_readers, dev, depth, read_workers, ingest, keep_u8s, decode_batch=1) -> List[Window]:
+    """The records of each reader: decoded ahead on threads (eval_vos.py:92), then up to ``depth`` of them on the device ahead of the
+    step that takes them (uploaded as they enter the window, their deferred decode check made as they leave it).  keep_u8s[k]: the
+    device-ingest records of reader k keep their uint8 frame on the device (``info['image_u8']``: the device overlay of ``--visualize``
+    reads it).  decode_batch = B > 1 ('device-decode'): the windows take B records at a time and fill TOGETHER -- one
+    ``to_device_many`` call, i.e. one upload and one chain of decode launches, for the B frames of every feed that is due."""
+    B = _check_decode_batch(decode_batch, [(ingest or rd.ingest) for rd in vid_readers])
+    if B == 1:
+        return [Window(_read_ahead(rd, read_workers, ingest), lambda d, k=k: to_device(d, dev, defer_check=True, keep_u8=k), finish, depth)
+                for rd, k in zip(vid_readers, keep_u8s)]
+    staging = PngStaging() if dev.type == 'cuda' else None            # pinned upload buffers of these feeds (one driver, one thread)
+
+    def upload_many(records, owners):
+        return to_device_many(records, dev, defer_check=True, keep_u8=[w.tag for w in owners], staging=staging)
+
+    feeds = [Window(_read_ahead(rd, read_workers, ingest), None, finish, depth, upload_many=upload_many, batch=B, tag=k, fill=False)
+             for rd, k in zip(vid_readers, keep_u8s)]
+    fill_together(feeds)
+    return feeds
+
+
+def _take(windows, dev, lookahead):
+    """The next frame of every feed -> per feed (record, its mask on the device or None, its valid labels or None, hints or None).  The
+    hints are the frames of the following steps, already on the device: step(next_images=...) runs the image encoder over a window of
+    them (InferenceCore.prefetch_window); the SAME tensors come with the later records (the look-ahead matches frames by storage)."""
+    taken = []
+    for window, d in zip(windows, pop_together(windows)):
+        mask, valid = d.get('mask'), d.get('valid_labels')
+        hints = [x['rgb'] for x in window.queued] if (lookahead and window.queued) else None
+        taken.append((d, (mask.to(dev) if mask is not None else None), (valid.tolist() if valid is not None else None), hints))
+    return taken
 
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
@@ -129,7 +153,7 @@ def _save(saver, prob, info, last_frame, save_all):
 
 
 def _frame_kw(saver, info) -> Dict:
-    """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feed(keep_u8=True)``)."""
+    """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feeds(keep_u8s=...)``)."""
     return {'image_u8': info.get('image_u8')} if saver.overlay == 'device' else {}
 
 
@@ -143,7 +167,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
     on_gpu = dev.type == 'cuda'
     first_mask_loaded = start > 0
     for ti in range(start, n):
-        taken = [_take(w, dev, lookahead) for w in feeds]
+        taken = _take(feeds, dev, lookahead)
         info = taken[0][0]['info']
         if any(d['info']['frame'] != info['frame'] or tuple(d['info']['shape']) != tuple(info['shape']) for d, *_ in taken):
             raise ValueError(f"process_video_multiscale: the readers disagree on frame {ti} ({[d['info']['frame'] for d, *_ in taken]})")
@@ -163,7 +187,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict:
+                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -177,9 +201,9 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
                    overlay=overlay)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
-        feed = _feed(vid_reader, network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
-                     keep_u8=saver.overlay == 'device')
-        _run_video([lambda: nullcontext(processor)], [feed], len(vid_reader), 0, stats,
+        feeds = _feeds([vid_reader], network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
+                       [saver.overlay == 'device'], decode_batch)
+        _run_video([lambda: nullcontext(processor)], feeds, len(vid_reader), 0, stats,
                    lambda probs, info, last: _save(saver, probs[0], info, last, save_all), dev=network.device, lookahead=lookahead)
     finally:
         saver.end()
@@ -188,7 +212,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict:
+                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -225,7 +249,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
     try:
         depth = (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1
         # (the first member's records carry the frame for the overlay: `save` gets its info)
-        feeds = [_feed(rd, network.device, depth, read_workers, ingest, keep_u8=(s == 0 and saver.overlay == 'device')) for s, rd in enumerate(vid_readers)]
+        feeds = _feeds(vid_readers, network.device, depth, read_workers, ingest, [s == 0 and saver.overlay == 'device' for s in range(S)], decode_batch)
         _run_video([lambda s=s: members.clip(s) for s in range(S)], feeds, n, 0, stats, save, dev=network.device, lookahead=lookahead)
     finally:
         saver.end()
@@ -244,7 +268,7 @@ def lockstep_key(vid_reader):
 
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> Dict[int, Dict]:
+                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
@@ -261,9 +285,9 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
     try:
-        feeds = [_feed(rd, dev, 16 if lookahead else 1, read_workers, ingest, keep_u8=savers[c].overlay == 'device') for c, rd in enumerate(vid_readers)]
+        feeds = _feeds(vid_readers, dev, 16 if lookahead else 1, read_workers, ingest, [sv.overlay == 'device' for sv in savers], decode_batch)
         for ti in range(T):
-            data, masks, valid, hints = (list(v) for v in zip(*[_take(w, dev, lookahead) for w in feeds]))
+            data, masks, valid, hints = (list(v) for v in zip(*_take(feeds, dev, lookahead)))
             any_mask = any(m is not None for m in masks)
             hint = None
             if all(h is not None for h in hints) and not any_mask and ti < T - 1:
@@ -315,6 +339,10 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES),
                     help="device: upload the decoded uint8 frames, ToTensor + antialiased resize on the GPU (cutie_amd/inference/data/device_ingest.py); "
                          "device-decode: upload the JPEG bytes and decode them on the GPU as well (baseline JPEG; other frames as 'device')")
+    ap.add_argument('--decode-batch', type=int, default=1,
+                    help='--ingest device-decode: decode this many frames of a clip (of every clip of a --lockstep group, of every scale '
+                         'of --sizes) through ONE chain of launches (RESIZE flags 256); the look-ahead windows grow by N - 1 frames.  '
+                         'Same results.  Default 1: a launch chain per frame.  Ignored in the other ingest modes')
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES),
                     help='device: the GPU resamples + argmaxes the result in one kernel and writes the PNG zlib stream; the host copies a few '
                          'KB per frame without blocking and only wraps them in PNG chunks (cutie_amd/inference/utils/results_utils.py)')
@@ -367,6 +395,8 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error('--score: long-id datasets (RGB masks) cannot be scored: J&F is counted on uint8 id planes')
     elif args.gt is not None or args.score_all_frames:
         ap.error('--gt and --score-all-frames belong to --score')
+    if getattr(args, 'decode_batch', 1) < 1:
+        ap.error('--decode-batch is at least 1')
     if args.sizes is not None:
         if len(set(args.sizes)) != len(args.sizes) or len(args.sizes) < 2:
             ap.error('--sizes takes at least two distinct values')
@@ -398,6 +428,11 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
     common = dict(dataset=args.dataset, visualize=args.visualize, visualize_output_root=path.join(args.output, 'Visualizations'),
                   save_scores=args.save_scores, score_output_root=path.join(args.output, 'Scores'), read_workers=args.read_workers,
                   egress=args.egress, save_all=not burst, overlay=getattr(args, 'overlay', 'host'))     # (no ingest=: the readers carry the mode)
+    decode_batch = int(getattr(args, 'decode_batch', 1))
+    if decode_batch > 1 and args.ingest != 'device-decode':
+        log.warning('--decode-batch %d only matters with --ingest device-decode; ignored', decode_batch)
+    elif decode_batch != 1:
+        common.update(decode_batch=decode_batch)
     score = bool(getattr(args, 'score', False))
     if score:
         common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames), gt_decode=args.gt_decode)

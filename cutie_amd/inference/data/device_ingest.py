@@ -5,7 +5,9 @@ host.  ``VideoReader(ingest='device')`` produces the records this module finishe
 
 ``ingest='device-decode'`` goes one step further: the record carries the parsed JPEG (inference/data/jpeg.py Packet), only its
 compressed bytes are uploaded, and the decode runs on the GPU as three more RESIZE stages (ABI 6, flags 8 / 16 / 32) in front of
-the same resize.  The uint8 frame equals PIL's, so the record equals the other modes' records.
+the same resize.  The uint8 frame equals PIL's, so the record equals the other modes' records.  ``jpegs_to_device`` / ``to_device_many``
+decode several frames through ONE chain of launches (the batch forms, RESIZE flags 256; ``--decode-batch``): one upload, one launch per
+pass over all frames.
 
 ``png_to_device`` does the same for mask PNGs (inference/data/png_packet.py; RESIZE flags 64 / 128, ABI 11, forms added): a batch of parsed files is
 uploaded in one copy and inflated and unfiltered in one launch per stage, one wave per image -- what the scorer's ``gt_decode='device'``
@@ -252,6 +254,119 @@ def png_to_device(packets: Sequence[P.Packet], device, stream=None, names: Optio
     return res, chk
 
 
+class JpegBatchCheck:
+    """The status blocks of one batch JPEG decode (int32 [N, 4] per image: error bits, sync rounds, serial segments), copied to host memory
+    behind the decode on its stream.  ``chk()`` waits for that copy only, then raises ValueError naming the first bad frame; ``chk(k)``
+    does the same for frame k alone (the drivers check a frame when it leaves the look-ahead window: a bad frame further on raises when
+    its own turn comes).  A frame that passed is counted in ``decode_stats`` once."""
+    __slots__ = ('status', 'event', 'names', 'seen', 'lock')
+
+    def __init__(self, status_dev: torch.Tensor, names: Sequence[str]):
+        self.names, self.seen, self.lock = list(names), [False] * len(names), threading.Lock()
+        if status_dev.device.type == 'cuda':
+            self.status = torch.empty(status_dev.shape, dtype=torch.int32, pin_memory=True)
+            self.status.copy_(status_dev, non_blocking=True)
+            self.event = torch.cuda.Event()
+            self.event.record()
+        else:
+            self.status, self.event = status_dev.clone(), None
+
+    def __call__(self, k: Optional[int] = None):
+        with self.lock:
+            todo = [j for j in (range(len(self.names)) if k is None else (k,)) if not self.seen[j]]
+            if not todo:
+                return
+            if self.event is not None:
+                self.event.synchronize()
+                self.event = None
+            st = self.status.numpy()
+            for j in todo:
+                self.seen[j] = True
+                err, rounds, serial = (int(v) for v in st[j, :3])
+                if err:
+                    what = 'bad decode table or packet header' if err & 4 else 'corrupt or truncated JPEG data'
+                    raise ValueError(f'{self.names[j] or "frame"}: {what} (GPU decode error bits {err:#x})')
+                with _stats_lock:
+                    decode_stats['frames'] += 1
+                    decode_stats['serial_segments'] += serial
+                    decode_stats['max_sync_rounds'] = max(decode_stats['max_sync_rounds'], rounds)
+
+    def one(self, k: int):
+        """The check of frame k as a callable of its own (what a record's ``decode_check`` holds)."""
+        return lambda: self(k)
+
+
+def jpegs_to_device(packets: Sequence[J.Packet], device, sizes_hw=None, stream=None, names: Optional[Sequence[str]] = None, check: bool = True,
+                    keep_u8: bool = False, staging: Optional[PngStaging] = None, guard: int = 0):
+    """Parsed JPEGs -> a list of f32 [3, h, w] contiguous frames on `device`, each equal to what ``jpeg_to_device`` returns for that packet
+    ((h, w) = sizes_hw[k], default the frame's own size).  ONE upload -- the table and the packets in one buffer, through pinned staging
+    with a non-blocking copy -- then ONE op list on `stream` (default: the current stream): the three decode stages in their batch forms
+    (RESIZE flags 8 / 16 / 32 with 256: one launch per pass over all images) and the per-frame RESIZE of every image, into buffers of this
+    call.  The uint8 frames have an allocation of their own, so a caller that keeps one of them does not pin work, coef and planes.
+    check=True: wait for the status blocks and raise ValueError naming the first bad frame (`names`, default the packets' files).
+    check=False: -> (frames, JpegBatchCheck); the caller calls the check (whole, or per frame) before it uses a frame's result.
+    keep_u8=True: the decoded uint8 [H, W, 3] frames join the result: -> (frames, u8s) | (frames, check, u8s).
+    staging: a PngStaging whose pinned buffers are used in turn (a slot is reused once its upload has run).  guard: that many bytes (a multiple of 16) of 0xA5 in front of and behind
+    every image in coef, planes and rgb (tests)."""
+    from ... import _lib
+    dev = torch.device(device)
+    on_gpu = dev.type == 'cuda'
+    if on_gpu and not _lib.has_jpeg_batch():
+        raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no batch JPEG decode); rebuild it.')
+    n = len(packets)
+    if n == 0:
+        raise ValueError('jpegs_to_device: no packet')
+    names = [pk.source for pk in packets] if names is None else list(names)
+    table, sz = O.OpList.jpeg_layout(packets, guard=guard)
+    head = -(-32 * n // 16) * 16
+    total = head + sz['packets']
+    ctx = torch.cuda.stream(stream) if (on_gpu and stream is not None) else nullcontext()
+    with ctx:
+        slot = None
+        if on_gpu and staging is not None:
+            host, slot = staging.take(total)
+        elif on_gpu:
+            host = torch.empty(total, dtype=torch.uint8).pin_memory()
+        else:
+            host = torch.empty(total, dtype=torch.uint8)
+        hv = host.numpy()
+        hv[:32 * n] = table.reshape(-1).view(np.uint8)
+        for k, pk in enumerate(packets):
+            o = head + int(table[k, 0])
+            hv[o:o + pk.buf.nbytes] = pk.buf
+        blob = host[:total].to(dev, non_blocking=True)
+        if slot is not None:
+            slot['event'].record()
+
+        def buf(name, dtype, fill):
+            if guard:
+                return torch.full((sz[name],), fill, dtype=dtype, device=dev)
+            return torch.empty(sz[name], dtype=dtype, device=dev)
+        work = torch.empty(sz['work'], dtype=torch.int32, device=dev)
+        coef, planes, rgb = buf('coef', torch.int16, -0x5A5B), buf('planes', torch.uint8, 0xA5), buf('rgb', torch.uint8, 0xA5)
+        status = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        tab_dev, pk_dev = blob[:32 * n].view(torch.int32), blob[head:]
+        ol = O.OpList(prio=False)
+        ol.jpeg_huff_batch(pk_dev, tab_dev, sz, status, n=n, work=work, coef=coef)
+        ol.jpeg_idct_batch(pk_dev, tab_dev, sz, status, n=n, coef=coef, planes=planes)
+        ol.jpeg_color_batch(pk_dev, tab_dev, sz, status, n=n, planes=planes, rgb=rgb)
+        outs, u8s = [], []
+        for k, pk in enumerate(packets):
+            H, W = pk.shape
+            h, w = (H, W) if (sizes_hw is None or sizes_hw[k] is None) else (int(sizes_hw[k][0]), int(sizes_hw[k][1]))
+            o = int(table[k, 4])
+            u8 = rgb[o:o + H * W * 3].view(H, W, 3)
+            u8s.append(u8)
+            outs.append(_resize(ol, u8, H, W, 3, h, w, 3 * W, dev))
+        ol.finalize()
+        ol.run()
+        chk = JpegBatchCheck(status, names)          # (not left in the staging slot: a slot that comes round must not raise for a frame
+    if check:                                        #  that is still queued -- the slot's event alone guards the pinned buffer)
+        chk()
+        return (outs, u8s) if keep_u8 else outs
+    return (outs, chk, u8s) if keep_u8 else (outs, chk)
+
+
 def frame_to_device(rgb_u8, device, size_hw=None, stream=None, keep_u8: bool = False):
     """uint8 [H, W, C] (numpy array or CPU tensor; rows may be padded, pixels packed) -> f32 [C, h, w] contiguous on `device`,
     (h, w) = size_hw (default (H, W): ToTensor only).  One synchronous uint8 copy, one RESIZE launch on `stream` (default: the
@@ -302,6 +417,35 @@ def to_device(record: Dict, device, stream=None, defer_check: bool = False, keep
     if keep_u8 and src.shape[2] == 3:
         record['info']['image_u8'] = src
     return record
+
+
+def to_device_many(records: Sequence[Dict], device, stream=None, defer_check: bool = True, keep_u8: bool = False,
+                   staging: Optional[PngStaging] = None) -> List[Dict]:
+    """``to_device`` for several records at once, in order: the 'device-decode' records among them (they hold ``jpeg``) go through ONE
+    ``jpegs_to_device`` call -- one upload, one chain of launches -- and every other record (host-path, ``rgb_u8``, a frame the parser
+    declined) through ``to_device`` as it is.  Every decoded record gets a ``decode_check`` that resolves its own frame of the shared
+    check, so ``finish(record)`` works unchanged; defer_check=False checks them all here.  keep_u8: one bool, or one per record (the
+    records of several feeds in one call)."""
+    records = list(records)
+    keep = [bool(keep_u8)] * len(records) if isinstance(keep_u8, (bool, int)) else [bool(v) for v in keep_u8]
+    batch = [k for k, r in enumerate(records) if 'jpeg' in r]
+    if batch:
+        pkts = [records[k].pop('jpeg') for k in batch]
+        infos = [records[k]['info'] for k in batch]
+        frames, chk, u8s = jpegs_to_device(pkts, device, [i.pop('rgb_shape') for i in infos], stream,
+                                           [i.get('path_to_image') or p.source for i, p in zip(infos, pkts)], check=False, keep_u8=True,
+                                           staging=staging)
+        for j, k in enumerate(batch):
+            records[k]['rgb'] = frames[j]
+            if keep[k]:
+                infos[j]['image_u8'] = u8s[j]
+            records[k]['decode_check'] = chk.one(j)
+    done = set(batch)
+    out = [r if k in done else to_device(r, device, stream, defer_check=defer_check, keep_u8=keep[k]) for k, r in enumerate(records)]
+    if not defer_check:
+        for r in out:
+            finish(r)
+    return out
 
 
 def finish(record: Dict) -> Dict:

@@ -50,12 +50,26 @@ class Window:
     every decode).  ``queued`` holds what is still waiting, in order; a caller builds its ``next_images`` hints from it -- the
     same objects arrive later through ``pop``, which is what the look-ahead of ``InferenceCore.step`` matches frames by."""
 
-    def __init__(self, records, upload: Callable, check: Callable, depth: int):
+    def __init__(self, records, upload: Callable, check: Callable, depth: int, upload_many: Optional[Callable] = None, batch: int = 1,
+                 tag=None, fill: bool = True):
+        """batch = B > 1: the records enter B at a time through ONE ``upload_many(records, owners)`` call (owners[i] = the window that
+        record i belongs to; ``tag`` is the caller's note on a window for that function) -- a refill happens when at least B places
+        are free or the source ends, and the depth grows by B - 1, so ``queued`` is never shorter at a pop than with batch = 1.  The
+        popped sequence is the same.  Several such windows fill in one call through ``pop_together``."""
         self.records, self.upload, self.check, self.depth = iter(records), upload, check, max(1, depth)
+        self.upload_many, self.batch, self.tag = upload_many, max(1, int(batch)), tag
+        if self.batch > 1:
+            if upload_many is None:
+                raise ValueError('Window: batch > 1 needs upload_many')
+            self.depth += self.batch - 1
         self.queued = deque()
-        self._fill()
+        self.dry = False                     # (batch > 1) the source has ended
+        if fill:                             # (fill=False: the caller fills it with others, fill_together)
+            self._fill()
 
     def _fill(self):
+        if self.batch > 1:
+            return fill_together([self])
         while len(self.queued) < self.depth:
             try:
                 record = next(self.records)
@@ -68,3 +82,42 @@ class Window:
         record = self.check(self.queued.popleft())
         self._fill()
         return record
+
+    def _group(self):
+        """(batch > 1) The records that are due to enter now: ``batch`` of them once that many places are free, fewer when the source
+        ends there; [] while the window is full enough or dry."""
+        group = []
+        if not self.dry and self.depth - len(self.queued) >= self.batch:
+            for _ in range(self.batch):
+                try:
+                    group.append(next(self.records))
+                except StopIteration:
+                    self.dry = True
+                    break
+        return group
+
+
+def fill_together(windows):
+    """Fill batched windows in ONE ``upload_many`` call per round: the groups that are due in each of them go up together (the feeds of a
+    lock-step group, the scales of a multi-scale run: C x B frames per call).  A window that is full or dry takes no part; the call
+    of the first window with records is used -- windows filled together share one uploader."""
+    while True:
+        groups = [(w, w._group()) for w in windows]
+        owners = [w for w, g in groups for _ in g]
+        if not owners:
+            return
+        uploaded = owners[0].upload_many([r for _, g in groups for r in g], owners)
+        for w, record in zip(owners, uploaded):
+            w.queued.append(record)
+
+
+def pop_together(windows):
+    """``pop`` of every window, in order -> their records.  Batched windows are filled again in one joint call after all have popped
+    (fill_together); with batch = 1 this is ``[w.pop() for w in windows]``."""
+    if all(w.batch == 1 for w in windows):
+        return [w.pop() for w in windows]
+    if any(w.batch == 1 for w in windows):
+        raise ValueError('pop_together: the windows are all batched or none is')
+    records = [w.check(w.queued.popleft()) for w in windows]
+    fill_together(windows)
+    return records

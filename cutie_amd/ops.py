@@ -1134,6 +1134,78 @@ class OpList:
         return self._jpeg(32, pkt, planes=planes, rgb=rgb)
 
     @staticmethod
+    def jpeg_layout(packets, rounds=JPEG_SYNC_ROUNDS, guard=0):
+        """The buffers of one batch JPEG decode over ``packets`` (inference/data/jpeg.py Packet) -> (table int32 [N, 8], sizes).  Table row
+        (include/cutie_hip.h, ABI 11, forms added): the offsets of the image's packet (bytes, a multiple of 16), work area (int32 words, 8-byte
+        aligned), coefficients (int16 elements, 16-byte aligned), planes (bytes, 8-byte aligned) and rgb (bytes, 16-byte aligned), its
+        packet bytes, its rgb row stride (3 W), 0.  ``sizes``: the element counts of the buffers -- 'packets' uint8, 'work' int32, 'coef'
+        int16, 'planes' uint8, 'rgb' uint8 (per image jpeg.stage_sizes, rounded up to the alignment) -- the largest 'max_chunk' /
+        'max_seg' / 'max_block' / 'max_pix' of the batch (the grids) and 'rounds'.  ``guard`` bytes (a multiple of 16) lie in front of
+        and behind every image's region in coef, planes and rgb.  Every buffer stays below 2^31 bytes (ValueError)."""
+        from .inference.data import jpeg as J
+        if guard < 0 or guard % 16:
+            raise ValueError('jpeg batch: guard is a multiple of 16 bytes')
+        table = np.zeros((len(packets), 8), dtype=np.int32)
+        po = wo = co = plo = ro = 0
+        mx = [0, 0, 0, 0]
+        for k, pkt in enumerate(packets):
+            sz, h = J.stage_sizes(pkt, rounds), pkt.hdr
+            co += guard // 2
+            plo += guard
+            ro += guard
+            W = int(h[J.HDR_W])
+            row = (po, wo, co, plo, ro, pkt.buf.nbytes, 3 * W, 0)
+            po += -(-pkt.buf.nbytes // 16) * 16
+            wo += -(-sz['work'] // 2) * 2
+            co += -(-(sz['coef'] + guard // 2) // 8) * 8
+            plo += -(-(sz['planes'] + guard) // 8) * 8
+            ro += -(-(sz['rgb'] + guard) // 16) * 16
+            if max(po, 4 * wo, 2 * co, plo, ro) >= 1 << 31:
+                raise ValueError('jpeg batch: the buffers of one launch stay below 2^31 bytes')
+            table[k] = row
+            mx = [max(a, int(b)) for a, b in zip(mx, (h[J.HDR_NCHUNK], h[J.HDR_NSEG], h[J.HDR_NBLOCK], int(h[J.HDR_H]) * W))]
+        return table, {'packets': po, 'work': wo, 'coef': co, 'planes': plo, 'rgb': ro, 'rounds': rounds,
+                       'max_chunk': mx[0], 'max_seg': mx[1], 'max_block': mx[2], 'max_pix': mx[3]}
+
+    def _jpeg_batch(self, flags, packets, table, sizes, status, *, n, work=None, coef=None, planes=None, rgb=None):
+        """RESIZE flags 8 / 16 / 32 with 256 (include/cutie_hip.h, ABI 11, forms added): one stage of the JPEG decode of ``n`` packets in the
+        uint8 buffer ``packets``, laid out by ``table`` / ``sizes`` (jpeg_layout); every stage gets the same table, sizes and status."""
+        # as _png: the forms came without a new ABI number, and a library from before would read the descriptor as a one-frame decode
+        if not getattr(_lib._executor, 'is_mock', False):
+            try:
+                known = _lib.has_jpeg_batch()
+            except _lib.HipLibraryError:
+                known = True
+            if not known:
+                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no batch JPEG decode, RESIZE flags 256); rebuild it.')
+        if not 1 <= n <= 65535:
+            raise ValueError(f'jpeg batch: {n} images, 1 .. 65535')
+        if table.dtype != torch.int32 or table.numel() < 8 * n or not table.is_contiguous():
+            raise ValueError(f'jpeg batch: table is a contiguous int32 [{n}, 8]')
+        if status.dtype != torch.int32 or status.numel() < 4 * n or not status.is_contiguous():
+            raise ValueError(f'jpeg batch: status is a contiguous int32 [{n}, 4]')
+        for name, t, dt in (('packets', packets, torch.uint8), ('work', work, torch.int32), ('coef', coef, torch.int16),
+                            ('planes', planes, torch.uint8), ('rgb', rgb, torch.uint8)):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.numel() < sizes[name]):
+                raise ValueError(f'jpeg batch: {name} is a contiguous {dt} buffer of at least {sizes[name]} elements')
+        ints = [n] + [sizes[k] for k in ('packets', 'work', 'coef', 'planes', 'rgb', 'rounds', 'max_chunk', 'max_seg', 'max_block', 'max_pix')]
+        return self.add(RESIZE, flags | 256, ints, [], [packets, table, work, coef, planes, rgb, status])
+
+    def jpeg_huff_batch(self, packets, table, sizes, status, *, n, work, coef):
+        """Stage 1 over ``n`` images, one launch per pass: -> coef int16 (per image [nblock, 64] at its table offset), status int32 [n, 4],
+        cleared by the launch: per image error bits (1 bad code, 2 data ends early, 4 bad table or header: the image is skipped), sync
+        rounds, serial segments.  work int32, 8-byte aligned; coef 16-byte aligned."""
+        return self._jpeg_batch(8, packets, table, sizes, status, n=n, work=work, coef=coef)
+
+    def jpeg_idct_batch(self, packets, table, sizes, status, *, n, coef, planes):
+        """Stage 2 over ``n`` images in one launch: -> planes uint8 (per image at its table offset)."""
+        return self._jpeg_batch(16, packets, table, sizes, status, n=n, coef=coef, planes=planes)
+
+    def jpeg_color_batch(self, packets, table, sizes, status, *, n, planes, rgb):
+        """Stage 3 over ``n`` images in one launch: -> rgb uint8 (per image [H, W, 3] packed at its table offset)."""
+        return self._jpeg_batch(32, packets, table, sizes, status, n=n, planes=planes, rgb=rgb)
+
+    @staticmethod
     def png_layout(packets, guard=0):
         """The buffers of one PNG decode launch over ``packets`` (inference/data/png_packet.py Packet) -> (table int32 [N, 4] = per image the
         byte offset of its packet, of its inflated rows and of its pixels, 0; packet bytes, inflate bytes, output bytes).  Packets and

@@ -44,7 +44,7 @@ from PIL import Image
 from .config import default_config
 from .eval_vos import timed_step
 from .inference.data import jpeg
-from .inference.data.device_ingest import frame_to_device, jpeg_to_device
+from .inference.data.device_ingest import PngStaging, frame_to_device, jpeg_to_device, jpegs_to_device
 from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
@@ -151,8 +151,10 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
-                  layer=None) -> Dict:
-    """gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
+                  layer=None, decode_batch: int = 1) -> Dict:
+    """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
+    (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
+    gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
     joins the result.  vis_modes / soft_masks / alpha_matte / target_objects / layer: ResultSaver's (the module docstring); 'folders' of
     the result names the folders they wrote."""
     if ingest not in INGEST_MODES:
@@ -170,6 +172,21 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             return (f.to(dev) if ingest == 'host' else frame_to_device(f, dev)), None
         frame, u8 = frame_to_device(f, dev, keep_u8=True)
         return frame, None, u8
+
+    if decode_batch < 1:
+        raise ValueError(f'decode_batch must be at least 1, not {decode_batch}')
+    batch = decode_batch if ingest == 'device-decode' else 1
+    staging = PngStaging() if (batch > 1 and dev.type == 'cuda') else None
+
+    def upload_many(frames, owners):
+        """``upload`` for the frames that enter the window together: the parsed JPEGs among them are decoded by ONE chain of launches"""
+        items = [None] * len(frames)
+        ks = [k for k, f in enumerate(frames) if isinstance(f, jpeg.Packet)]
+        if ks:
+            outs, chk, u8s = jpegs_to_device([frames[k] for k in ks], dev, check=False, keep_u8=True, staging=staging)
+            for j, k in enumerate(ks):
+                items[k] = (outs[j], chk.one(j), u8s[j]) if want_u8 else (outs[j], chk.one(j))
+        return [upload(f) if item is None else item for f, item in zip(frames, items)]
 
     def checked(item):
         """-> (frame, its uint8 twin on the device or None)"""
@@ -213,7 +230,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             frame = src.read(int(name[:-4]))
             if frame is None:
                 break
-            processor.step(checked(upload(frame))[0], one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
+            item = upload(frame) if batch == 1 else upload_many([frame], None)[0]
+            processor.step(checked(item)[0], one_hot_planes(index_mask(name), num_objects, dev), idx_mask=False,
                            force_permanent=True)
         # 2. the whole video
         scorer = None
@@ -225,7 +243,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             alpha_matte=alpha_matte, target_objects=target_objects, layer=layer)
         total, n, cleanups = 0.0, 0, 0
         try:
-            ahead = Window(src, upload, checked, 1)           # the next frame is on the device while this one is stepped
+            # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
+            ahead = Window(src, upload, checked, 1) if batch == 1 else Window(src, None, checked, 1, upload_many=upload_many, batch=batch)
             while ahead.queued:
                 frame, u8 = ahead.pop()
                 name = f'{n:07d}.png'
@@ -262,6 +281,8 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--mem_cleanup_ratio', type=float, default=-1)
     ap.add_argument('--model', default='base', choices=['base', 'small'], help='cutie/config/model/{base,small}.yaml')
     ap.add_argument('--ingest', default='host', choices=list(INGEST_MODES), help='device: upload uint8 frames, ToTensor on the GPU; device-decode: decode JPEG frames on the GPU too')
+    ap.add_argument('--decode-batch', type=int, default=1,
+                    help='--ingest device-decode: decode this many frames through one chain of launches (default 1: one chain per frame; same results)')
     ap.add_argument('--egress', default='host', choices=list(EGRESS_MODES), help='device: the GPU writes the PNG streams of the masks (ResultSaver(egress=...))')
     ap.add_argument('--vis', nargs='+', default=[], choices=list(VIS_MODES), metavar='MODE',
                     help=f'visualisations written as OUT/visualization/MODE/*.jpg, composed and encoded on the GPU: {", ".join(VIS_MODES)}')
@@ -280,6 +301,11 @@ def main():
     args = ap.parse_args()
     if 'layer' in args.vis and not args.layer:
         ap.error('--vis layer needs --layer FILE')
+    if args.decode_batch < 1:
+        ap.error('--decode-batch is at least 1')
+    if args.decode_batch > 1 and args.ingest != 'device-decode':
+        print(f'--decode-batch {args.decode_batch} only matters with --ingest device-decode; ignored')
+        args.decode_batch = 1
     from .model.cutie import CUTIE
     cfg = video_config(model=args.model, mem_every=args.mem_every, max_internal_size=args.max_internal_size)
     net = CUTIE(cfg).cuda().eval()
@@ -289,7 +315,8 @@ def main():
         print('No model weights loaded. Are you sure about this?')
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
                       mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
-                      vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer)
+                      vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
+                      decode_batch=args.decode_batch)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

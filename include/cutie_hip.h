@@ -487,6 +487,31 @@ enum {
      *  flags&32 colour: libjpeg's fancy upsampling (h2v1 / h2v2 where the chroma width is > 2, h1v2 always; else replication) and its
      *    fixed-point YCbCr -> RGB tables (SCALEBITS 16); one component is replicated -> p5 = uint8 [H, W, 3], row stride i11 bytes:
      *    the source of RESIZE flags 4 / 6.
+     * ABI 11, forms added (the number stays 11; cutie_hip_build_flags() bit 2, value 4, says the forms are present -- a library from before
+     *    would read such a descriptor as a one-frame decode, so the callers ask first: cutie_amd/_lib.py has_jpeg_batch) -- flags&256
+     *    "batch": the stages above (flags 8 / 16 / 32, any of them, in that order; every other flag is an error) over N images, every pass
+     *    ONE launch over all of them (device_ingest.jpegs_to_device, --decode-batch): a frame's Huffman passes take about as long for 16
+     *    frames as for one, so a window of frames pays the chain once.
+     *    i: 0 N images (1 .. 65535)  1 bytes of p0  2 int32 words of p2  3 int16 elements of p3  4 bytes of p4  5 bytes of p5
+     *       6 sync rounds  7 / 8 / 9 / 10 the largest chunk / segment / block / pixel (H * W) count of the batch: the grids.
+     *    p0 = packets uint8: the unchanged packets of jpeg.py, each starting at a multiple of 16.  p1 = table int32 [N][8], per image:
+     *    0 byte offset of its packet in p0 (multiple of 16)  1 int32-word offset of its work area in p2 (even: 8-byte aligned)  2 int16-element
+     *    offset of its coefficient blocks in p3 (multiple of 8: 16-byte aligned)  3 byte offset of its planes in p4 (multiple of 8)
+     *    4 byte offset of its rgb in p5 (multiple of 16)  5 its packet bytes  6 its rgb row stride in bytes (>= 3 W)  7 zero.  Every other
+     *    geometry is read from the image's own packet header.  p2 = work int32 (8-byte aligned; per image 10 * chunks + (i6 + 1) *
+     *    segments words, as above), p3 = coef int16 (16-byte aligned), p4 = planes uint8 (8-byte aligned), p5 = rgb uint8 (16-byte aligned),
+     *    p6 = status int32 [N][4]: row k means for image k what status[4] means above, cleared by the launch with flags&8 (one memset;
+     *    the per-round flags and the coefficients of all images are cleared by one kernel -- their regions lie apart -- so the number
+     *    of memsets does not depend on N).  p0, p1, p6 16-byte aligned.  ops.py OpList.jpeg_layout lays the buffers out.
+     *    Table and headers are device data: every kernel checks the image's row and header against i1 .. i10 before it reads or writes
+     *    anything else of the image -- the magic word and the header's byte count against the row; every section offset plus its size
+     *    inside the packet; the counts (components 1 | 3, 1 .. 10 blocks per MCU, 1 .. 6 tables, chunk bits >= 64, sampling 1 | 2) and
+     *    chunks / segments / blocks / pixels against i7 .. i10; offsets plus sizes inside each buffer and their alignment; and 10 * chunks
+     *    + (i6 + 1) * segments against the words between the row's work offset and the next row's (i2 for the last row), i.e. the header's
+     *    chunk count against what the host laid out.  An image that fails gets error bit 4 ("bad table or header") in its status[0] and
+     *    every stage skips it; the other images are not affected, and no read or write leaves an image's own extents whatever the
+     *    entropy data holds (the section tables inside a packet are the parser's, as in the one-frame form).  Grids: the image is
+     *    blockIdx.y (the scan: one workgroup per image), sized by i7 .. i10; workgroups past an image's own count return.
      * ABI 11, forms added (the number stays 11; cutie_hip_build_flags() bit 1 says the forms are present -- a library from before would run
      *    such a descriptor as a plain RESIZE, so the callers ask first) -- mask PNGs decoded on the GPU (SequenceScorer gt_decode='device',
      *    score_masks --decode device; kernels in png_dec.hip, their serial core in png_inflate_core.h; the Python model: tests/png_dec_ref.py):
@@ -561,7 +586,9 @@ const char* cutie_hip_last_error(void);
 int cutie_hip_abi_version(void);
 int cutie_op_struct_size(void);
 /* bit 0: the library was built with -DCUTIE_DIAG (make DIAG=1): measured-and-lost kernel variants (ATTN_P2Q flags&32) are present.
- * The product library returns 0 and rejects those descriptors. */
+ * The product library returns 0 and rejects those descriptors.
+ * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
+ * JPEG decode stages, are present (both came without a new ABI number). */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

@@ -6,6 +6,9 @@ the GPU pays.
                                                               # sync rounds / serial segments, eval_vos wall-clock frames/s per mode
     python tools/ingest_probe.py decode [--frames 40]         # only the JPEG decodes at 480p / 720p / 1080p, for
                                                               # rocprofv3 --kernel-trace --stats (per-stage kernel times)
+        [--batch 1 4 8 16]                                    # ... the same frames N per call: 1 = the one-frame forms (jpeg_to_device),
+                                                              # N > 1 = the batch forms (jpegs_to_device, RESIZE flags 256)
+    python tools/ingest_probe.py gpu --decode-batch 4 8 16    # ... the eval_vos legs also with 'device-decode' and --decode-batch N
     [--out FILE.md]                                           # also append the markdown table to FILE
 
 Synthetic JPEG folders (smooth random content, quality 90) are generated in a temporary directory.  The eval_vos numbers are
@@ -71,36 +74,46 @@ def cpu_part(frames):
     return rows
 
 
-def decode_part(frames, rows=None):
+def decode_part(frames, rows=None, batches=(1,)):
     """The GPU JPEG decode of one synthetic frame per size, `frames` times after a warm-up: us per frame (events, packet upload
-    included), and the sync statistics of the last decode."""
+    included), and the sync statistics of the last decode.  batches: frames per call -- 1 is jpeg_to_device (the one-frame forms),
+    N > 1 is jpegs_to_device over N copies of the frame (the batch forms), frames // N calls."""
     from cutie_amd.inference.data import device_ingest as D
     from cutie_amd.inference.data import jpeg as J
     rows = rows if rows is not None else []
-    rows += ['| JPEG decode (device_ingest.jpeg_to_device, native size) | bytes | chunks | us per frame (events) | sync rounds | serial segments |',
-             '|---|---|---|---|---|---|']
+    rows += ['| JPEG decode (device_ingest.jpeg_to_device / jpegs_to_device, native size) | frames per call | bytes | chunks | us per frame (events) | sync rounds | serial segments |',
+             '|---|---|---|---|---|---|---|']
     with tempfile.TemporaryDirectory() as root:
         for tag, (h, w, _) in SIZES.items():
             make_video(root, tag, 1, h, w, seed=3)
             pkt, why = J.parse_file(os.path.join(root, 'JPEGImages', tag, '00000.jpg'))
             assert pkt is not None, why
-            for _ in range(5):
-                D.jpeg_to_device(pkt, 'cuda', stream=torch.cuda.current_stream())
-            torch.cuda.synchronize()
-            stats0 = dict(D.decode_stats)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(frames):
-                D.jpeg_to_device(pkt, 'cuda', stream=torch.cuda.current_stream())
-            e1.record()
-            torch.cuda.synchronize()
-            serial = D.decode_stats['serial_segments'] - stats0['serial_segments']
-            rows.append(f'| {w}x{h} | {pkt.buf.nbytes} | {int(pkt.hdr[J.HDR_NCHUNK])} | {e0.elapsed_time(e1) / frames * 1e3:.1f} | '
-                        f'{D.decode_stats["max_sync_rounds"]} | {serial} |')
+            for B in batches:
+                staging = D.PngStaging()
+
+                def call():
+                    if B == 1:
+                        D.jpeg_to_device(pkt, 'cuda', stream=torch.cuda.current_stream())
+                    else:
+                        D.jpegs_to_device([pkt] * B, 'cuda', stream=torch.cuda.current_stream(), staging=staging)
+                calls = max(1, frames // B)
+                for _ in range(5):
+                    call()
+                torch.cuda.synchronize()
+                stats0 = dict(D.decode_stats)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    call()
+                e1.record()
+                torch.cuda.synchronize()
+                serial = D.decode_stats['serial_segments'] - stats0['serial_segments']
+                rows.append(f'| {w}x{h} | {B} | {pkt.buf.nbytes} | {int(pkt.hdr[J.HDR_NCHUNK])} | {e0.elapsed_time(e1) / (calls * B) * 1e3:.1f} | '
+                            f'{D.decode_stats["max_sync_rounds"]} | {serial} |')
     return rows
 
 
-def gpu_part(frames):
+def gpu_part(frames, decode_batches=()):
     from cutie_amd import ops as O
     from cutie_amd.config import default_config
     from cutie_amd.eval_vos import process_video, process_videos_lockstep
@@ -130,8 +143,8 @@ def gpu_part(frames):
         rows.append(f'| RESIZE flags {int(ol.arr["flags"][0])} | {W}x{H} -> {OW}x{OH} | {e0.elapsed_time(e1) / 200 * 1e3:.1f} |')
     rows.append('')
     decode_part(frames, rows)
-    rows += ['', '| eval_vos (1280x720, --size 480, 4 videos) | ingest | frames | wall s | wall frames/s | step-only frames/s |',
-             '|---|---|---|---|---|---|']
+    rows += ['', '| eval_vos (1280x720, --size 480, 4 videos) | ingest | decode batch | frames | wall s | wall frames/s | step-only frames/s |',
+             '|---|---|---|---|---|---|---|']
     net = CUTIE(default_config()).cuda().eval()
     net.load_weights(make_state_dict(seed=0))
     cfg = default_config()
@@ -139,22 +152,23 @@ def gpu_part(frames):
         for v in range(4):
             make_video(root, f'v{v}', frames, 720, 1280, seed=10 + v)
         for lockstep in (1, 4):
-            for mode in MODES + MODES:                                     # each mode twice: the first pass warms plans and allocator
+            legs = [(m, 1) for m in MODES] + [('device-decode', B) for B in decode_batches if B > 1]
+            for mode, B in legs + legs:                                    # each leg twice: the first pass warms plans and allocator
                 ds = VOSTestDataset(os.path.join(root, 'JPEGImages'), os.path.join(root, 'Annotations'), use_all_masks=False, size=480, ingest=mode)
                 rds = list(ds.get_datasets())
-                out = os.path.join(root, f'out_{mode}_{lockstep}')
+                out = os.path.join(root, f'out_{mode}_{B}_{lockstep}')
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 with torch.inference_mode():
                     if lockstep == 1:
-                        st = [process_video(net, cfg, rd, out) for rd in rds]
+                        st = [process_video(net, cfg, rd, out, decode_batch=B) for rd in rds]
                     else:
-                        st = list(process_videos_lockstep(net, cfg, rds, out).values())
+                        st = list(process_videos_lockstep(net, cfg, rds, out, decode_batch=B).values())
                 torch.cuda.synchronize()
                 wall = time.perf_counter() - t0
                 n = sum(s['frames'] for s in st)
                 step = sum(s['seconds'] for s in st)
-                rows.append(f'| --lockstep {lockstep} | {mode} | {n} | {wall:.2f} | {n / wall:.0f} | {n / max(step, 1e-9):.0f} |')
+                rows.append(f'| --lockstep {lockstep} | {mode} | {B} | {n} | {wall:.2f} | {n / wall:.0f} | {n / max(step, 1e-9):.0f} |')
     return rows
 
 
@@ -163,8 +177,18 @@ def main():
     ap.add_argument('part', choices=['cpu', 'gpu', 'decode'])
     ap.add_argument('--frames', type=int, default=None)
     ap.add_argument('--out')
+    ap.add_argument('--batch', type=int, nargs='+', default=[1], help='decode: frames per call (1: the one-frame forms)')
+    ap.add_argument('--decode-batch', type=int, nargs='+', default=[], help="gpu: eval_vos legs with 'device-decode' and this decode_batch")
     a = ap.parse_args()
-    rows = {'cpu': cpu_part, 'gpu': gpu_part, 'decode': decode_part}[a.part](a.frames or (24 if a.part == 'cpu' else 40))
+    if min(a.batch + a.decode_batch) < 1:
+        ap.error('--batch / --decode-batch are at least 1')
+    frames = a.frames or (24 if a.part == 'cpu' else 40)
+    if a.part == 'cpu':
+        rows = cpu_part(frames)
+    elif a.part == 'gpu':
+        rows = gpu_part(frames, tuple(a.decode_batch))
+    else:
+        rows = decode_part(frames, batches=tuple(a.batch))
     text = '\n'.join(rows) + '\n'
     print(text)
     if a.out:

@@ -74,6 +74,13 @@ def has_jpeg_batch():
     return bool(load().cutie_hip_build_flags() & 4)
 
 
+def has_mixed_lockstep():
+    """Does the loaded library know the mixed forms of the lock-step ops (clips with different object counts: UPSAMPLE2X_ADD i6,
+    UP4_SOFTMAX i5, ATTN_Q2P i10, STEM i10, COPY2D i4)?  Added without a new ABI number; a library from before would ignore the counts word
+    and run the uniform form, so LockstepCores(mixed_objects=True) asks first."""
+    return bool(load().cutie_hip_build_flags() & 8)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

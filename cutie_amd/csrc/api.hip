@@ -131,8 +131,9 @@ const char* cutie_hip_last_error(void) { return g_err; }
 int cutie_hip_abi_version(void) { return 11; }
 int cutie_op_struct_size(void) { return (int)sizeof(cutie_op); }
 int cutie_hip_build_flags(void) {
-    // bit 1: RESIZE flags 64 / 128, the PNG decode stages; bit 2: RESIZE flags 256, the batch forms of the JPEG decode (ABI 11, forms added)
-    const int forms = 2 | 4;
+    // bit 1: RESIZE flags 64 / 128, the PNG decode stages; bit 2: RESIZE flags 256, the batch forms of the JPEG decode (ABI 11, forms added);
+    // bit 3: the mixed forms of the lock-step ops (clips with different object counts)
+    const int forms = 2 | 4 | 8;
 #ifdef CUTIE_DIAG
     return forms | 1;
 #else

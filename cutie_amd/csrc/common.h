@@ -78,6 +78,39 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// Clips in lock step with DIFFERENT object counts (the "mixed" forms, include/cutie_hip.h): the counts of up to 8 clips of 1 .. 7 objects
+// as 3-bit fields of one 24-bit word, clip c at bits 3c .. 3c + 2, a zero field ends the list.  Everything a launch needs per clip follows
+// from the prefix sums over the fields (uniform scalar arithmetic wherever the clip is block-uniform).
+__host__ __device__ __forceinline__ int mixed_count(unsigned word, int clip) { return (int)((word >> (3 * clip)) & 7u); }
+// the first object of clip `clip` = the sum of the counts in front of it
+__host__ __device__ __forceinline__ int mixed_start(unsigned word, int clip) {
+    int s = 0;
+    for (int c = 0; c < clip; ++c) s += mixed_count(word, c);
+    return s;
+}
+// the clip that holds object b, and that clip's first object (b below the sum of the counts)
+__host__ __device__ __forceinline__ int mixed_clip_of(unsigned word, int b, int& start) {
+    int c = 0, s = 0;
+#pragma unroll
+    for (int q = 0; q < 7; ++q) {
+        const int n = mixed_count(word, c);
+        const bool past = b >= s + n;
+        s += past ? n : 0;
+        c += past ? 1 : 0;
+    }
+    start = s;
+    return c;
+}
+// host side: number of clips and objects of a word (0 clips: not a valid word -- an empty list, or bits above the 24)
+static inline int mixed_clips(unsigned word, int* objects) {
+    int n = 0, total = 0;
+    if (word >> 24) { *objects = 0; return 0; }
+    while (n < 8 && mixed_count(word, n)) total += mixed_count(word, n++);
+    if (n < 8 && (word >> (3 * n))) { *objects = 0; return 0; }      // a count behind the end of the list
+    *objects = total;
+    return n;
+}
+
 // launchers implemented in the .hip files; all return hipError_t as int
 int launch_conv(const cutie_op* op, hipStream_t s);
 int launch_elementwise(const cutie_op* op, hipStream_t s);   // everything in elementwise.hip

@@ -73,6 +73,8 @@ __device__ __forceinline__ void up_coord(int o, int n_in, float scale, int& i0, 
 }
 
 // Kg > 0 (clips in lock step): the objects come in groups of Kg, group q adds the skip map at skip + q * gstride pixels (Kg = 0: one map for all)
+// MIXED (clips with different object counts): Kg holds the counts word (common.h), the group of object b comes from its prefix sums
+template <bool MIXED = false>
 __global__ void upsample2x_add_kernel(const uint4* __restrict__ g, const uint4* __restrict__ skip, uint4* __restrict__ y,
                                       int B, int h, int w, int C8, int Kg, long gstride, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(1);               // CUTIE_F_PRIO: a launch of the frame's critical path (the plan decides, ops.OpList.prio)
@@ -88,7 +90,10 @@ __global__ void upsample2x_add_kernel(const uint4* __restrict__ g, const uint4* 
     const uint4* gb = g + (long)b * h * w * C8;
     uint4 v00 = gb[((long)y0 * w + x0) * C8 + c], v01 = gb[((long)y0 * w + x1) * C8 + c];
     uint4 v10 = gb[((long)y1 * w + x0) * C8 + c], v11 = gb[((long)y1 * w + x1) * C8 + c];
-    uint4 sk = skip[((Kg > 0 ? (b / Kg) * gstride : 0l) + (long)oy * OW + ox) * C8 + c];
+    long grp;
+    if (MIXED) { int st; grp = mixed_clip_of((unsigned)Kg, b, st); }
+    else grp = Kg > 0 ? b / Kg : 0;
+    uint4 sk = skip[(grp * gstride + (long)oy * OW + ox) * C8 + c];
     const uint32_t* a = &v00.x; const uint32_t* bq = &v01.x; const uint32_t* cq = &v10.x; const uint32_t* d = &v11.x;
     const uint32_t* s = &sk.x;
     float w00 = (1.f - ly) * (1.f - lx), w01 = (1.f - ly) * lx, w10 = ly * (1.f - lx), w11 = ly * lx;
@@ -659,6 +664,28 @@ __device__ __forceinline__ void up4_four(const float* __restrict__ lg, int Krt, 
     }
 }
 
+// The body of up4_softmax_fused4_kernel below for ONE clip of the mixed form (lg / prob / lup point at the clip's planes): the same statements,
+// kept apart from the kernel so that the uniform instantiations stay what they were, register for register.
+template <int PMAX, int KC>
+__device__ __forceinline__ void up4_fused4_body(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup, int Krt, int h, int w) {
+    const int K = KC > 0 ? KC : Krt;
+    const int OH = 4 * h, OW = 4 * w;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;             // (oy, j): output pixels (oy, 4j .. 4j + 3)
+    if (idx >= (long)OH * w) return;
+    const int j = idx % w, oy = idx / w;
+    const long OHW = (long)OH * OW;
+    float out[PMAX][4];
+    float lo[PMAX][4];
+    up4_four<PMAX, KC>(lg, K, h, w, oy, j, out, lo);
+    const long base = (long)oy * OW + 4 * j;
+#pragma unroll
+    for (int p = 0; p < PMAX; ++p)
+        if (p <= K) {
+            if (lup) *reinterpret_cast<float4*>(lup + p * OHW + base) = make_float4(lo[p][0], lo[p][1], lo[p][2], lo[p][3]);
+            *reinterpret_cast<float4*>(prob + p * OHW + base) = make_float4(out[p][0], out[p][1], out[p][2], out[p][3]);
+        }
+}
+
 template <int PMAX, int KC = 0>
 __global__ __launch_bounds__(256) void up4_softmax_fused4_kernel(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup,
                                                                  int Krt, int h, int w, int prio) {
@@ -686,11 +713,96 @@ __global__ __launch_bounds__(256) void up4_softmax_fused4_kernel(const float* __
         }
 }
 
+// Mixed form (clips in lock step with different object counts, `counts` = their 3-bit fields): the clip blockIdx.y has K_c objects and its
+// planes start behind those of the clips in front (start_c logit planes in, start_c + c probability planes out).  One block-uniform
+// branch into the body instantiated for K_c: every clip runs exactly the code of its one-clip launch.
+#define UP4_MIXED_SWITCH(BODY) switch (Kc) { case 1: BODY(1); break; case 2: BODY(2); break; case 3: BODY(3); break; case 4: BODY(4); break; \
+                                             case 5: BODY(5); break; case 6: BODY(6); break; default: BODY(7); break; }
+template <int PMAX>
+__global__ __launch_bounds__(256) void up4_softmax_fused4_mixed_kernel(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup,
+                                                                       unsigned counts, int h, int w, int prio) {
+    if (prio) __builtin_amdgcn_s_setprio(1);
+    const int cl = blockIdx.y, Kc = mixed_count(counts, cl), st = mixed_start(counts, cl);
+    const long OHW = (long)16 * h * w;
+    lg += (long)st * h * w; prob += (long)(st + cl) * OHW;
+    if (lup) lup += (long)(st + cl) * OHW;
+#define UP4_BODY_(KC) up4_fused4_body<PMAX, KC>(lg, prob, lup, KC, h, w)
+    UP4_MIXED_SWITCH(UP4_BODY_)
+#undef UP4_BODY_
+}
+
 // The same, one WAVE per 16 x 16 output cell (= one stride-16 pixel), which lets the launch also produce what MASK_DOWN derives from
 // these probabilities for the NEXT frame's pixel fusion: m16[k] = mean of object plane k over the cell, pair = (m16[k], clamp(sum of
 // the others)).  The cell's values go through LDS so that every lane sums the same four entries in the same order as
 // mask_down_pair_kernel (entries lane, lane + 64, +128, +192 of the row-major cell) and the same wave_sum follows: bit-identical to the
 // MASK_DOWN launch it replaces.  4 waves (cells) per block; needs H, W multiples of 16 and K + 1 <= PMAX.
+// The body of up4_softmax_md_kernel (below, where its comments are) for ONE clip of the mixed form: every pointer at the clip's own planes / cells; cellw = this wave's [PMAX - 1][256]
+// floats of LDS, srcw = its [PMAX][36].  The same statements in the same order; kept apart so that the uniform instantiations do not move.
+template <int PMAX, int KC, bool SH>
+__device__ __forceinline__ void up4_md_body(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup, int Krt, int h, int w,
+                                            float* __restrict__ m16, uint4* __restrict__ pair, int ld8, float* cellw, float* srcw) {
+    const int K = KC > 0 ? KC : Krt;
+    const int OH = 4 * h, OW = 4 * w, ch = OH >> 4, cw = OW >> 4, ncell = ch * cw;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int cid = blockIdx.x * 4 + wave;
+    if (cid >= ncell) return;                               // whole wave
+    const int cy = cid / cw, cx = cid - cy * cw;
+    const int r = lane >> 2, q4 = lane & 3;
+    const int oy = cy * 16 + r, j = cx * 4 + q4;
+    const long OHW = (long)OH * OW;
+    float out[PMAX][4];
+    float lo[PMAX][4];
+    if (SH) {
+        // the 6 x 6 source pixels of this cell, one per lane (36 of 64), aggregated once
+        if (lane < 36) {
+            const int sly = lane / 6, slx = lane - sly * 6;
+            const long o = (long)min(max(4 * cy - 1 + sly, 0), h - 1) * w + min(max(4 * cx - 1 + slx, 0), w - 1);
+            float raw[PMAX - 1], Lp[PMAX];
+#pragma unroll
+            for (int k = 0; k < PMAX - 1; ++k)
+                if (k < K) raw[k] = lg[(long)k * h * w + o];
+            up4_src<PMAX>(raw, K, Lp);
+#pragma unroll
+            for (int p = 0; p < PMAX; ++p)
+                if (p <= K) srcw[p * 36 + lane] = Lp[p];
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): srcL is wave-private
+        __builtin_amdgcn_wave_barrier();
+    }
+    up4_four<PMAX, KC, SH>(lg, K, h, w, oy, j, out, lo, srcw, 4 * cy - 1, 4 * cx - 1);
+    const long base = (long)oy * OW + 4 * j;
+#pragma unroll
+    for (int p = 0; p < PMAX; ++p)
+        if (p <= K) {
+            if (lup) *reinterpret_cast<float4*>(lup + p * OHW + base) = make_float4(lo[p][0], lo[p][1], lo[p][2], lo[p][3]);
+            *reinterpret_cast<float4*>(prob + p * OHW + base) = make_float4(out[p][0], out[p][1], out[p][2], out[p][3]);
+            if (p >= 1) *reinterpret_cast<float4*>(&cellw[(p - 1) * 256 + r * 16 + 4 * q4]) = make_float4(out[p][0], out[p][1], out[p][2], out[p][3]);
+        }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0xc07f);                     // lgkmcnt(0): the cell is wave-private
+    float sum = 0.f, mk[PMAX - 1];
+#pragma unroll
+    for (int k = 0; k < PMAX - 1; ++k)
+        if (k < K) {
+            float acc = 0.f;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc += cellw[k * 256 + lane + 64 * i];
+            const float a = wave_sum(acc) / 256.f;
+            sum += a;
+            mk[k] = a;
+        }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < PMAX - 1; ++k)
+            if (k < K) {
+                m16[(long)k * ncell + cid] = mk[k];
+                const float others = fminf(fmaxf(sum - mk[k], 0.f), 1.f);
+                pair[((long)k * ncell + cid) * ld8] = make_uint4(pack_bf2(mk[k], others), 0u, 0u, 0u);
+            }
+    }
+}
+
 template <int PMAX, int KC = 0, bool SH = false>
 __global__ __launch_bounds__(256) void up4_softmax_md_kernel(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup,
                                                              int Krt, int h, int w, float* __restrict__ m16, uint4* __restrict__ pair, int ld8, int prio) {
@@ -763,6 +875,24 @@ __global__ __launch_bounds__(256) void up4_softmax_md_kernel(const float* __rest
                 pair[((long)k * ncell + cid) * ld8] = make_uint4(pack_bf2(mk[k], others), 0u, 0u, 0u);
             }
     }
+}
+
+// Mixed form of the above (see up4_softmax_fused4_mixed_kernel): m16 / pair advance by the start_c objects in front of the clip.
+template <int PMAX, bool SH>
+__global__ __launch_bounds__(256) void up4_softmax_md_mixed_kernel(const float* __restrict__ lg, float* __restrict__ prob, float* __restrict__ lup,
+                                                                   unsigned counts, int h, int w, float* __restrict__ m16, uint4* __restrict__ pair, int ld8, int prio) {
+    if (prio) __builtin_amdgcn_s_setprio(1);
+    __shared__ float cell[4][PMAX - 1][256];
+    __shared__ float srcL[4][SH ? PMAX : 1][36];
+    const int cl = blockIdx.y, Kc = mixed_count(counts, cl), st = mixed_start(counts, cl);
+    const long ncell = (long)(h >> 2) * (w >> 2), OHW = (long)16 * h * w;
+    lg += (long)st * h * w; prob += (long)(st + cl) * OHW;
+    if (lup) lup += (long)(st + cl) * OHW;
+    m16 += (long)st * ncell; pair += (long)st * ncell * ld8;
+    const int wave = threadIdx.x >> 6;
+#define UP4_BODY_(KC) up4_md_body<PMAX, KC, SH>(lg, prob, lup, KC, h, w, m16, pair, ld8, &cell[wave][0][0], &srcL[wave][0][0])
+    UP4_MIXED_SWITCH(UP4_BODY_)
+#undef UP4_BODY_
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1105,6 +1235,17 @@ __global__ void copy2d_kernel(const uint32_t* __restrict__ s, uint32_t* __restri
     long r = i / roww; int c = i - r * roww;
     d[r * ds + c] = s[r * ss + c];
 }
+// COPY2D, mixed form (clips in lock step with different object counts): destination row r -- one object -- is a copy of source row
+// clip(r): a per-clip map (the x_transform of MainToGroupDistributor, group_modules.py:112-115) expanded to one map per object, which the
+// following conv adds as an ordinary residual -- the values the per-clip broadcast adds.  16 bytes per thread.
+__global__ void copy2d_clips_kernel(const uint4* __restrict__ s, uint4* __restrict__ d, long rows, int roww, long ss, long ds, unsigned counts) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * roww) return;
+    long r = i / roww; int c = i - r * roww;
+    int st;
+    const int cl = mixed_clip_of(counts, (int)r, st);
+    d[r * ds + c] = s[cl * ss + c];
+}
 // BANK_WRITE: blockIdx.y = segment (0..5 copies, 6..7 fills), blockIdx.x strides over its words
 struct BankWrite { const uint32_t* src[6]; uint32_t* dst[8]; int words[8]; uint32_t pattern[2]; };
 __global__ __launch_bounds__(256) void bank_write_kernel(BankWrite w) {
@@ -1342,8 +1483,14 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
         case CUTIE_OP_UPSAMPLE2X_ADD: {
             int C8 = i[3] / 8;
             long n = (long)i[0] * 4 * i[1] * i[2] * C8;
+            if (i[6]) {                                       // mixed form: i6 = the clips' object counts (3-bit fields), i5 = pixels between the clips' skip maps
+                int objs; const int nc = mixed_clips((unsigned)i[6], &objs);
+                if (nc < 1 || objs != i[0] || i[4] != 0 || i[5] < 4 * i[1] * i[2]) { cutie_set_error("upsample2x_add (mixed form): the counts 0x%x do not add up to B = %d (or i4 != 0, or the stride is below one map)", i[6], i[0]); return -2; }
+                hipLaunchKernelGGL(upsample2x_add_kernel<true>, GRID1D(n, BS), dim3(BS), 0, s, (const uint4*)p[0], (const uint4*)p[1], (uint4*)p[2], i[0], i[1], i[2], C8, i[6], (long)i[5], PRIO);
+                break;
+            }
             if (i[4] < 0 || (i[4] > 0 && (i[0] % i[4] || i[5] < 4 * i[1] * i[2]))) { cutie_set_error("upsample2x_add: skip groups of %d objects do not divide B = %d (or their stride is below one map)", i[4], i[0]); return -2; }
-            hipLaunchKernelGGL(upsample2x_add_kernel, GRID1D(n, BS), dim3(BS), 0, s, (const uint4*)p[0], (const uint4*)p[1], (uint4*)p[2], i[0], i[1], i[2], C8, i[4], (long)i[5], PRIO);
+            hipLaunchKernelGGL(upsample2x_add_kernel<false>, GRID1D(n, BS), dim3(BS), 0, s, (const uint4*)p[0], (const uint4*)p[1], (uint4*)p[2], i[0], i[1], i[2], C8, i[4], (long)i[5], PRIO);
             break;
         }
         case CUTIE_OP_AREA_DOWN: {
@@ -1419,6 +1566,24 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
                 const bool vec = !(op->flags & 2) && i[0] <= 8 && (((uintptr_t)p[1] | (uintptr_t)p[2]) & 15) == 0;      // four pixels per thread, 16-byte stores
                 const int nclip = i[4] > 1 ? i[4] : 1;           // clips in lock step: grid.y (the four-pixel forms only)
                 if (nclip > 1 && !vec) { cutie_set_error("up4_softmax: several clips per launch need the four-pixel form (P <= 8, aligned outputs)"); return -2; }
+                if (i[5]) {                                       // mixed form: i5 = the clips' object counts (3-bit fields); i4 = their number, i0 = the largest count + 1
+                    int objs; const int nc = mixed_clips((unsigned)i[5], &objs);
+                    if (nc < 1 || nc != i[4] || !vec || (op->flags & 8)) { cutie_set_error("up4_softmax (mixed form): %d clips in the counts 0x%x, i4 = %d; needs the four-pixel form with compile-time object counts", nc, i[5], i[4]); return -2; }
+                    if (op->flags & 4) {
+                        if (!p[3] || !p[4] || (i[1] & 3) || (i[2] & 3) || i[3] < 8 || (i[3] & 7)) { cutie_set_error("up4_softmax: the mask-down form needs h, w multiples of 4, m16 and pair"); return -2; }
+                        const int ncell = (i[1] / 4) * (i[2] / 4);
+                        if (op->flags & 16)
+                            hipLaunchKernelGGL((up4_softmax_md_mixed_kernel<8, false>), dim3((ncell + 3) / 4, nc), dim3(256), 0, s, (const float*)p[0], (float*)p[1], (float*)p[2], (unsigned)i[5],
+                                               i[1], i[2], (float*)p[3], (uint4*)p[4], i[3] / 8, PRIO);
+                        else
+                            hipLaunchKernelGGL((up4_softmax_md_mixed_kernel<8, true>), dim3((ncell + 3) / 4, nc), dim3(256), 0, s, (const float*)p[0], (float*)p[1], (float*)p[2], (unsigned)i[5],
+                                               i[1], i[2], (float*)p[3], (uint4*)p[4], i[3] / 8, PRIO);
+                    } else {
+                        const long n4 = (long)4 * i[1] * i[2];
+                        hipLaunchKernelGGL(up4_softmax_fused4_mixed_kernel<8>, dim3((unsigned)((n4 + BS - 1) / BS), nc), dim3(BS), 0, s, (const float*)p[0], (float*)p[1], (float*)p[2], (unsigned)i[5], i[1], i[2], PRIO);
+                    }
+                    break;
+                }
                 if (op->flags & 4) {                              // + MASK_DOWN of the probabilities (p3 = m16, p4 = pair, i3 = channel pitch of pair)
                     if (!vec || !p[3] || !p[4] || (i[1] & 3) || (i[2] & 3) || i[3] < 8 || (i[3] & 7)) { cutie_set_error("up4_softmax: the mask-down form needs P <= 8, h, w multiples of 4, m16 and pair"); return -2; }
                     const int ncell = (i[1] / 4) * (i[2] / 4);
@@ -1512,6 +1677,12 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
         case CUTIE_OP_COPY2D: {
             int roww = i[1] / 4;
             long n = (long)i[0] * roww;
+            if (i[4]) {                                       // mixed form: i4 = the clips' object counts; row r (an object) copies the row of ITS CLIP
+                int objs; const int nc = mixed_clips((unsigned)i[4], &objs);
+                if (nc < 1 || objs != i[0] || (i[1] & 15) || (i[2] & 15) || (i[3] & 15) || ((p[0] | p[1]) & 15)) { cutie_set_error("copy2d (mixed form): the counts 0x%x do not add up to %d rows (or rows / strides / pointers are not multiples of 16 bytes)", i[4], i[0]); return -2; }
+                hipLaunchKernelGGL(copy2d_clips_kernel, GRID1D(n / 4, BS), dim3(BS), 0, s, (const uint4*)p[0], (uint4*)p[1], (long)i[0], roww / 4, (long)i[2] / 16, (long)i[3] / 16, (unsigned)i[4]);
+                break;
+            }
             hipLaunchKernelGGL(copy2d_kernel, GRID1D(n, BS), dim3(BS), 0, s, (const uint32_t*)p[0], (uint32_t*)p[1], (long)i[0], roww, (long)i[2] / 4, (long)i[3] / 4);
             break;
         }

@@ -178,7 +178,10 @@ __device__ __forceinline__ bool aux_fg_late(const float* __restrict__ lg, int K,
 // the 80 KB of rows + weights and three block-wide barriers in front of the pixel loop are gone.
 // NW waves per block (8: half the per-wave prologue instructions of the 16-wave form contend for the SIMDs; the pixel loop is bound by
 // the K / V bytes of the block either way).  KT: the mask logits of this thread's pixels are fetched at entry for K <= KT objects (0: late).
-template <bool QPRE, bool ACC, int KT, int NW>
+// MIXED (clips in lock step with different object counts): Kg holds the counts word (common.h); object k's clip, that clip's count and
+// first object come from its prefix sums (block-uniform).  Instantiated with KT = 8 only: the flags are the same booleans for every KT
+// (slots >= K are selected away, aux_fg_vals), so a clip of <= 4 objects decides what its one-clip launch (KT = 4) decides.
+template <bool QPRE, bool ACC, int KT, int NW, bool MIXED = false>
 __global__ __launch_bounds__(NW * 64) void q2p_chain_kernel(QIn in, QOut out, const bf16_t* __restrict__ kv, const float* __restrict__ lg,
                                                            int HW, int HWp, int ldkv, int voff, int hstride, const float* __restrict__ qpre, int Kg) {
     if (in.prio) __builtin_amdgcn_s_setprio(1);            // CUTIE_F_PRIO: a launch of the frame's critical path (the plan decides, ops.OpList.prio)
@@ -195,7 +198,15 @@ __global__ __launch_bounds__(NW * 64) void q2p_chain_kernel(QIn in, QOut out, co
     extern __shared__ uint8_t dynlds[];                    // [HWp foreground flags][NW waves x 32 pixels x 80 B of V]
     // Kg: objects per clip (clips in lock step: the grid holds gridDim.y / Kg clips).  The foreground mask is decided among the Kg objects of
     // object k's clip (planes lg[clip * Kg ..]); everything else of the launch is per object.
-    const int hh = blockIdx.x, k = blockIdx.y, K = Kg, kin = k % Kg;
+    const int hh = blockIdx.x, k = blockIdx.y;
+    int K, kin;
+    if (MIXED) {
+        int st;
+        const int cl = mixed_clip_of((unsigned)Kg, k, st);
+        K = mixed_count((unsigned)Kg, cl); kin = k - st;
+    } else {
+        K = Kg; kin = k % Kg;
+    }
     lg += (long)(k - kin) * HW;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int c16 = lane & 15, g = lane >> 4;
@@ -867,20 +878,26 @@ int launch_qchain(const cutie_op* op, hipStream_t s) {
                 return -2;
             }
             // one instantiation per (q handed in, accumulator input, logits fetched at entry for <= 4 / <= 8 objects / late)
-            const int Kg = i[9] > 0 ? i[9] : i[0];            // i9: objects per clip (0: one clip holds all i0 objects)
-            if (i[0] % Kg) { cutie_set_error("attn_q2p (chain form): clips of %d objects do not divide K = %d", Kg, i[0]); return -2; }
+            const bool mixed = i[10] != 0;                    // i10: the clips' object counts as 3-bit fields (the mixed form; i9 = 0 then)
+            int Kg = i[9] > 0 ? i[9] : i[0];                  // i9: objects per clip (0: one clip holds all i0 objects)
+            if (mixed) {
+                int objs; const int nc = mixed_clips((unsigned)i[10], &objs);
+                if (nc < 1 || objs != i[0] || i[9] != 0) { cutie_set_error("attn_q2p (chain form, mixed): the counts 0x%x do not add up to K = %d (or i9 != 0)", i[10], i[0]); return -2; }
+                Kg = i[10];
+            } else if (i[0] % Kg) { cutie_set_error("attn_q2p (chain form): clips of %d objects do not divide K = %d", Kg, i[0]); return -2; }
             const int kt = Kg <= 4 ? 1 : Kg <= 8 ? 2 : 0;
-            const int var = (qp ? 6 : ac ? 3 : 0) + kt;
+            const int var = mixed ? 9 + (qp ? 2 : ac ? 1 : 0) : (qp ? 6 : ac ? 3 : 0) + kt;
             constexpr int NWV = 8;
             typedef void (*Kern)(QIn, QOut, const bf16_t*, const float*, int, int, int, int, int, const float*, int);
-            static const Kern kerns[9] = {
+            static const Kern kerns[12] = {
                 q2p_chain_kernel<false, false, 0, NWV>, q2p_chain_kernel<false, false, 4, NWV>, q2p_chain_kernel<false, false, 8, NWV>,
                 q2p_chain_kernel<false, true, 0, NWV>, q2p_chain_kernel<false, true, 4, NWV>, q2p_chain_kernel<false, true, 8, NWV>,
-                q2p_chain_kernel<true, false, 0, NWV>, q2p_chain_kernel<true, false, 4, NWV>, q2p_chain_kernel<true, false, 8, NWV>};
+                q2p_chain_kernel<true, false, 0, NWV>, q2p_chain_kernel<true, false, 4, NWV>, q2p_chain_kernel<true, false, 8, NWV>,
+                q2p_chain_kernel<false, false, 8, NWV, true>, q2p_chain_kernel<false, true, 8, NWV, true>, q2p_chain_kernel<true, false, 8, NWV, true>};
             const Kern kern = kerns[var];
             const size_t dyn = (size_t)HWp + NWV * 32 * Q2C_VLD * 2;
             if (dyn > 96 * 1024) { cutie_set_error("attn_q2p (chain form): HW = %d does not fit the LDS flag array", i[2]); return -2; }
-            static bool attr_set[9] = {};
+            static bool attr_set[12] = {};
             if (!attr_set[var]) {
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
                     cutie_set_error("attn_q2p (chain form): cannot raise the dynamic LDS limit");

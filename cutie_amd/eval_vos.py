@@ -266,17 +266,52 @@ def lockstep_key(vid_reader):
     return (tuple(int(v) for v in hw), int(len(d0['valid_labels'])), bool(vid_reader.use_all_mask))
 
 
+def lockstep_key_mixed(vid_reader):
+    """``lockstep_key`` without the number of objects -- what the videos of a group share under --lockstep-mixed
+    (``LockstepCores(mixed_objects=True)``): frame size and mask schedule.  None: no group for this video (no mask on its first frame, or
+    more objects than a batched plan holds per clip)."""
+    k = lockstep_key(vid_reader)
+    if k is None or not 1 <= k[1] <= 7:
+        return None
+    return (k[0], k[2])
+
+
+def lockstep_groups(mine, readers, lockstep, mixed=False):
+    """The lock-step groups of the videos `mine` (indices into `readers`): videos that can advance together, longest first so that the videos
+    of a group have similar lengths; groups of one video are left out (they run one by one).  mixed: grouped by frame size and mask
+    schedule only, and the videos INSIDE a group sorted by object count -- the counts tuple keys the plans, so the fewer orders the fewer
+    plans (and neighbours of one count share their conv launches, plans.Plan.conv)."""
+    key = lockstep_key_mixed if mixed else lockstep_key
+    by_key = {}
+    for c in mine:
+        k = key(readers[c])
+        if k is not None:
+            by_key.setdefault(k, []).append(c)
+    grouped = []
+    for k, cs in by_key.items():
+        cs.sort(key=lambda c: -len(readers[c]))
+        for g0 in range(0, len(cs) - 1, lockstep):
+            grp = cs[g0:g0 + lockstep]
+            if len(grp) >= 2:
+                if mixed:
+                    grp.sort(key=lambda c: lockstep_key(readers[c])[1])
+                grouped.append(grp)
+    return grouped
+
+
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
-                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict[int, Dict]:
+                            ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
+                            mixed_objects=False) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
-    videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key``; they may differ in length -- the
+    videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key`` (mixed_objects: ``lockstep_key_mixed``
+    -- their object counts may differ); they may differ in length -- the
     group runs as long as its shortest video, the others finish on their own cores.  Returns {index in vid_readers: {'frames', 'seconds'}}
     (the seconds of a lock-step frame are split evenly over its videos)."""
     _check_ingest(ingest)
     from .inference.lockstep import LockstepCores
     C = len(vid_readers)
-    ls = LockstepCores(network, cfg, C)
+    ls = LockstepCores(network, cfg, C, mixed_objects=mixed_objects)
     dev = network.device
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
@@ -330,6 +365,9 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--long-term', action='store_true')
     ap.add_argument('--visualize', action='store_true')
     ap.add_argument('--clips-in-flight', type=int, default=1)
+    ap.add_argument('--lockstep-mixed', action='store_true',
+                    help='--lockstep groups by frame size and mask schedule only: videos with different numbers of objects (1 .. 7) share the '
+                         'batched plans (LockstepCores(mixed_objects=True); same results per video)')
     ap.add_argument('--lockstep', type=int, default=1, help='advance up to this many videos of one frame size / object count in LOCK STEP through one launch plan '
                                                             'per stage (cutie_amd/inference/lockstep.py; same results per video); the others run as --clips-in-flight says')
     ap.add_argument('--read-workers', type=int, default=4, help='decode threads per clip (0 = inline)')
@@ -448,20 +486,10 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
         if args.lockstep > 1 and not args.flip_aug:
             # groups of videos that can advance together (same frame size, object count and mask schedule), longest first so that the
             # videos of a group have similar lengths; what is left over runs one by one below
-            by_key = {}
-            for c in mine:
-                k = lockstep_key(readers[c])
-                if k is not None:
-                    by_key.setdefault(k, []).append(c)
-            grouped = []
-            for k, cs in by_key.items():
-                cs.sort(key=lambda c: -len(readers[c]))
-                for g0 in range(0, len(cs) - 1, args.lockstep):
-                    grp = cs[g0:g0 + args.lockstep]
-                    if len(grp) >= 2:
-                        grouped.append(grp)
+            # (--lockstep-mixed: same frame size and mask schedule only)
+            grouped = lockstep_groups(mine, readers, args.lockstep, mixed=args.lockstep_mixed)
             for grp in grouped:
-                st = process_videos_lockstep(net, cfg, [readers[c] for c in grp], mask_root, **common)
+                st = process_videos_lockstep(net, cfg, [readers[c] for c in grp], mask_root, mixed_objects=args.lockstep_mixed, **common)
                 for j, c in enumerate(grp):
                     res[c] = st[j]
             mine = [c for c in mine if c not in res]

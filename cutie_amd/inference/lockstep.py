@@ -23,6 +23,12 @@ batch = C x K objects (clip-major):
 Per clip every launch computes what the one-clip plan computes, with conv tiles of the same K-order class (``Plan.korder_ref``), so a
 clip's probabilities are bit-identical to its own ``InferenceCore`` run (tests: test_lockstep_clips_match_sequential, CPU + GPU).
 
+``mixed_objects=True``: the clips of a group may hold DIFFERENT numbers of objects (1 .. 7 each).  The plans are then built with the clips' counts
+(``clips=(K_0, K_1, ..)``): every per-object tensor holds sum(K_c) rows, clip c's at the prefix sum of the counts; the launches that couple a
+clip's objects take the counts as one word (include/cutie_hip.h, "mixed forms"); a convolution whose one-clip tiles sum over K in different
+orders for different counts is cut into one launch per run of clips of one K-order class (plans.Plan.conv); the look-ahead read-outs stay
+in every clip's own lane (the joint pass writes uniform groups only).  Still every clip's own bits and bank.
+
 A step is batched when every clip is in the plain propagation state (memory engaged, one bucket holding all of its K objects, the
 same frame / memory schedule and geometry, no mask, no ``end``); anything else -- the first frame with its masks, ``end=True`` --
 runs clip by clip through the cores' own ``step``.
@@ -34,6 +40,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from .. import _lib, frame_context
+from .. import ops as O
 from ..model import plans
 from ..model.cutie import group_logical
 from . import inference_core as IC
@@ -68,10 +75,15 @@ class LockstepCores(ClipCores):
     # that frame j of every clip -- and with it the read-outs pixel fusion takes -- is one stacked tensor); off: every clip's own look-ahead lane (A/B switch)
     JOINT = os.environ.get('CUTIE_AMD_LS_JOINT', '1') not in ('', '0')
 
-    def __init__(self, network, cfg, clips: int):
+    def __init__(self, network, cfg, clips: int, mixed_objects: bool = False):
         super().__init__(network, cfg, clips)
         self.network = network
         self.cfg = cfg
+        self.mixed_objects = bool(mixed_objects)    # clips with different object counts share the batched plans (off: they run clip by clip)
+        if self.mixed_objects:
+            ex = _lib.get_executor()
+            if not getattr(ex, 'ex', ex).is_mock and not _lib.has_mixed_lockstep():
+                raise _lib.HipLibraryError('libcutie_hip.so lacks the mixed forms of the lock-step ops: rebuild it (make -C cutie_amd/csrc)')
         if self.WINDOW <= 0:
             self.WINDOW = max(1, round(12 / clips))
         self._state = None              # (sens_f32 [C*K,h,w,CS], sens_bf16, objv [C*K,Q,CE+1]): the stacked per-object state of the group
@@ -106,30 +118,42 @@ class LockstepCores(ClipCores):
             ids = core.object_manager.all_obj_ids
             if list(b.objects) != list(ids) or mm._ids != list(ids) or mm._objv_ids != list(ids):
                 return False
-            K = len(ids) if K is None else K
+            if self.mixed_objects:                           # (every clip its own count)
+                K = len(ids)
+            else:
+                K = len(ids) if K is None else K
             if len(ids) != K or K < 1 or K + 1 > 8:
                 return False
             if (core.curr_ti, core.last_mem_ti, core.mem_every) != (c0.curr_ti, c0.last_mem_ti, c0.mem_every) or core.stagger_ti != c0.stagger_ti:
                 return False
             if core.last_mask is None or core.last_mask.shape[1] != K:
                 return False
-        return True
+        return not self.mixed_objects or len(self.cores) <= 8
 
-    def _stack_state(self, K):
-        """The sensory state and the object summaries of the clips as ONE tensor each (clip-major); every clip's MemoryManager keeps
-        working on its slice (views: the kernels update the state in place, memory_manager.py:360-375 / :252-271)."""
+    def _counts(self):
+        """(the clips' object counts, their prefix sums, do they differ)"""
+        if not self.mixed_objects:                          # (a batched step without the switch: one count -- nothing to add up per frame)
+            K, G = self.cores[0].object_manager.num_obj, len(self.cores)
+            return (K,) * G, range(0, (G + 1) * K, K), False
+        counts = tuple(core.object_manager.num_obj for core in self.cores)
+        return counts, O.clip_starts(counts), len(set(counts)) > 1
+
+    def _stack_state(self, counts, o):
+        """The sensory state and the object summaries of the clips as ONE tensor each (clip-major, clip c's objects at the prefix sum of the
+        counts); every clip's MemoryManager keeps working on its slice (views: the kernels update the state in place,
+        memory_manager.py:360-375 / :252-271)."""
         mms = [c.memory for c in self.cores]
         st = self._state
-        if st is not None and st[0].shape[0] == K * len(mms) and all(
-                mm._sens_f32.data_ptr() == st[0][c * K].data_ptr() and mm._sens_bf16.data_ptr() == st[1][c * K].data_ptr()
-                and mm._objv.data_ptr() == st[2][c * K].data_ptr() and mm._sens_f32.shape[0] == K for c, mm in enumerate(mms)):
+        if st is not None and st[0].shape[0] == o[-1] and all(
+                mm._sens_f32.data_ptr() == st[0][o[c]].data_ptr() and mm._sens_bf16.data_ptr() == st[1][o[c]].data_ptr()
+                and mm._objv.data_ptr() == st[2][o[c]].data_ptr() and mm._sens_f32.shape[0] == counts[c] for c, mm in enumerate(mms)):
             return st
         sf = torch.cat([mm._sens_f32 for mm in mms], 0).contiguous()
         sb = torch.cat([mm._sens_bf16 for mm in mms], 0).contiguous()
         ov = torch.cat([mm._objv for mm in mms], 0).contiguous()
         for c, mm in enumerate(mms):
-            mm._sens_f32, mm._sens_bf16 = sf[c * K:(c + 1) * K], sb[c * K:(c + 1) * K]
-            mm._objv = ov[c * K:(c + 1) * K]            # (a new content token: the queries are initialised again)
+            mm._sens_f32, mm._sens_bf16 = sf[o[c]:o[c + 1]], sb[o[c]:o[c + 1]]
+            mm._objv = ov[o[c]:o[c + 1]]                # (a new content token: the queries are initialised again)
         self._state = (sf, sb, ov)
         self._qtoken = None
         return self._state
@@ -227,7 +251,7 @@ class LockstepCores(ClipCores):
         memory frame, as far as they lie behind each other in one frame-major encoder batch; first_alone (a memory frame): the next frame
         of every clip as a pass of its own -- the next step waits for it -- and the rest of the memory cycle behind it.  False: not
         possible here (the caller lets every clip's own look-ahead lane do it)."""
-        if not self.JOINT:
+        if not self.JOINT or (self.mixed_objects and self._counts()[2]):          # (a mixed group: every clip's own look-ahead lane -- the joint pass writes K objects per bank)
             return False
         cores, net = self.cores, self.network
         c0 = cores[0]
@@ -383,8 +407,11 @@ class LockstepCores(ClipCores):
         c0 = cores[0]
         is_mem_frame = c0.curr_ti - c0.last_mem_ti >= c0.mem_every      # (inference_core.py:238, mask is None and not end)
         update_sensory = (c0.curr_ti - c0.last_mem_ti) in c0.stagger_ti  # (:243)
-        K = cores[0].object_manager.num_obj
-        sf, sb, ov = self._stack_state(K)
+        counts, st, mixed = self._counts()
+        K = counts[0]
+        lay = (counts, 0) if mixed else (G, K)                          # (plan / pool keys; the builders' clips argument)
+        clips = counts if mixed else G
+        sf, sb, ov = self._stack_state(counts, st)
         if next_images is not None and len(next_images) == G:
             self._prefetch(next_images, affinity=not is_mem_frame)
         # ---- affinity read-out: per clip (its own bank), taken over from the look-ahead lane where that ran against this bank version
@@ -401,10 +428,10 @@ class LockstepCores(ClipCores):
         # ---- pixel fusion -> object transformer -> decoder: one plan each for the C x K objects
         ws = recs[0]['_wstride']
         m = net.model_cfg
-        KT = G * K
+        KT = st[-1]
         md = self._md_valid
-        P = eng.plan(('ls_fuse', G, K, h, w, md, ws, stacked is not None), plans.build_pixel_fusion, K, h, w, True, md, G, ws, stacked is not None)
-        fused = eng.pool.get(('ls_fuse', G, K, h, w, eng.devstr), dict(fused=((KT, h, w, m['embed_dim']), BF16, False)), dev)['fused']
+        P = eng.plan(('ls_fuse',) + lay + (h, w, md, ws, stacked is not None), plans.build_pixel_fusion, K, h, w, True, md, clips, ws, stacked is not None)
+        fused = eng.pool.get(('ls_fuse',) + lay + (h, w, eng.devstr), dict(fused=((KT, h, w, m['embed_dim']), BF16, False)), dev)['fused']
         dyn = {'pixel%d' % c: readouts[c] for c in range(G)} if stacked is None else dict(pixel=stacked)
         if not md:
             dyn.update({'last_mask%d' % c: _f32c(core.last_mask[0]) for c, core in enumerate(cores)})
@@ -412,21 +439,23 @@ class LockstepCores(ClipCores):
         token = tuple(core.memory._objv_token for core in cores)
         fresh = token != self._qtoken or not plans.QINIT_SKIP
         self._qtoken = token
-        P = eng.plan(('ls_rq', G, K, h, w, fresh), plans.build_readout_query, K, h, w, False, fresh, G)
-        out = eng.pool.get(('ls_rq', G, K, h, w, eng.devstr), dict(out=((KT, h, w, m['embed_dim']), BF16, False)), dev)['out']
+        P = eng.plan(('ls_rq',) + lay + (h, w, fresh), plans.build_readout_query, K, h, w, False, fresh, clips)
+        out = eng.pool.get(('ls_rq',) + lay + (h, w, eng.devstr), dict(out=((KT, h, w, m['embed_dim']), BF16, False)), dev)['out']
         P.run(pixel=fused, obj_mem=ov, out=out)
-        P = eng.plan(('ls_seg', G, K, h, w, bool(update_sensory), ws), plans.build_segment, K, h, w, bool(update_sensory), True, True, G, ws)
-        prob = eng.pool.get(('ls_seg', G, K, h, w, eng.devstr), dict(prob=((G, K + 1, 16 * h, 16 * w), F32, False)), dev)['prob']
+        P = eng.plan(('ls_seg',) + lay + (h, w, bool(update_sensory), ws), plans.build_segment, K, h, w, bool(update_sensory), True, True, clips, ws)
+        # (a mixed group: clip c's K_c + 1 planes lie behind those of the clips in front)
+        prob = eng.pool.get(('ls_seg',) + lay + (h, w, eng.devstr), dict(prob=((KT + G, 16 * h, 16 * w) if mixed else (G, K + 1, 16 * h, 16 * w), F32, False)), dev)['prob']
         P.run(p16=out, sensory_f32=sf, sensory_bf16=sb, prob=prob, logits_up=None, f8p=recs[0]['f8p'], f4p=recs[0]['f4p'])
         self._md_valid = True
+        probs = [prob[st[c] + c:st[c + 1] + c + 1] for c in range(G)] if mixed else [prob[c] for c in range(G)]
         for c, core in enumerate(cores):
-            core.last_mask = prob[c, 1:].unsqueeze(0)                   # (inference_core.py:302)
+            core.last_mask = probs[c][1:].unsqueeze(0)                  # (inference_core.py:302)
         if is_mem_frame:
-            self._memorise(prepared, recs, feats, prob, (h0, w0, H, W, pl, pt), K, next_images)
+            self._memorise(prepared, recs, feats, prob, (h0, w0, H, W, pl, pt), (counts, st, mixed), next_images)
         self.batched_steps += 1
-        return [unpad(prob[c], core.pad) for c, core in enumerate(cores)]
+        return [unpad(probs[c], core.pad) for c, core in enumerate(cores)]
 
-    def _memorise(self, prepared, recs, feats, prob, geometry, K, next_images):
+    def _memorise(self, prepared, recs, feats, prob, geometry, layout, next_images):
         """Memory frame (inference_core.py:71-121, :308-315) of all clips: the mask encoder once for the C x K objects, then every clip's
         bank insertion, then -- while this stream goes on with the sensory deep update and the object summaries -- the next frame's
         read-outs against the new banks on the side stream (the two-part order of InferenceCore._add_memory)."""
@@ -439,10 +468,12 @@ class LockstepCores(ClipCores):
         m = net.model_cfg
         sf, sb, _ = self._state
         ws = recs[0]['_wstride']
-        KT = G * K
+        counts, st, mixed = layout
+        K, KT = counts[0], st[-1]
+        lay = (counts, 0) if mixed else (G, K)
         md = self._md_valid
-        P = eng.plan(('ls_emask', G, K, h0, w0, H, W, pl, pt, md, ws), plans.build_encode_mask, K, h0, w0, H, W, pl, pt, True, md, G, ws)
-        o = eng.pool.get(('ls_emask', G, K, h, w, eng.devstr),
+        P = eng.plan(('ls_emask',) + lay + (h0, w0, H, W, pl, pt, md, ws), plans.build_encode_mask, K, h0, w0, H, W, pl, pt, True, md, counts if mixed else G, ws)
+        o = eng.pool.get(('ls_emask',) + lay + (h, w, eng.devstr),
                          dict(value=((KT, h, w, m['value_dim']), BF16, False),
                               summ=((KT, m['object_summarizer']['num_summaries'], m['embed_dim'] + 1), F32, False)), dev)
         value, summ = o['value'], o['summ']
@@ -454,7 +485,7 @@ class LockstepCores(ClipCores):
             ids = core.object_manager.all_obj_ids
             _, _, key, shrinkage, selection = feats[c]
             with frame_context.context(self._ctx[c]):
-                core.memory.add_memory(key, shrinkage, group_logical(value[c * K:(c + 1) * K]), None, ids, selection=selection, as_permanent='first')
+                core.memory.add_memory(key, shrinkage, group_logical(value[st[c]:st[c + 1]]), None, ids, selection=selection, as_permanent='first')
         if next_images is not None:
             # every clip's next frame first (the next step waits for them), the stacked passes for the rest of the memory cycle behind them
             nxt = []
@@ -475,7 +506,7 @@ class LockstepCores(ClipCores):
         for c, core in enumerate(cores):
             ids = core.object_manager.all_obj_ids
             with frame_context.context(self._ctx[c]):
-                core.memory.add_object_values(summ[c * K:(c + 1) * K].unsqueeze(0), ids)
+                core.memory.add_object_values(summ[st[c]:st[c + 1]].unsqueeze(0), ids)
             core.last_mem_ti = core.curr_ti
 
     def output_prob_to_mask(self, probs: Sequence[torch.Tensor], **kw) -> List[torch.Tensor]:

@@ -248,6 +248,10 @@ class Plan:
         self._arena_views = {}           # name -> (offset, shape, dtype)
         self._graphs = {}                # pointer signature -> HIP graph of this plan (_lib.HipExecutor.run_cached)
         self.korder_ref = 0              # B > 1: a batched twin of a B = 1 plan -- tiles from the K-order class the B = 1 plan uses (autotune_convs)
+        # clips in lock step with DIFFERENT object counts (the builders' clips=(K_0, K_1, ..)): the counts; and per conv launch that holds
+        # several of those clips the object count of the clip whose one-clip plan names its K-order class (conv / autotune_convs)
+        self.mixed = None
+        self.kref = {}
 
     def buf(self, name, shape, dtype=BF16, persistent=False):
         assert name not in self.bufs, name
@@ -367,17 +371,19 @@ class Plan:
                 continue
             i = arr['i'][n]
             M, cout, cin = int(i[0]) * int(i[7]) * int(i[8]), int(i[9]), int(i[3]) + int(i[4])
-            key = (M, cout, cin, int(i[11]), int(i[13]), int(arr['flags'][n]) & 3, int(i[1]), int(i[2]))
+            fl = int(arr['flags'][n])
+            key = O.conv_tile_key(M, cout, cin, int(i[11]), int(i[13]), fl & O.F_RELU_IN, fl & O.F_OUT_F32, int(i[1]), int(i[2]))
             best = cache.get(key)
             twin = self.korder_ref and int(i[0]) % self.korder_ref == 0     # (a lock-step plan also holds launches of ONE clip, B = 1: those are the one-clip plan's own geometry)
+            kref = self.kref.get(n)                          # (a mixed group: the launch holds several clips, kref objects in the one that names the class)
+            twin = twin or kref is not None
             if twin:
                 # batched twin of a B = 1 plan (the look-ahead window of the image encoder): whatever the table says for the batched
                 # geometry, the tile must sum over K in the order of the tile the B = 1 plan runs for this layer -- that keeps frame b
                 # of the batch bit-identical to the same frame through the B = 1 plan
-                Bk = self.korder_ref
-                key1 = (M // Bk,) + key[1:]
-                ref = cache.get(key1) or (O.COUT1_TILE if (int(i[17]) == O.COUT1_TILE) else
-                                          O.pick_tile(M // Bk, cout, cin, dict(kh=int(i[11]), c2=int(i[4]))), 1)
+                M1 = M // self.korder_ref if kref is None else M * kref // int(i[0])
+                key1 = (M1,) + key[1:]
+                ref = cache.get(key1) or (O.static_tile(M1, cout, cin, int(i[11]), int(i[4]), cout1=int(i[17]) == O.COUT1_TILE), 1)
                 want = O.korder_class(*ref)
                 if isinstance(want, str) and cache.get(key + (want,)) is not None:
                     best = cache[key + (want,)]              # a table entry FOR this class (two layers of one batched geometry may need different classes)
@@ -432,11 +438,45 @@ class Plan:
             assert out.B == x.B and out.H == OH and out.W == OW and out.C == w.cout, (wname, out.B, out.H, out.W, out.C, OH, OW, w.cout)
         if res is not None:
             assert res.C == w.cout and res.H == OH and res.W == OW
-        self.ol.conv(x.t, w, out.t, B=x.B, H=x.H, W=x.W, C1=x.C, ldx1=x.ld, OH=OH, OW=OW, ldy=out.ld, stride=stride,
-                     pad=pad, x2=None if x2 is None else x2.t, C2=0 if x2 is None else x2.C,
-                     ldx2=0 if x2 is None else x2.ld, res=None if res is None else res.t,
-                     ldr=0 if res is None else res.ld, res_bcast=res_bcast, relu_in=relu_in, act=act, out_f32=out_f32,
-                     gap_acc=gap_acc, zero=zero, prio=self.prio, res_group=res_group)
+
+        def emit(s0, s1, zero):
+            """One launch over the objects [s0, s1) of the operands."""
+            whole = s0 == 0 and s1 == x.B
+            cut = (lambda a, elem: a.t) if whole else (lambda a, elem: _objects_from(a, s0, elem))
+            return self.ol.conv(cut(x, 2), w, cut(out, 4 if out_f32 else 2), B=s1 - s0, H=x.H, W=x.W, C1=x.C, ldx1=x.ld, OH=OH, OW=OW, ldy=out.ld, stride=stride,
+                                pad=pad, x2=None if x2 is None else cut(x2, 2), C2=0 if x2 is None else x2.C,
+                                ldx2=0 if x2 is None else x2.ld, res=None if res is None else (res.t if res_bcast else cut(res, 2)),
+                                ldr=0 if res is None else res.ld, res_bcast=res_bcast, relu_in=relu_in, act=act, out_f32=out_f32,
+                                gap_acc=gap_acc if (gap_acc is None or whole) else gap_acc[s0:], zero=zero, prio=self.prio, res_group=res_group)
+        if self.mixed is None or x.B != sum(self.mixed):
+            emit(0, x.B, zero)
+            return out
+        # A mixed group: every clip must get the bits of ITS one-clip plan, whose tile -- hence the order of the fp32 sum over K -- comes from
+        # the tile table by the clip's own geometry (M = K_c x OH x OW).  Clips whose one-clip tiles are of one K-order class share a launch;
+        # where the classes differ between neighbours the launch is cut there (consecutive clips only: the group is sorted by count).
+        assert res_group is None
+        counts, st = self.mixed, O.clip_starts(self.mixed)
+        side = gap_acc is not None or zero is not None
+        cin = x.C + (0 if x2 is None else x2.C)
+
+        def one_clip_class(Kc):
+            M1 = Kc * OH * OW
+            key1 = O.conv_tile_key(M1, w.cout, cin, w.kh, stride, relu_in, out_f32, x.H, x.W)
+            static = O.static_tile(M1, w.cout, cin, w.kh, 0 if x2 is None else x2.C, res is not None, side)
+            return O.korder_class(*(self.eng.tile_cache.get(key1) or (static, 1)))
+        cls = [one_clip_class(k) for k in counts]
+        c0 = 0
+        for c in range(1, len(counts) + 1):
+            if c < len(counts) and cls[c] == cls[c0]:
+                continue
+            z = zero
+            if zero is not None and c - c0 < len(counts):        # the launch's share of the buffer it clears (per object), or all of it with the first launch
+                per_obj = zero.dim() == 2 and zero.shape[0] == x.B       # (ca_block's GAP sums [B, C]; the query chain's accumulators are [3 nb, M, C])
+                z = zero[st[c0]:st[c]] if per_obj else (zero if c0 == 0 else None)
+            n = emit(st[c0], st[c], z)
+            if c - c0 > 1:
+                self.kref[n] = counts[c0]                     # several clips: a twin of the one-clip plan of any of them (one class)
+            c0 = c
         return out
 
     # ---- shared blocks ------------------------------------------------------------------
@@ -468,10 +508,18 @@ class Plan:
 
     def fusion_block(self, prefix, x, g, name, out=None, xt=None, xt_group=None):
         """GroupFeatureFusionBlock (group_modules.py:102-127).  xt: x_transform(x) computed elsewhere (the encoder plan).
-        xt_group = (objects per clip, rows between the clips' xt maps): clips in lock step -- every clip's objects add their clip's map."""
+        xt_group = (objects per clip, rows between the clips' xt maps): clips in lock step -- every clip's objects add their clip's map.
+        Objects per clip a sequence (a mixed group): ONE copy launch (COPY2D, mixed form; MIXED_FUSION_EXTRA) expands the per-clip maps to a
+        map per object, which the conv adds as an ordinary residual -- the values the broadcast adds, the conv kernels untouched."""
         if xt is None:
             xt = self.conv(prefix + '.distributor.x_transform', x, name=name + '.xt')
-        g0 = self.conv(prefix + '.distributor.g_transform', g, name=name + '.g0', res=xt, res_bcast=True, res_group=xt_group)
+        if xt_group is not None and not isinstance(xt_group[0], int):
+            counts, stride = xt_group
+            xte = self.buf(name + '.xte', (g.B, xt.H, xt.W, xt.C))
+            self.ol.copy2d(xt.t, xte, rows=g.B, rowbytes=xt.H * xt.W * xt.C * 2, src_stride=stride * xt.ld * 2, dst_stride=xt.H * xt.W * xt.C * 2, clips=counts)
+            g0 = self.conv(prefix + '.distributor.g_transform', g, name=name + '.g0', res=Act(xte, g.B, xt.H, xt.W, xt.C))
+        else:
+            g0 = self.conv(prefix + '.distributor.g_transform', g, name=name + '.g0', res=xt, res_bcast=True, res_group=xt_group)
         g1 = self.ca_block(prefix + '.block1', g0, name + '.b1')
         return self.ca_block(prefix + '.block2', g1, name + '.b2', out=out)
 
@@ -496,6 +544,28 @@ class Plan:
                     x = self.conv(p + '.conv2', t1, res=r, act=O.ACT_RELU, out=out)
             feats[lname] = x
         return x, feats
+
+
+def _objects_from(a, s0, elem):
+    """The tensor (or Dyn slot) of Act `a` from object s0 on; elem = bytes per element."""
+    per_obj = a.H * a.W * a.ld
+    if isinstance(a.t, Dyn):
+        return Dyn(a.t.name, a.t.offset + s0 * per_obj * elem)
+    assert a.t.is_contiguous() and a.t.element_size() == elem, (a.t.shape, a.t.dtype, elem)
+    return a.t.reshape(-1)[s0 * per_obj:]
+
+
+MIXED_FUSION_EXTRA = 1      # launches a mixed group adds per fusion block: the copy that expands the per-clip x_transform maps (fusion_block)
+
+
+def clip_layout(K, clips):
+    """(number of clips, their object counts, the prefix sums, is the group mixed) of the builders' `K, clips`: clips = G with K objects each, or
+    clips = (K_0, K_1, ..) -- the clips' own counts (K is ignored then); equal counts are the uniform group of that many clips."""
+    if isinstance(clips, int):
+        counts = (int(K),) * clips
+    else:
+        counts = tuple(int(k) for k in clips)
+    return len(counts), counts, O.clip_starts(counts), len(set(counts)) > 1
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -586,24 +656,29 @@ def build_pixel_fusion(eng, K, h, w, pre=False, pre_md=False, clips=1, wstride=1
     per-clip tensors (fuse_xt: needs pre) are the slices of one frame in the encoder window's output, `wstride` frames apart; the read-outs
     of the clips (dyn in pixel0 .. pixel<clips-1>, one tensor per memory bank) are gathered by the first launch -- or, stacked, come as
     one tensor `pixel` [clips * K, h, w, CV] (a read-out pass over all banks, MemoryManager.prefetch_affinity_joint); dyn in last_mask0.. when
-    the masks were not down-sampled by the segment in front (pre_md).  Per clip the launches compute what the one-clip plan computes."""
-    G, Kc = clips, K
-    K = G * Kc
+    the masks were not down-sampled by the segment in front (pre_md).  Per clip the launches compute what the one-clip plan computes.
+    clips = (K_0, K_1, ..): a MIXED group, clip c with K_c objects (K is ignored; see clip_layout) -- every per-object tensor has sum(K_c) rows,
+    clip c's at the prefix sum of the counts; the launches that couple a clip's objects take the counts (include/cutie_hip.h, mixed forms)."""
+    G, counts, st, mixed = clip_layout(K, clips)
+    gkey = counts if mixed else G                        # (the buffers both plans know are a set per layout)
+    K = st[-1]
     assert G == 1 or pre, 'clips in lock step take x_transform(pix_feat) from the encoder plan'
+    assert not (mixed and stacked), 'the joint read-out pass writes uniform groups only'
     P = Plan(eng, touch=weights_go_cold(h * w, K))
+    P.mixed = counts if mixed else None
     m = eng.m
     if pre_md:                                           # written by the previous frame's up-sampling launch (build_segment(md=True))
-        pair = eng.mask_down_bufs(K, h, w, G)[0]
+        pair = eng.mask_down_bufs(K, h, w, gkey)[0]
         P.ol.keep.append(pair)
     else:
         pair = P.buf('pair', (K, h, w, 64), persistent=True)       # (mask, others) in channels 0, 1 of a ZEROED 64-channel tensor: a whole K tile
         m16 = P.buf('m16', (K, h, w), F32)
         for c in range(G):                               # ("others" = the other objects of the SAME clip: one launch per clip)
-            P.ol.mask_down(Dyn('last_mask' if G == 1 else 'last_mask%d' % c), pair[c * Kc:], m16[c * Kc:], K=Kc, H=16 * h, W=16 * w, pair_channels=64)
+            P.ol.mask_down(Dyn('last_mask' if G == 1 else 'last_mask%d' % c), pair[st[c]:], m16[st[c]:], K=counts[c], H=16 * h, W=16 * w, pair_channels=64)
     if G > 1 and not stacked:
         px = P.buf('pixel_all', (K, h, w, m['value_dim']))
-        nb = Kc * h * w * m['value_dim'] * 2
-        P.ol.bank_write([(Dyn('pixel%d' % c), px[c * Kc:], nb) for c in range(G)])
+        nb = h * w * m['value_dim'] * 2
+        P.ol.bank_write([(Dyn('pixel%d' % c), px[st[c]:], counts[c] * nb) for c in range(G)])
         pixel = Act(px, K, h, w, m['value_dim'])
     else:
         pixel = Act(Dyn('pixel'), K, h, w, m['value_dim'])
@@ -611,8 +686,8 @@ def build_pixel_fusion(eng, K, h, w, pre=False, pre_md=False, clips=1, wstride=1
                  x2=Act(pair, K, h, w, 64), res=pixel, name='p16')
     xt = Act(Dyn('fuse_xt'), G, h, w, eng.w['pixel_fuser.fuser.distributor.x_transform'].cout) if pre else None
     P.fusion_block('pixel_fuser.fuser', Act(Dyn('pix_feat'), 1, h, w, m['pixel_dim']), p16, 'fuse',
-                   out=Act(Dyn('fused'), K, h, w, m['embed_dim']), xt=xt, xt_group=(Kc, wstride * h * w) if G > 1 else None)
-    if G > 1:
+                   out=Act(Dyn('fused'), K, h, w, m['embed_dim']), xt=xt, xt_group=(counts if mixed else counts[0], wstride * h * w) if G > 1 else None)
+    if G > 1 and not mixed:
         P.korder_ref = G                                 # tiles from the K-order class of the one-clip plan's: same bits per clip
     return P
 
@@ -624,11 +699,13 @@ def build_readout_query(eng, K, h, w, last_aux=True, fresh=True, clips=1):
     head after the LAST block: its logits mask no attention any more (the reference computes them anyway, object_transformer.py:164,
     and only save_aux / training read them).
     clips > 1: that many clips of K objects in lock step (see build_pixel_fusion) -- every launch of the transformer is per object; the
-    foreground masks are decided among the objects of one clip (ATTN_Q2P i9)."""
-    G, Kc = clips, K
-    K = G * Kc
+    foreground masks are decided among the objects of one clip (ATTN_Q2P i9).  clips = (K_0, K_1, ..): a mixed group (ATTN_Q2P i10)."""
+    G, counts, st, mixed = clip_layout(K, clips)
+    K = st[-1]
+    Kc = counts if mixed else counts[0]
     P = Plan(eng, touch=weights_go_cold(h * w, K))
-    if G > 1:
+    P.mixed = counts if mixed else None
+    if G > 1 and not mixed:
         P.korder_ref = G
     m, ol, W = eng.m, P.ol, eng.w
     ot = m['object_transformer']
@@ -774,12 +851,17 @@ def build_segment(eng, K, h, w, update_sensory, pre=False, md=False, clips=1, ws
     pre: f8p, f4p (decoder_feat_proc of f8 / f4, from the encoder plan) instead of f8, f4.
     dyn out: prob f32 [K+1,16h,16w] (+ logits_up if bound).
     clips > 1: that many clips of K objects in lock step (see build_pixel_fusion; needs pre): f8p / f4p are the slices of one frame in the
-    encoder window's output, `wstride` frames apart; dyn out prob f32 [clips, K+1, 16h, 16w]."""
-    G, Kc = clips, K
-    K = G * Kc
+    encoder window's output, `wstride` frames apart; dyn out prob f32 [clips, K+1, 16h, 16w].
+    clips = (K_0, K_1, ..): a mixed group -- dyn out prob f32 [sum(K_c) + clips, 16h, 16w], clip c's K_c + 1 planes from plane start_c + c on."""
+    G, counts, st, mixed = clip_layout(K, clips)
+    K = st[-1]
+    Kc = max(counts)
     assert G == 1 or (pre and Kc + 1 <= 8), 'clips in lock step: image-only decoder convs from the encoder plan, <= 7 objects per clip'
     P = Plan(eng, touch=weights_go_cold(h * w, K))
-    if G > 1:
+    P.mixed = counts if mixed else None
+    gkey = counts if mixed else G
+    sgrp = counts if mixed else counts[0]
+    if G > 1 and not mixed:
         P.korder_ref = G
     m, ol = eng.m, P.ol
     up = m['mask_decoder']['up_dims']
@@ -793,13 +875,13 @@ def build_segment(eng, K, h, w, update_sensory, pre=False, md=False, clips=1, ws
         f4p = P.conv('mask_decoder.decoder_feat_proc.transforms.1', Act(Dyn('f4'), 1, h4, w4, ms[2]), name='f4p')
     p16 = Act(Dyn('p16'), K, h, w, up[0])
     u8 = P.buf('u8', (K, h8, w8, up[0]))
-    ol.upsample2x_add(p16.t, f8p.t, u8, B=K, h=h, w=w, C=up[0], skip_group=(Kc, wstride * h8 * w8) if G > 1 else None)
+    ol.upsample2x_add(p16.t, f8p.t, u8, B=K, h=h, w=w, C=up[0], skip_group=(sgrp, wstride * h8 * w8) if G > 1 else None)
     u8 = Act(u8, K, h8, w8, up[0])
     t1 = P.conv('mask_decoder.up_16_8.out_conv.conv1', u8, relu_in=True, act=O.ACT_RELU)
     ds = P.conv('mask_decoder.up_16_8.out_conv.downsample', u8)
     p8 = P.conv('mask_decoder.up_16_8.out_conv.conv2', t1, res=ds, name='p8')
     u4 = P.buf('u4', (K, h4, w4, up[1]))
-    ol.upsample2x_add(p8.t, f4p.t, u4, B=K, h=h8, w=w8, C=up[1], skip_group=(Kc, wstride * h4 * w4) if G > 1 else None)
+    ol.upsample2x_add(p8.t, f4p.t, u4, B=K, h=h8, w=w8, C=up[1], skip_group=(sgrp, wstride * h4 * w4) if G > 1 else None)
     u4 = Act(u4, K, h4, w4, up[1])
     t2 = P.conv('mask_decoder.up_8_4.out_conv.conv1', u4, relu_in=True, act=O.ACT_RELU)
     p4 = P.conv('mask_decoder.up_8_4.out_conv.conv2', t2, res=u4, name='p4')
@@ -821,8 +903,8 @@ def build_segment(eng, K, h, w, update_sensory, pre=False, md=False, clips=1, ws
     if Kc + 1 <= 16:              # aggregation recomputed per bilinear tap inside the up-sampling launch
         # md: the launch also derives what the NEXT frame's pixel fusion needs from these probabilities (MASK_DOWN: the stride-16 means
         # of the object planes and the (mask, others) pairs), into buffers both plans know (Engine.mask_down_bufs)
-        ol.up4_softmax(logits, Dyn('prob'), Dyn('logits_up'), P=Kc + 1, h=h4, w=w4, from_logits=True, clips=G,
-                       mask_down=(eng.mask_down_bufs(K, h, w, G)[1], eng.mask_down_bufs(K, h, w, G)[0], 64) if md else None)
+        ol.up4_softmax(logits, Dyn('prob'), Dyn('logits_up'), P=Kc + 1, h=h4, w=w4, from_logits=True, clips=counts if mixed else G,
+                       mask_down=(eng.mask_down_bufs(K, h, w, gkey)[1], eng.mask_down_bufs(K, h, w, gkey)[0], 64) if md else None)
     else:
         agg = P.buf('agg', (K + 1, h4, w4), F32)
         ol.seg_agg(logits, agg, K=K, hw=h4 * w4)
@@ -837,16 +919,20 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
     dyn out: value bf16 [K,h,w,CV], summ f32 [K,Q,C+1].
     clips > 1: that many clips of K objects in lock step (see build_pixel_fusion): dyn in image0 .., masks = the probabilities
     f32 [clips, K+1, H, W] of the segment in front (clip c's object planes at [c, 1:]), pix_feat = clip 0's slice of the encoder window's
-    output (`wstride` frames between the clips); value / summ / the sensory state hold clips * K objects."""
-    G, Kc = clips, K
-    K = G * Kc
+    output (`wstride` frames between the clips); value / summ / the sensory state hold clips * K objects.
+    clips = (K_0, K_1, ..): a mixed group -- masks = the probabilities f32 [sum(K_c) + clips, H, W] of its segment (clip c's object planes from
+    plane start_c + c + 1 on), the clips are the frames of the STEM launch's mixed form."""
+    G, counts, st, mixed = clip_layout(K, clips)
+    K = st[-1]
+    Kc = counts[0]
     P = Plan(eng, touch=weights_go_cold((H // 16) * (W // 16), K))
-    if G > 1:
+    P.mixed = counts if mixed else None
+    if G > 1 and not mixed:
         P.korder_ref = G
     m, ol = eng.m, P.ol
     h, w = H // 16, W // 16
     CV, CS, CE, Q = m['value_dim'], m['sensory_dim'], m['embed_dim'], m['object_summarizer']['num_summaries']
-    masks_of = (lambda c: Dyn('masks')) if G == 1 else (lambda c: Dyn('masks', 4 * (c * (Kc + 1) + 1) * H * W))
+    masks_of = (lambda c: Dyn('masks')) if G == 1 else (lambda c: Dyn('masks', 4 * (st[c] + c + 1) * H * W))
     assert G == 1 or stem_ok(eng, 'mask_encoder.conv1')
     if stem_ok(eng, 'mask_encoder.conv1'):
         pool = P.buf('pool', (K, H // 4, W // 4, 64))
@@ -854,9 +940,9 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
         iname = lambda c: Dyn('image' if G == 1 else 'image%d' % c)
         SM = O.OpList.STEM_MAX_IMAGES
         for c0 in range(0, G, SM):
-            ol.stem(iname(c0), masks_of(c0), eng.w['mask_encoder.conv1'], pool[c0 * Kc:], h0=h0, w0=w0, H=H, W=W, pad_left=pad_left, pad_top=pad_top,
+            ol.stem(iname(c0), masks_of(c0), eng.w['mask_encoder.conv1'], pool[st[c0]:], h0=h0, w0=w0, H=H, W=W, pad_left=pad_left, pad_top=pad_top,
                     K=Kc, mean=m['pixel_mean'], std=m['pixel_std'], relu=True, more_images=[iname(c) for c in range(c0 + 1, min(G, c0 + SM))],
-                    mask_stride=(Kc + 1) * H * W)
+                    mask_stride=(Kc + 1) * H * W, counts=counts if mixed else None)      # (a mixed group: <= 8 clips, one launch)
     else:
         x8 = P.buf('x8', (K, H, W, 8))
         ol.img_prep(Dyn('image'), Dyn('masks'), x8, h0=h0, w0=w0, H=H, W=W, pad_left=pad_left, pad_top=pad_top, K=K,
@@ -872,7 +958,7 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
         for c in range(G):
             P.conv('mask_encoder.fuser.distributor.x_transform', Act(Dyn('pix_feat', 2 * c * wstride * h * w * m['pixel_dim']), 1, h, w, m['pixel_dim']),
                    out=Act(xt_t[c:c + 1], 1, h, w, wx.cout))
-        xt, xt_group = Act(xt_t, G, h, w, wx.cout), (Kc, h * w)
+        xt, xt_group = Act(xt_t, G, h, w, wx.cout), (counts if mixed else Kc, h * w)
     value = P.fusion_block('mask_encoder.fuser', Act(Dyn('pix_feat'), 1, h, w, m['pixel_dim']), g16, 'fuse',
                            out=Act(Dyn('value'), K, h, w, CV), xt=xt, xt_group=xt_group)
     P.meta['value_done'] = len(ol.recs)               # what follows reads named tensors only (value, masks, sensory): see CUTIE._encode_mask_split
@@ -882,12 +968,12 @@ def build_encode_mask(eng, K, h0, w0, H, W, pad_left, pad_top, deep_update=True,
         ol.gru(vals.t, Dyn('sensory_f32'), Dyn('sensory_bf16'), n=K * h * w, C=CS)
     # object summarizer
     if pre_md:                                           # written by the last segment's up-sampling launch (build_segment(md=True)): these very masks
-        m16 = eng.mask_down_bufs(K, h, w, G)[1]
+        m16 = eng.mask_down_bufs(K, h, w, counts if mixed else G)[1]
     else:
         pair = P.buf('pair', (K, h, w, 8))
         m16 = P.buf('m16', (K, h, w), F32)
         for c in range(G):
-            ol.mask_down(masks_of(c), pair[c * Kc:], m16[c * Kc:], K=Kc, H=H, W=W)
+            ol.mask_down(masks_of(c), pair[st[c]:], m16[st[c]:], K=counts[c], H=H, W=W)
     # two launches instead of five (Engine: '.in_fw0', '.fw2'): value -> [f1 | w1] with the composed weights, then the block-diagonal
     # second layers -> fp32 [feature | weight logits]
     fw1 = P.conv('object_summarizer.in_fw0', value, res=Act(eng.pe_sum(h, w), 1, h, w, 2 * CE), res_bcast=True, act=O.ACT_RELU, name='sum.fw1')

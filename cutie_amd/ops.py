@@ -235,6 +235,21 @@ def pick_tile(M, cout, cin=64, geom=None):
     return best
 
 
+def static_tile(M, cout, cin, kh, c2=0, res=False, side=False, cout1=None):
+    """The tile a conv takes when the tile table has no entry for it: the Cout = 1 kernel where it applies (never with a residual, a second
+    source or a side job), else pick_tile.  ONE statement of the rule for OpList.conv, for the K-order twins of Plan.autotune_convs and for
+    the cuts of a mixed lock-step plan (Plan.conv): a clip's bits follow from the tile its one-clip plan takes.  cout1 (a finished descriptor,
+    whose operands are no longer at hand): was the launch given the Cout = 1 kernel -- that part of the rule does not look at M."""
+    if (cout1_ok(cout, cin, c2, res) and not side) if cout1 is None else cout1:
+        return COUT1_TILE
+    return pick_tile(M, cout, cin, dict(kh=kh, c2=c2))
+
+
+def conv_tile_key(M, cout, cin, kh, stride, relu_in, out_f32, H, W):
+    """Key of a conv geometry in the tile table (cutie_amd/tiles_gfx950.json, Engine.tile_cache): M = B x OH x OW rows, H x W the input."""
+    return (int(M), int(cout), int(cin), int(kh), int(stride), (1 if relu_in else 0) | (2 if out_f32 else 0), int(H), int(W))
+
+
 def aa_taps(n_in, n_out):
     """Tap ranges and weights of F.interpolate(mode='bilinear', align_corners=False, antialias=True) along one axis, rounded as
     torch's CPU kernel rounds them (aten/src/ATen/native/cpu/UpSampleKernel.cpp, _compute_weights_aa for float input): scale and
@@ -281,6 +296,22 @@ def resize_aa_table(H, W, OH, OW):
         tab[r:r + n, 2:2 + w.shape[1]] = w.view(np.int32)
         r += n
     return tab
+
+
+def pack_counts(counts):
+    """The object counts of the clips of a lock-step group as ONE word of 3-bit fields, clip c at bits 3c .. 3c + 2 (include/cutie_hip.h, "mixed
+    forms"): at most 8 clips of 1 .. 7 objects; a zero field ends the list."""
+    counts = [int(k) for k in counts]
+    assert 1 <= len(counts) <= 8 and all(1 <= k <= 7 for k in counts), counts
+    return sum(k << (3 * c) for c, k in enumerate(counts))
+
+
+def clip_starts(counts):
+    """Prefix sums of the counts: clip c holds the objects [starts[c], starts[c + 1])."""
+    st = [0]
+    for k in counts:
+        st.append(st[-1] + int(k))
+    return st
 
 
 class Dyn:
@@ -443,7 +474,7 @@ class OpList:
         M = B * OH * OW
         side = gap_acc is not None or zero is not None
         if tile is None:
-            tile = COUT1_TILE if (cout1_ok(w.cout, C1 + C2, C2, res is not None) and not side) else pick_tile(M, w.cout, C1 + C2, dict(kh=w.kh, c2=C2))
+            tile = static_tile(M, w.cout, C1 + C2, w.kh, C2, res is not None, side)
         if side:
             assert (tile in DMA_TILES or tile in PC_TILES) and not out_f32 and w.cout % 8 == 0 and ldy % 8 == 0, 'GAP accumulation needs an LDS-DMA conv (see conv_side_jobs_ok)'
         part = splitk_scratch(w.weight.device, self.scratch_owner)
@@ -467,13 +498,19 @@ class OpList:
 
     STEM_MAX_IMAGES = 12
 
-    def stem(self, image, masks, w, y, *, h0, w0, H, W, pad_left, pad_top, K, mean, std, relu=True, more_images=(), mask_stride=0):
+    def stem(self, image, masks, w, y, *, h0, w0, H, W, pad_left, pad_top, K, mean, std, relu=True, more_images=(), mask_stride=0, counts=None):
         """IMG_PREP + 7x7 / stride-2 conv (w: PackedConv, Cin padded to 8, Cout 64) + 3x3 / stride-2 max pool (+ ReLU) in one launch.
         more_images (ABI 4, <= 11): further frames of the SAME launch -- frame f reads more_images[f - 1], the masks `mask_stride` floats
-        behind frame f - 1's, and writes behind frame f - 1's output (y holds all frames)."""
+        behind frame f - 1's, and writes behind frame f - 1's output (y holds all frames).
+        counts (the mixed form): the frames are clips with THESE object counts -- clip c's masks are the planes (start_c + c) .. of `masks`
+        (the probability tensor of a mixed group, from its first object plane on), its output the objects start_c ..; K and mask_stride unused."""
         assert w.cout == 64 and w.kh == 7 and w.cin_padded == 8 and H % 16 == 0 and W % 16 == 0
         more = list(more_images)
         assert len(more) < self.STEM_MAX_IMAGES
+        if counts is not None:
+            assert len(counts) == 1 + len(more) and len(counts) > 1
+            ints = [h0, w0, H, W, pad_left, pad_top, max(counts), w.kpad, len(counts), 0, pack_counts(counts)]
+            return self.add(STEM, 1 if relu else 0, ints, list(mean) + list(std), [image, masks, w.weight, w.bias, y] + more)
         ints = [h0, w0, H, W, pad_left, pad_top, K, w.kpad] + ([1 + len(more), int(mask_stride)] if more else [])
         return self.add(STEM, 1 if relu else 0, ints, list(mean) + list(std), [image, masks, w.weight, w.bias, y] + more)
 
@@ -481,9 +518,14 @@ class OpList:
         return self.add(IMG_PREP, 0, [h0, w0, H, W, pad_left, pad_top, K], list(mean) + list(std), [image, masks, y])
 
     def upsample2x_add(self, g, skip, y, *, B, h, w, C, skip_group=None):
-        """skip_group = (objects per clip, pixels between the clips' skip maps): clips in lock step (ABI 4)."""
+        """skip_group = (objects per clip, pixels between the clips' skip maps): clips in lock step (ABI 4); objects per clip a sequence: the
+        clips' own counts (the mixed form, i6)."""
         ints = [B, h, w, C]
-        if skip_group is not None:
+        if skip_group is not None and not isinstance(skip_group[0], int):
+            counts, stride = skip_group
+            assert sum(counts) == B and stride >= 4 * h * w
+            ints += [0, int(stride), pack_counts(counts)]
+        elif skip_group is not None:
             kg, stride = int(skip_group[0]), int(skip_group[1])
             assert kg > 0 and B % kg == 0 and stride >= 4 * h * w
             ints += [kg, stride]
@@ -537,7 +579,17 @@ class OpList:
     def up4_softmax(self, agg, prob, logits_up, *, P, h, w, from_logits=False, mask_down=None, clips=1):
         """from_logits: `agg` holds the K = P - 1 raw logit planes and the aggregation (SEG_AGG) runs inside the launch (P <= 16).
         mask_down = (m16 f32 [K, hw16], pair bf16 [K, h16, w16, pitch], pitch): the launch also writes MASK_DOWN(prob[1:], r = 16).
-        clips > 1 (clips in lock step, ABI 4; the four-pixel forms): every array holds that many clips, P planes out / P - 1 in each."""
+        clips > 1 (clips in lock step, ABI 4; the four-pixel forms): every array holds that many clips, P planes out / P - 1 in each.
+        clips a sequence (the mixed form, i5): the clips' own object counts -- clip c has K_c logit planes in, K_c + 1 planes out, behind those
+        of the clips in front; P is ignored (the largest count + 1 is recorded)."""
+        if not isinstance(clips, int):
+            counts = [int(k) for k in clips]
+            assert from_logits and len(counts) > 1 and h % 4 == 0 and w % 4 == 0 and not UP4_RTK, 'the mixed form: compile-time object counts'
+            ints = [max(counts) + 1, h, w, 0, len(counts), pack_counts(counts)]
+            if mask_down is not None:
+                m16, pair, ints[3] = mask_down
+                return self.add(UP4_SOFTMAX, 1 | 4 | UP4_LANES, ints, [], [agg, prob, logits_up, m16, pair])
+            return self.add(UP4_SOFTMAX, 1, ints, [], [agg, prob, logits_up])
         if mask_down is not None:
             assert from_logits and P <= 8 and h % 4 == 0 and w % 4 == 0
             m16, pair, pitch = mask_down
@@ -618,15 +670,20 @@ class OpList:
         out_proj (needs proj; chain form, see _proj_extras): y is not written; acc_in optional.
         q_pre (chain form, instead of proj): q f32 [K*Q, 256], already projected and scaled by 1/sqrt(32) -- by the ATTN_P2Q launch of the
         previous transformer block (attn_p2q(next_q=...)).
-        clip_objects (chain form, ABI 4): objects per clip when the K objects are those of several clips in lock step (i9)."""
+        clip_objects (chain form, ABI 4): objects per clip when the K objects are those of several clips in lock step (i9); a sequence: the
+        clips' own counts (the mixed form, i10)."""
         hs = 0 if hstride in (None, C // heads) else hstride   # chain form only: elements between the heads' k (and v) inside a pixel row (i8)
+        mixed = []
+        if clip_objects is not None and not isinstance(clip_objects, int):
+            assert out_proj is not None and sum(clip_objects) == K and len(clip_objects) > 1, 'clips in lock step need the chain form'
+            mixed, clip_objects = [pack_counts(clip_objects)], None
         kg = 0 if clip_objects in (None, K) else int(clip_objects)
         assert kg == 0 or (out_proj is not None and K % kg == 0), 'clips in lock step need the chain form'
         if q_pre is not None:
             assert proj is None and acc_in is None and out_proj is not None and logits is not None
             flags, ints, ptrs = self._proj_extras(3 | 16, [K, Q, HW, C, heads, ldkv, voff, 256], [q_pre, kv, logits, None, None], None, out_proj)
             ints[8] = hs
-            return self.add(ATTN_Q2P, flags, ints + [kg], [], ptrs)
+            return self.add(ATTN_Q2P, flags, ints + [kg] + mixed, [], ptrs)
         if proj is not None:
             assert logits is not None
             ldx, ln_out, tail = self._proj(proj)
@@ -634,7 +691,7 @@ class OpList:
             flags, ints, ptrs = self._proj_extras(3, [K, Q, HW, C, heads, ldkv, voff, ldx], [proj['x'], kv, logits, ln_out, y] + tail, acc_in, out_proj)
             assert hs == 0 or out_proj is not None, 'a head stride needs the chain form'
             ints[8] = hs
-            return self.add(ATTN_Q2P, flags, ints + [kg], [], ptrs)
+            return self.add(ATTN_Q2P, flags, ints + [kg] + mixed, [], ptrs)
         assert acc_in is None and out_proj is None
         if logits is not None:
             return self.add(ATTN_Q2P, 1, [K, Q, HW, C, heads, ldkv, voff], [], [q, kv, logits, None, y])
@@ -767,8 +824,13 @@ class OpList:
             idx = self.add(BANK_WRITE, 0, ints, [], ptrs)
         return idx
 
-    def copy2d(self, src, dst, *, rows, rowbytes, src_stride, dst_stride):
+    def copy2d(self, src, dst, *, rows, rowbytes, src_stride, dst_stride, clips=None):
+        """clips (the mixed form, i4): the object counts of the clips of a lock-step group -- destination row r (an object) copies the source
+        row of its CLIP: a per-clip map expanded to one map per object (16-byte granularity)."""
         assert rowbytes % 4 == 0 and src_stride % 4 == 0 and dst_stride % 4 == 0
+        if clips is not None:
+            assert sum(clips) == rows and rowbytes % 16 == 0 and src_stride % 16 == 0 and dst_stride % 16 == 0
+            return self.add(COPY2D, 0, [rows, rowbytes, src_stride, dst_stride, pack_counts(clips)], [], [src, dst])
         return self.add(COPY2D, 0, [rows, rowbytes, src_stride, dst_stride], [], [src, dst])
 
     def axpy(self, x, y, *, n, a=1.0):

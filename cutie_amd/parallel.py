@@ -200,7 +200,8 @@ def run_interleaved(net, clip_ids: Sequence[int], run_clip: Callable, *, streams
     return results
 
 
-def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight: int = 1, lookahead: int = 16, on_frame: Callable = None) -> Dict[int, List]:
+def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight: int = 1, lookahead: int = 16, on_frame: Callable = None,
+                mixed_objects: bool = False) -> Dict[int, List]:
     """Several clips per GPU in LOCK STEP (cutie_amd/inference/lockstep.py): groups of ``lockstep`` clips advance together through ONE launch
     plan per stage -- batch = clips x objects for the pixel fusion, the object transformer, the decoder and the mask encoder, one joint
     encoder window, one memory bank and one look-ahead read-out lane per clip.  Per clip the results are bit-identical to its own
@@ -212,7 +213,8 @@ def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight
 
     clips: [{'frames': sequence of [3, H, W] tensors on the device, 'mask': the first frame's mask, 'objects': its object ids}, ...];
     the clips of a group should share geometry, object count and length (a group whose clips differ still runs -- clip by clip where the
-    states differ, see LockstepCores).  on_frame(clip_index, t, prob, core) receives every result (default: the uint8 object-id masks are
+    states differ, see LockstepCores).  mixed_objects: the clips of a group may hold different numbers of objects (1 .. 7 each) and still share
+    the batched plans (LockstepCores(mixed_objects=True); off: such a group runs clip by clip).  on_frame(clip_index, t, prob, core) receives every result (default: the uint8 object-id masks are
     collected).  Returns {clip index: [per-frame results]}."""
     from .inference.lockstep import LockstepCores
     results: Dict[int, List] = {i: [] for i in range(len(clips))}
@@ -226,7 +228,7 @@ def run_batched(net, cfg, clips: Sequence[Dict], *, lockstep: int = 4, in_flight
         group = groups[gi]
         frames = [clips[i]['frames'] for i in group]
         T = min(len(f) for f in frames)
-        ls = LockstepCores(view, cfg, len(group))
+        ls = LockstepCores(view, cfg, len(group), mixed_objects=mixed_objects)
         for t in range(T):
             hint = {}
             if lookahead > 0 and 0 < t < T - 1:

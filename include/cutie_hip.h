@@ -30,6 +30,20 @@ extern "C" {
 #define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
 #define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
 
+/* Mixed forms (added without a new ABI number: cutie_hip_build_flags() bit 3, value 8, says they are present -- a library from before
+ * would ignore the counts word and run the uniform form, so the callers ask first: cutie_amd/_lib.py has_mixed_lockstep).
+ * Clips in lock step (ABI 4) used to hold the same number of objects each, and every launch that couples the objects of a clip found the
+ * clip of object b as b / objects_per_clip.  In a MIXED group clip c holds K_c objects, 1 <= K_c <= 7, at most 8 clips.  The counts
+ * travel as ONE 24-bit word of 3-bit fields -- clip c at bits 3c .. 3c + 2, a zero field ends the list -- in an integer slot that every
+ * uniform descriptor leaves 0 (no device table: the word is a kernel argument, and every offset a launch needs is a prefix sum over at
+ * most 8 fields, scalar arithmetic where the clip is block-uniform): start_c = K_0 + .. + K_(c-1) is clip c's first object, object b
+ * belongs to the clip with start_c <= b < start_c + K_c.  Per-object tensors stay clip-major and dense (clip c's objects at start_c);
+ * the probability tensor of a mixed group holds sum(K_c) + clips planes, clip c's K_c + 1 planes from plane start_c + c on.
+ * The forms: UPSAMPLE2X_ADD i6, UP4_SOFTMAX i5, ATTN_Q2P (chain form) i10, STEM i10, COPY2D i4 -- see each op.  The uniform encodings keep
+ * their meaning bit for bit and reach the same kernel instantiations (the launchers branch on the word).  CONV has no mixed form: the
+ * per-clip broadcast residual (f0 / f1) of a mixed group is expanded to one map per object by COPY2D i4 and added as an ordinary
+ * residual -- the same values, the conv kernels untouched.  The joint AFF_READOUT (i8) has none either: a mixed group reads every bank
+ * in its clip's own look-ahead lane.  Per clip every mixed launch computes exactly what the uniform launch of that clip alone computes. */
 typedef struct cutie_op {
     int32_t kind;               /* CUTIE_OP_* */
     int32_t flags;              /* op-specific bit flags */
@@ -94,7 +108,8 @@ enum {
     /* UPSAMPLE2X_ADD: y = bilinear_x2(g, align_corners=False) + skip (broadcast over objects)
      * group_modules.py:19-23 + MainToGroupDistributor('add') modules.py:15-18
      * p0=g bf16 [B,h,w,C] p1=skip bf16 [1,2h,2w,C] p2=y bf16 [B,2h,2w,C]   i: 0 B 1 h 2 w 3 C
-     * ABI 4: i4 > 0 = objects per clip (clips in lock step, see CONV): group q = b / i4 adds the skip map at p1 + q * i5 pixels (i5 >= 4hw) */
+     * ABI 4: i4 > 0 = objects per clip (clips in lock step, see CONV): group q = b / i4 adds the skip map at p1 + q * i5 pixels (i5 >= 4hw)
+     * Mixed form: i6 != 0 = the clips' object counts (3-bit fields, sum = B; i4 = 0): object b adds the map of ITS clip, p1 + clip(b) * i5 pixels */
     CUTIE_OP_UPSAMPLE2X_ADD = 4,
     /* AREA_DOWN: r x r mean (F.interpolate mode='area', integer ratio) on NHWC bf16|f32 input
      * group_modules.py:26-30 (modules.py:59-60)
@@ -136,7 +151,11 @@ enum {
      * flags&8 (with flags&1): the kernels with a run-time object count (A/B switch; default: one instantiation per K = 1..7, whose loads are
      *      all in flight together -- same bits)
      * ABI 4: i4 > 1 = clips per launch (grid.y; the four-pixel forms only): clip c reads logits p0 + c*K*h*w and writes prob / logits_up
-     *      + c*(K+1)*16hw, m16 + c*K*(hw/16), pair + c*K*(hw/16)*i3 -- per clip exactly the one-clip launch */
+     *      + c*(K+1)*16hw, m16 + c*K*(hw/16), pair + c*K*(hw/16)*i3 -- per clip exactly the one-clip launch
+     * Mixed form (with flags&1, without flags&2 / flags&8): i5 != 0 = the object counts of the i4 clips (3-bit fields); i0 = the largest count + 1.
+     *      Clip c (grid.y, block-uniform) reads its K_c logit planes at p0 + start_c * h*w and writes its K_c + 1 planes at prob / logits_up
+     *      + (start_c + c) * 16hw, m16 + start_c * (hw/16), pair + start_c * (hw/16) * i3; every block branches ONCE into the code instantiated
+     *      for K_c objects, so a clip runs the instructions of its one-clip launch */
     CUTIE_OP_UP4_SOFTMAX = 11,
     /* MASK_MERGE: build the per-object mask planes of a frame with an input mask
      * inference_core.py:259-300.  plane t: src[t] >= 0 -> (idx==src[t]) [idx mode] / fmask[src[t]] [float
@@ -188,7 +207,9 @@ enum {
      * flags&16 (chain form, instead of flags&4 and of the projection operands): p0 = q f32 [K*Q, 256], already projected and scaled by
      *      1/sqrt(32) (ATTN_P2Q flags&16 of the previous transformer block produces it); p3, p5..p11 unused
      * ABI 4 (chain form): i9 > 0 = objects per clip (clips in lock step): the foreground mask of object k is decided among the i9 objects
-     *      of its own clip (logit planes (k / i9) * i9 ...), as object_transformer.py:179-205 aggregates over one video's objects */
+     *      of its own clip (logit planes (k / i9) * i9 ...), as object_transformer.py:179-205 aggregates over one video's objects
+     * Mixed form (chain form): i10 != 0 = the clips' object counts (3-bit fields, sum = K; i9 = 0): object k's mask is decided among the
+     *      K_c objects of its clip (logit planes start_c ..) */
     CUTIE_OP_ATTN_Q2P = 18,
     /* ATTN_SELF: 16x16 self attention per object  transformer_layers.py:12-41
      * p0=qk f32 [K,Q,ldqk] (q at +0, k at +C) p1=v f32 [K,Q,ldv] p2=y f32 [K,Q,C]
@@ -268,7 +289,10 @@ enum {
     /* MEMSET32: fill n 32-bit words with value i[1]   p0=dst   i: 0 n 1 value */
     CUTIE_OP_MEMSET32 = 27,
     /* COPY2D: rows x rowbytes strided device copy (bank append / compaction; replaces torch.cat,
-     * kv_memory_store.py:7-16)   p0=src p1=dst   i: 0 rows 1 rowbytes(mult of 4) 2 src_stride 3 dst_stride */
+     * kv_memory_store.py:7-16)   p0=src p1=dst   i: 0 rows 1 rowbytes(mult of 4) 2 src_stride 3 dst_stride
+     * Mixed form: i4 != 0 = the object counts of the clips of a lock-step group (3-bit fields, sum = rows): destination row r -- an object --
+     *      is a copy of source row clip(r): a per-clip map (x_transform of MainToGroupDistributor, group_modules.py:112-115) expanded to one map
+     *      per object.  rowbytes, both strides and both pointers multiples of 16 */
     CUTIE_OP_COPY2D = 28,
     /* AXPY: y[i] += a * x[i] (f32)  streaming object-memory sum, memory_manager.py:264-269
      * p0=x p1=y  i: 0 n  f: 0 a */
@@ -561,7 +585,10 @@ enum {
      * f: 0-2 mean 3-5 std   flags&1: ReLU (before or after the pool: the same)
      * ABI 4: i8 > 1 = frames per launch (<= 12; grid.y): frame f > 0 reads the image at p[4 + f] (p5 .. p15) and the masks at p1 + f * i9 floats and
      *      writes y + f * K*(H/4)*(W/4)*64 -- the frames of a look-ahead encoder window, or the clips of a lock-step group (one image + K masks each),
-     *      in one launch that fills the chip (a 480p frame is 210 blocks: a partial round of its own); per frame exactly the one-frame launch */
+     *      in one launch that fills the chip (a 480p frame is 210 blocks: a partial round of its own); per frame exactly the one-frame launch
+     * Mixed form: i10 != 0 = the object counts of the i8 clips (3-bit fields; needs p1; i6 = the largest count = grid.z; i9 unused): clip f has
+     *      K_f objects, its masks are the planes p1 + (start_f + f) * H*W .. (p1 = the first object plane of a mixed group's probability
+     *      tensor) and it writes y + start_f * (H/4)*(W/4)*64; blocks with z >= K_f return */
     CUTIE_OP_STEM = 41,
     /* BANK_WRITE: the contiguous copies and fills of one memory insertion (memory_manager.py:210-296, kv_memory_store.py:55-149: the
      * reference torch.cat's every tensor of the bank; here a frame's keys / shrinkage / selection / per-object values go to their slot)
@@ -588,7 +615,7 @@ int cutie_op_struct_size(void);
 /* bit 0: the library was built with -DCUTIE_DIAG (make DIAG=1): measured-and-lost kernel variants (ATTN_P2Q flags&32) are present.
  * The product library returns 0 and rejects those descriptors.
  * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
- * JPEG decode stages, are present (both came without a new ABI number). */
+ * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

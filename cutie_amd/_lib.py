@@ -81,6 +81,12 @@ def has_mixed_lockstep():
     return bool(load().cutie_hip_build_flags() & 8)
 
 
+def has_track_stats():
+    """Does the loaded library know PROB_TO_ID flags == 1024, the per-object track statistics?  Added without a new ABI number; a library
+    from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing (ResultSaver tracks=...)."""
+    return bool(load().cutie_hip_build_flags() & 16)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

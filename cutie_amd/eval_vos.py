@@ -17,6 +17,9 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
                                             counted on the GPU from the id planes while the videos run (inference/utils/davis_metrics.py); writes
                                             global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output;
                                             the first and last ground-truth frame of a video are left out unless --score-all-frames)
+        [--tracks]                         (one row per object and saved frame -- area, box, centroid, confidence -- counted on the GPU from the id
+                                            plane and the probabilities (inference/utils/track_report.py): OUT/tracks/<video>/tracks.json and
+                                            tracks_mot.txt; with --sizes the confidence is null; not for long-id (RGB) masks)
 
 BURST (a --dataset name containing "burst", e.g. burst-val | burst-test; eval_vos.py:42-54,108,156-157,171-172 of the reference):
     python -m cutie_amd.eval_vos --dataset burst-val --images DIR/frames/val --json DIR/val/first_frame_annotations.json --output OUT
@@ -44,6 +47,7 @@ from .inference.inference_core import InferenceCore
 from .inference.utils.burst_utils import BURSTResultHandler
 from .inference.utils.davis_metrics import SequenceScorer, global_line, write_results
 from .inference.utils.results_utils import EGRESS_MODES, OVERLAY_MODES, ResultSaver, make_zip
+from .inference.utils.track_report import TrackReport
 
 log = logging.getLogger()
 
@@ -118,8 +122,15 @@ def _take(windows, dev, lookahead):
 
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
-           score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host') -> ResultSaver:
-    """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer."""
+           score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', tracks=False,
+           tracks_output_root=None) -> ResultSaver:
+    """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer.
+    tracks (--tracks): the saver gets the video's own TrackReport and writes it into tracks_output_root/<video>/ when it ends."""
+    report = None
+    if tracks:
+        if vid_reader.use_long_id:
+            raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no track report')
+        report = TrackReport(vid_reader.vid_name)
     scorer = None
     if score_gt is not None:
         if vid_reader.use_long_id:
@@ -129,6 +140,7 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
                        use_long_id=vid_reader.use_long_id, palette=vid_reader.get_palette(), visualize=visualize,
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
                        score_output_root=score_output_root, egress=egress, scorer=scorer, overlay=overlay,
+                       tracks=report, tracks_output_root=tracks_output_root,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -143,6 +155,8 @@ def _with_json(stats, saver):
         stats['video_json'] = saver.video_json
     if saver.scorer is not None:                 # a scored run: the video's counts and J / F per frame and object (None: nothing was scored)
         stats['scores'] = saver.scores
+    if saver.tracks is not None:                 # --tracks: the video's report (what tracks.json holds), so that sharded ranks can gather them
+        stats['tracks'] = saver.tracks.as_dict()
     return stats
 
 
@@ -153,8 +167,12 @@ def _save(saver, prob, info, last_frame, save_all):
 
 
 def _frame_kw(saver, info) -> Dict:
-    """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feeds(keep_u8s=...)``)."""
-    return {'image_u8': info.get('image_u8')} if saver.overlay == 'device' else {}
+    """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feeds(keep_u8s=...)``).
+    tracks: the frame's 1-based position in the video as the reader orders it."""
+    kw = {'image_u8': info.get('image_u8')} if saver.overlay == 'device' else {}
+    if saver.tracks is not None and info.get('time_index') is not None:
+        kw['frame_index'] = int(info['time_index']) + 1
+    return kw
 
 
 def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
@@ -187,7 +205,8 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict:
+                  read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
+                  tracks=False, tracks_output_root=None) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -198,7 +217,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode,
-                   overlay=overlay)
+                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         feeds = _feeds([vid_reader], network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
@@ -212,7 +231,8 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
-                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1) -> Dict:
+                             read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
+                             tracks=False, tracks_output_root=None) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -237,7 +257,8 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
         raise ValueError('process_video_multiscale: the readers must be of the same video (name and length)')
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
-                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay)
+                   egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay,
+                   tracks=tracks, tracks_output_root=tracks_output_root)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -302,7 +323,7 @@ def lockstep_groups(mine, readers, lockstep, mixed=False):
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
                             ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                            mixed_objects=False) -> Dict[int, Dict]:
+                            mixed_objects=False, tracks=False, tracks_output_root=None) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key`` (mixed_objects: ``lockstep_key_mixed``
     -- their object counts may differ); they may differ in length -- the
@@ -315,7 +336,8 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     dev = network.device
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
-                     score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay) for c, rd in enumerate(vid_readers)]
+                     score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay, tracks=tracks,
+                     tracks_output_root=tracks_output_root) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -398,6 +420,10 @@ def arg_parser() -> argparse.ArgumentParser:
                          '(inference/data/png_packet.py; a file the parser declines is decoded by PIL); default host: PIL on the issuing thread')
     ap.add_argument('--score-all-frames', action='store_true',
                     help='--score: also score the first and the last ground-truth frame of a video (the DAVIS protocol leaves them out)')
+    ap.add_argument('--tracks', action='store_true',
+                    help='per video OUT/tracks/<video>/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every '
+                         'saved frame, counted on the GPU (cutie_amd/inference/utils/track_report.py).  With --sizes the confidence is null.  '
+                         'Not for long-id (RGB) masks')
     return ap
 
 
@@ -433,6 +459,8 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
             ap.error('--score: long-id datasets (RGB masks) cannot be scored: J&F is counted on uint8 id planes')
     elif args.gt is not None or args.score_all_frames:
         ap.error('--gt and --score-all-frames belong to --score')
+    if getattr(args, 'tracks', False) and args.masks is not None and _long_id_masks(args.masks):
+        ap.error('--tracks: long-id datasets (RGB masks) have no uint8 id plane to count on')
     if getattr(args, 'decode_batch', 1) < 1:
         ap.error('--decode-batch is at least 1')
     if args.sizes is not None:
@@ -474,6 +502,8 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
     score = bool(getattr(args, 'score', False))
     if score:
         common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames), gt_decode=args.gt_decode)
+    if getattr(args, 'tracks', False):                        # (off: no argument is passed and no launch is issued)
+        common.update(tracks=True, tracks_output_root=path.join(args.output, 'tracks'))
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is

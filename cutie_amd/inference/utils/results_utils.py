@@ -37,7 +37,14 @@ composes the frame from the probability planes, the uint8 frame and the id plane
 the JPEG stage above encodes the composed frame (no id plane); the soft masks (flags == 512) and the alpha matte are uint8 planes that
 go through the PNG stage and leave as greyscale PNGs.  Files: ``<output_root>/<video>/visualization/<mode>/<frame>.jpg``,
 ``.../soft_masks/<object id>/<frame>.png``, ``.../alpha/<frame>.png``.  Status blocks and stream heads ride pinned copies in front of
-one event per frame; the writer thread wraps and writes.  The full-size float planes never leave the device."""
+one event per frame; the writer thread wraps and writes.  The full-size float planes never leave the device.
+
+``tracks`` (not in the reference; DESIGN.md section 19, utils/track_report.py): one row per object and frame -- area, box, centroid,
+confidence.  Behind the id stage of every path -- with egress='host' before the plane's ``.cpu()`` -- one op (PROB_TO_ID flags == 1024,
+csrc/tracks.hip) reads the uint8 id plane the PNG is written from and, where the frame has them, the probabilities ``step`` returned (at
+the model's resolution, in place); the table of 48 bytes per object rides a pinned copy with an event behind it, and the writer thread
+hands it to the ``TrackReport``.  ``end`` writes ``tracks.json`` and ``tracks_mot.txt`` into ``<tracks_output_root>/<video>/``.
+``process_merged`` has S probability sources and no single model resolution: it passes none, and the confidence is null there."""
 import logging
 import os
 import shutil
@@ -139,6 +146,19 @@ class _MatteBuffers:
         self.event = torch.cuda.Event() if on_gpu else _NoEvent()
 
 
+class _TrackBuffers:
+    """What one frame in flight owns of the track report: the table of up to 255 objects on the device, its pinned twin and the event
+    recorded behind the copy."""
+
+    def __init__(self, device):
+        from ... import ops as O
+        words = O.OpList.TRACK_MAX_OBJECTS * O.OpList.TRACK_WORDS
+        on_gpu = torch.device(device).type == 'cuda'
+        self.dev = torch.empty(words, dtype=torch.int32, device=device)
+        self.host = torch.empty(words, dtype=torch.int32).pin_memory() if on_gpu else torch.empty(words, dtype=torch.int32)
+        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
+
+
 class _NoEvent:
     def record(self):
         pass
@@ -165,13 +185,15 @@ class _Job:
     matte: Optional[_MatteBuffers] = None    # vis_modes / soft_masks / alpha_matte: the frame's composed outputs arrive in these
     matte_objects: Tuple = ()                # ... the object id of every soft-mask plane, in plane order
     matte_keep: Tuple = ()                   # ... what the launches read (planes, frame, tables), kept until the writer is done with the frame
+    tracks: Optional[_TrackBuffers] = None   # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
+    track_meta: Optional[Tuple] = None       # ... (frame index, object ids of the rows, H, W): the frame is reported
 
 
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
-                 target_objects=None, layer=None):
+                 target_objects=None, layer=None, tracks=None, tracks_output_root=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -192,7 +214,20 @@ class ResultSaver:
         frame (``image_u8`` or ``path_to_image`` of ``process``); a ``use_long_id`` saver refuses them.  ``target_objects``: the object
         ids that 'popup', 'layer' and the matte keep (default: all objects of the frame; ids that are not -- yet, or any more -- objects
         are left out).  ``layer``: the RGBA image of mode 'layer' (a PIL image, a uint8 [h, w, 4] array or a file name), resized once
-        to the output size with PIL and uploaded once."""
+        to the output size with PIL and uploaded once.
+        ``tracks`` (not in the reference; a utils/track_report.py TrackReport, see the module docstring): every frame's area, box,
+        coordinate sums and confidence per object are counted on the device and reported to it; ``end`` writes its two files into
+        ``tracks_output_root``/<video>/ (default: <output_root>/tracks).  Needs ``processor``; long ids (RGB masks) have no uint8 plane."""
+        if tracks is not None and use_long_id:
+            raise ValueError('tracks: the statistics are counted on uint8 id planes; a use_long_id saver (RGB masks) cannot report them')
+        if tracks is not None and processor is None:
+            raise ValueError('tracks needs the processor (its device and object table)')
+        self.tracks = tracks
+        self.tracks_output_root = tracks_output_root if tracks_output_root is not None else path.join(output_root, 'tracks')
+        self._track_free: Queue = Queue()
+        self._track_allocated, self._track_objs, self._track_count = 0, {}, 0
+        if tracks is not None and not tracks.video_name:
+            tracks.video_name = video_name
         vis_modes = tuple(vis_modes)
         unknown = [m for m in vis_modes if m not in VIS_MODES]
         if unknown or len(set(vis_modes)) != len(vis_modes):
@@ -253,11 +288,13 @@ class ResultSaver:
         self.thread.start()
 
     def process(self, prob: torch.Tensor, frame_name: str, resize_needed: bool = False, shape: Optional[Tuple[int, int]] = None,
-                last_frame: bool = False, path_to_image: str = None, image_u8: Optional[torch.Tensor] = None):
+                last_frame: bool = False, path_to_image: str = None, image_u8: Optional[torch.Tensor] = None, *, frame_index: Optional[int] = None):
         """``image_u8`` (overlay='device'): the frame as uint8 [H, W, 3] at the output size, on the device or on the host; without it
-        ``path_to_image`` is decoded with PIL and uploaded (slow: see the module docstring)."""
+        ``path_to_image`` is decoded with PIL and uploaded (slow: see the module docstring).
+        ``frame_index`` (tracks): the frame's 1-based position in the video; without it the running count of reported frames."""
         if self.egress == 'device':
-            return self._process_device(prob, frame_name, resize_needed, shape, last_frame, path_to_image, image_u8)
+            return self._process_device(prob, frame_name, resize_needed, shape, last_frame, path_to_image, image_u8, frame_index=frame_index)
+        model_prob = prob                        # (tracks: the confidence is taken at the model's resolution)
         if resize_needed:
             prob = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0]
         out_dtype = torch.int32 if self.use_long_id else torch.uint8
@@ -277,9 +314,61 @@ class ResultSaver:
         ov = self._queue_overlay(None, mask, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
         if self._matte_on:
             ov.update(self._queue_matte(prob, tuple(prob.shape[1:]), mask, all_ids, path_to_image, image_u8))
+        if self.tracks is not None:
+            ov.update(self._queue_tracks(mask, all_ids, model_prob, None, frame_index))
         self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, all_ids,
                             prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, **ov))
+
+    # ---- tracks -----------------------------------------------------------------------------------------------------------------
+    def _lut_device(self, P, dev):
+        """plane -> object id as int32 [P] on the device (PROB_TO_ID's lut; changes when objects come or go, not per frame)"""
+        lut = [0] * P
+        for tmp_id, obj in self.object_manager.tmp_id_to_obj.items():
+            if tmp_id < P:
+                lut[tmp_id] = int(obj.id)
+        lut_dev = self._luts.get(tuple(lut))
+        if lut_dev is None:
+            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
+        return lut_dev
+
+    def _queue_tracks(self, ids, all_ids, prob, lut_dev, frame_index) -> dict:
+        """Queue the track statistics of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), the pinned copy of the table (48 bytes per object) and an event.  ``prob``: f32 [P, h, w] as ``step`` returned it, or
+        None (no confidence); ``lut_dev``: its lut on the device when the caller has it.  -> the _Job fields.  Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        self._track_count += 1
+        meta = (self._track_count if frame_index is None else int(frame_index), list(all_ids), H, W)
+        n = len(all_ids)
+        if n == 0:                               # a frame without objects is reported with no rows: nothing to launch
+            return dict(track_meta=meta)
+        if n > O.OpList.TRACK_MAX_OBJECTS:
+            raise ValueError(f'tracks: {n} objects, at most {O.OpList.TRACK_MAX_OBJECTS} per frame')
+        objs = self._track_objs.get(tuple(all_ids))
+        if objs is None:                         # (changes when objects come or go, not per frame)
+            objs = self._track_objs[tuple(all_ids)] = torch.tensor(list(all_ids), dtype=torch.int32).to(dev)
+        if prob is not None:
+            if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
+                prob = prob.to(device=dev, dtype=torch.float32).contiguous()
+            if lut_dev is None:
+                lut_dev = self._lut_device(int(prob.shape[0]), dev)
+        try:
+            b = self._track_free.get_nowait()
+        except Empty:
+            if self._track_allocated < self.queue.maxsize + 2:
+                self._track_allocated += 1
+                b = _TrackBuffers(dev)
+            else:
+                b = self._track_free.get()       # the next set the writer gives back
+        words = n * O.OpList.TRACK_WORDS
+        ol = O.OpList()
+        ol.track_stats(ids, objs, b.dev[:words], prob=prob, lut=lut_dev if prob is not None else None)
+        ol.run()
+        b.host[:words].copy_(b.dev[:words], non_blocking=True)
+        b.event.record()
+        return dict(tracks=b, track_meta=meta)
 
     # ---- egress='device' --------------------------------------------------------------------------------------------------------
     def _take(self, H, W, device, png=True) -> _EgressBuffers:
@@ -493,7 +582,7 @@ class ResultSaver:
         self._wstream.synchronize()
         return rest.numpy().tobytes()
 
-    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame, path_to_image=None, image_u8=None):
+    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame, path_to_image=None, image_u8=None, *, frame_index=None):
         from ... import ops as O
         core = self.processor
         dev = core.network.device
@@ -532,6 +621,8 @@ class ResultSaver:
         ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
         if self._matte_on:
             ov.update(self._queue_matte(prob, (H, W), b.ids, all_ids, path_to_image, image_u8))
+        if self.tracks is not None:
+            ov.update(self._queue_tracks(b.ids, all_ids, prob, lut_dev, frame_index))
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         if rle:
             b.rle_host.copy_(b.rle_dev, non_blocking=True)
@@ -545,14 +636,16 @@ class ResultSaver:
 
     # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
     def process_merged(self, probs, frame_name: str, shape: Tuple[int, int], last_frame: bool = False, path_to_image: str = None, *,
-                       id_maps=None, image_u8: Optional[torch.Tensor] = None):
+                       id_maps=None, image_u8: Optional[torch.Tensor] = None, frame_index: Optional[int] = None):
         """One frame of a multi-scale run (not in the reference, whose protocol is one run per size with ``save_scores`` and
         scripts/merge_multi_scale.py afterwards): ``probs`` = the members' [K+1, h_s, w_s] probabilities of the frame,
         every one resampled to ``shape``, quantised to uint8 and summed as the file route does, argmax + remap -- ONE kernel (PROB_TO_ID
         flags&16) that reads the members' views in place; no full-size plane and no score file exists.  egress='host': the id plane
         (uint8, int32 with long ids) is copied to the host and the writer thread does the rest (visualize, long ids); egress='device':
         the same op carries the PNG stage, as in ``process``.  ``id_maps``: the members' {tmp id: object id} tables -- they must be
-        equal (the members see the same first masks in the same order); this saver's object manager is the first member's."""
+        equal (the members see the same first masks in the same order); this saver's object manager is the first member's.
+        ``tracks``: area, box and centroid of the merged plane are reported; the merge has S probability sources and no single model
+        resolution, so no probabilities are passed and the confidence is null.  ``frame_index``: as in ``process``."""
         from ... import ops as O
         if self.json_style == 'burst':
             raise ValueError('process_merged: BURST has no multi-scale protocol (no json is written from merged scales)')
@@ -595,6 +688,8 @@ class ResultSaver:
             if self.scorer is not None:
                 self.scorer.add(frame_name, ids)
             ov = self._queue_overlay(None, ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+            if self.tracks is not None:
+                ov.update(self._queue_tracks(ids, all_ids, None, None, frame_index))
             self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame, **ov))
             return
         if self._scratch is None or self._scratch[0] != (H, W):
@@ -605,9 +700,12 @@ class ResultSaver:
         if self.scorer is not None:
             self.scorer.add(frame_name, b.ids)
         ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        has_overlay = bool(ov)
+        if self.tracks is not None:
+            ov.update(self._queue_tracks(b.ids, all_ids, None, None, frame_index))
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
         b.event.record()
-        self.queue.put(_Job(self, None, frame_name, path_to_image if ov else None, all_ids, last_frame=last_frame, egress=b, **ov))
+        self.queue.put(_Job(self, None, frame_name, path_to_image if has_overlay else None, all_ids, last_frame=last_frame, egress=b, **ov))
 
     def _fetch(self, b: _EgressBuffers) -> bytes:
         """Writer thread: the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
@@ -648,8 +746,11 @@ class ResultSaver:
         self.thread.join()
         self._free, self._allocated, self._scratch = Queue(), 0, None
         self._matte_free, self._matte_allocated, self._matte_png_scratch = Queue(), 0, None
+        self._track_free, self._track_allocated = Queue(), 0
         if self.scorer is not None:
             self.scores = self.scorer.finish()
+        if self.tracks is not None:
+            self.tracks.write(path.join(self.tracks_output_root, self.video_name))
 
 
 def _host_rle(ids: np.ndarray, all_obj_ids) -> dict:
@@ -718,7 +819,15 @@ def _writer(queue: Queue):
                 np.savez_compressed(path.join(sc_dir, job.frame_name[:-4] + '.npz'), prob=job.prob.numpy())
             if job.matte is not None:
                 s._write_matte(job)
-            segment = s._fetch_jpeg(job.overlay) if job.overlay is not None else None
+            if job.track_meta is not None:                         # tracks: the frame's table has landed behind its event
+                index, objs, H, W = job.track_meta
+                if job.tracks is not None:
+                    job.tracks.event.synchronize()
+                    table = job.tracks.host[:len(objs) * 12].numpy().reshape(-1, 12).copy()
+                else:
+                    table = np.zeros((0, 12), dtype=np.int32)
+                s.tracks.add(job.frame_name, index, table, objs, H, W)
+            segment =s._fetch_jpeg(job.overlay) if job.overlay is not None else None
             if segment is not None:                                # overlay='device': wrap the finished segment, no PIL
                 vis_dir = path.join(s.visualize_output_root, s.video_name)
                 os.makedirs(vis_dir, exist_ok=True)
@@ -750,6 +859,8 @@ def _writer(queue: Queue):
                 job.saver._free.put(b)
             if job.matte is not None:
                 job.saver._matte_free.put(job.matte)
+            if job.tracks is not None:
+                job.saver._track_free.put(job.tracks)
         queue.task_done()
 
 

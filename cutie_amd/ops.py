@@ -1031,6 +1031,61 @@ class OpList:
         return self.add(PROB_TO_ID, 64, [0, H, W, 0, 0, radius, 0, 0, min(scratch.numel(), (1 << 31) - 1), n], [],
                         [None, None, pred, gt, None, scratch, objs, counts])
 
+    TRACK_MAX_OBJECTS = 255
+    TRACK_WORDS = 12          # int32 words of a table row (csrc/tracks.hip TRK_WORDS)
+
+    def track_stats(self, ids_plane, obj_ids, table, prob=None, lut=None):
+        """PROB_TO_ID flags == 1024 (ABI 11, form added; include/cutie_hip.h): ids_plane uint8 [H, W] (contiguous) -> table int32 [n, 12],
+        WRITTEN by the launch: per object of ``obj_ids`` (a sequence of ints, or an int32 tensor of them on the device, which is not
+        inspected) area, xmin, ymin, xmax, ymax, sum of x, sum of y (64-bit pairs, low word first), and from ``prob`` (f32 [P, h, w], any
+        plane / row strides, last dimension contiguous: the un-padded view `step` returns is read in place) with ``lut`` (int32 [P] on
+        the device, plane -> object id) the number of samples the object's plane won and the sum of q16 of the winning probability
+        (64-bit).  Entries outside 1 .. 255 are absent objects, a repeated entry gets the first one's row; an object without a pixel
+        has area 0, xmin = W, ymin = H, xmax = ymax = -1.  table 16-byte aligned.  The caller keeps ``prob`` alive until the launch
+        has run (the list holds it)."""
+        # the form came without a new ABI number (an injected interpreter of the tests has no library; a missing library fails when the list runs)
+        if not getattr(_lib._executor, 'is_mock', False):
+            try:
+                known = _lib.has_track_stats()
+            except _lib.HipLibraryError:
+                known = True
+            if not known:
+                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no track statistics, PROB_TO_ID flags == 1024); rebuild it.')
+        if ids_plane.dtype != torch.uint8 or ids_plane.dim() != 2 or not ids_plane.is_contiguous():
+            raise ValueError(f'track_stats: ids_plane is a contiguous uint8 [H, W], not {ids_plane.dtype} {tuple(ids_plane.shape)}')
+        H, W = int(ids_plane.shape[0]), int(ids_plane.shape[1])
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f'track_stats: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        if torch.is_tensor(obj_ids):
+            if obj_ids.dtype != torch.int32 or obj_ids.dim() != 1 or not obj_ids.is_contiguous():
+                raise ValueError('track_stats: obj_ids on the device are a contiguous int32 [n]')
+            n, objs = int(obj_ids.numel()), obj_ids
+        else:
+            listed = [int(v) for v in obj_ids]
+            n, objs = len(listed), None
+        if not 0 <= n <= self.TRACK_MAX_OBJECTS:
+            raise ValueError(f'track_stats: {n} objects, 0 .. {self.TRACK_MAX_OBJECTS}')
+        if table.dtype != torch.int32 or table.numel() != n * self.TRACK_WORDS or not table.is_contiguous():
+            raise ValueError(f'track_stats: table is a contiguous int32 [{n}, {self.TRACK_WORDS}]')
+        if (prob is None) != (lut is None):
+            raise ValueError('track_stats: prob and lut come together')
+        ints = [0, H, W, 0, 0, 0, 0, 0, 0, n]
+        if prob is not None:
+            if prob.dim() != 3 or prob.dtype != torch.float32 or prob.stride(2) != 1 or prob.shape[1] < 1 or prob.shape[2] < 1:
+                raise ValueError('track_stats: prob is f32 [P, h, w] with a contiguous last dimension')
+            P, h, w = (int(v) for v in prob.shape)
+            if not 1 <= P <= 256:
+                raise ValueError(f'track_stats: {P} probability planes, 1 .. 256')
+            if h * w >= 1 << 31 or max(prob.stride(0), prob.stride(1)) >= 1 << 31 or prob.stride(1) < w:
+                raise ValueError('track_stats: h * w < 2^31, strides are 32-bit and a row stride covers the row')
+            if lut.dtype != torch.int32 or lut.numel() != P or not lut.is_contiguous():
+                raise ValueError(f'track_stats: lut is a contiguous int32 [{P}]')
+            ints[0], ints[3], ints[4], ints[5], ints[6] = P, int(prob.stride(0)), int(prob.stride(1)), h, w
+        if objs is None and n:
+            objs = torch.tensor(listed, dtype=torch.int32).to(ids_plane.device)
+            self.keep.append(objs)
+        return self.add(PROB_TO_ID, 1024, ints, [], [prob, lut, ids_plane, None, None, None, objs if n else None, table if n else None])
+
     JPEG_ENC_BLOCK_WORDS = 52     # JPG_BLOCK_WORDS (csrc/jpeg_enc.hip): a coded block is at most 22 + 63 * 26 = 1660 bits
 
     @staticmethod

@@ -49,6 +49,7 @@ from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
 from .inference.utils.results_utils import EGRESS_MODES, VIS_MODES, ResultSaver
+from .inference.utils.track_report import TrackReport
 
 IMAGE_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
 
@@ -151,12 +152,13 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
-                  layer=None, decode_batch: int = 1) -> Dict:
+                  layer=None, decode_batch: int = 1, tracks: bool = False) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
     joins the result.  vis_modes / soft_masks / alpha_matte / target_objects / layer: ResultSaver's (the module docstring); 'folders' of
-    the result names the folders they wrote."""
+    the result names the folders they wrote.  tracks: area, box, centroid and confidence of every object on every frame, counted on the
+    device (inference/utils/track_report.py): output_dir/tracks/tracks.json and tracks_mot.txt, and 'tracks' (the json's content) in the result."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -240,7 +242,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
             scorer = SequenceScorer(gt_dir, '', dev, skip_first_last=False, gt_decode=gt_decode)
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
                             palette=palette, processor=processor, egress=egress, scorer=scorer, vis_modes=vis_modes, soft_masks=soft_masks,
-                            alpha_matte=alpha_matte, target_objects=target_objects, layer=layer)
+                            alpha_matte=alpha_matte, target_objects=target_objects, layer=layer,
+                            tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None)
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -254,7 +257,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                                         else processor.step(frame, next_image=hint), dev.type == 'cuda')
                 total += secs
                 saver.process(prob, name, resize_needed=False, shape=None, last_frame=(n == len(src) - 1), path_to_image=None,
-                              image_u8=frame_u8(frame, u8) if want_u8 else None)
+                              image_u8=frame_u8(frame, u8) if want_u8 else None, frame_index=n + 1)
                 cleanups += check_to_clear_non_permanent_memory(processor, mem_cleanup_ratio, mem_get_info)
                 n += 1
         finally:
@@ -263,6 +266,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     out = {'frames': n, 'seconds': total, 'cleanups': cleanups, 'num_objects': num_objects, 'processor': processor}
     if scorer is not None:
         out['scores'] = saver.scores
+    if tracks:
+        out['tracks'] = saver.tracks.as_dict()
     if vis_modes or soft_masks or alpha_matte:
         out['folders'] = ([path.join(output_dir, 'visualization', m) for m in vis_modes] + ([path.join(output_dir, 'soft_masks')] if soft_masks else []) +
                           ([path.join(output_dir, 'alpha')] if alpha_matte else []))
@@ -293,6 +298,8 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
                     help='--gt: device = the ground-truth PNGs are decoded on the GPU (default host: PIL)')
     ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
+    ap.add_argument('--tracks', action='store_true',
+                    help='OUT/tracks/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every frame, counted on the GPU')
     return ap
 
 
@@ -316,7 +323,7 @@ def main():
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
                       mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
-                      decode_batch=args.decode_batch)
+                      decode_batch=args.decode_batch, tracks=args.tracks)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

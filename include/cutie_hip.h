@@ -478,7 +478,36 @@ enum {
      *  The launcher refuses, each with its own message and before any launch: OH, OW < 1 (and H, W < 1 where planes are read),
      *    H * W, 3 * OH * OW or P * OH * OW >= 2^31, P outside 1 .. 256, more than 255 targets or one outside 0 .. P - 1, an unknown
      *    mode, a null or misaligned pointer, a row stride below the row (planes: W elements, frame: 3 OW bytes), the id plane and
-     *    colour table missing for a hard mode, the layer for mode layer, the matte plane for mode alpha -- or given with a hard mode. */
+     *    colour table missing for a hard mode, the layer for mode layer, the matte plane for mode alpha -- or given with a hard mode.
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 4, value 16, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- the per-object track report (not in the reference; ResultSaver tracks=...,
+     *    eval_vos / process_video --tracks, cutie_amd/inference/utils/track_report.py):
+     *  flags == 1024, a stage ON ITS OWN (1024 combined with any other flag stays the "unknown flags" error): per listed object the area,
+     *    the bounding box and the coordinate sums of an existing uint8 id plane p2 = [i1, i2] = [H, W], row-major and contiguous, any
+     *    alignment -- the plane the PNG is written from -- and, optionally, how sure the model was of the object (kernels in tracks.hip;
+     *    the numpy model: tests/track_ref.py).  i7, i8 and p3 .. p5 unused.
+     *    p6 = object ids int32 [i9], 4-byte aligned, i9 = n, 0 <= n <= 255.  Ids of the plane that are not listed are background for
+     *    every listed object; an entry outside 1 .. 255 is an absent object; an entry equal to an earlier one gets the earlier one's row
+     *    again (the flags == 64 convention).
+     *    Confidence source, optional: p0 = probability planes f32, 4-byte aligned, or 0.  i0 = P planes of i5 x i6 (h x w) samples, i3 =
+     *    plane stride, i4 = row stride (elements, i4 >= w; the un-padded view that `step` returns is addressed in place); p1 = lut int32
+     *    [P], 4-byte aligned, plane -> object id, exactly PROB_TO_ID's lut.  With p0 == 0, i0, i3 .. i6 and p1 are unused.
+     *    p7 = table int32 [n, 12], 16-byte aligned, WRITTEN by the launch (whatever it held before).  Per object: 0 area, 1 xmin, 2 ymin,
+     *    3 xmax, 4 ymax, (5, 6) sum of x, (7, 8) sum of y, 9 confidence sample count, (10, 11) confidence sum; a pair is a 64-bit value,
+     *    low word first.  x = column, y = row of the id plane, 0-based.  An object without a pixel (and an absent one): area 0, xmin = W,
+     *    ymin = H, xmax = ymax = -1 -- the identities of min and max -- and all sums 0.
+     *    Confidence: for every sample of the planes q* = the first plane with the largest value -- prob_to_id_kernel's loop: plane 0,
+     *    then every plane whose value is > the best so far, so a NaN never displaces anything and nothing displaces a NaN in plane 0.
+     *    If lut[q*] is a listed object, its count grows by 1 and its sum by q16(prob[q*]), q16(v) = 0 if !(v > 0), 65535 if v >= 1, else
+     *    (int)(v * 65535.f + 0.5f) (float32, multiply and add rounded on their own): a NaN counts as 0.  With p0 == 0 words 9 .. 11 are 0.
+     *    The confidence is taken at the model's resolution -- the numbers the model produced, before any resample to the output size;
+     *    box, area and sums come from the id plane at the output size -- they describe the file that is written.
+     *    Every sum is an integer sum and every min / max an integer min / max, gathered with integer atomics (registers, then LDS, then
+     *    one set of global atomics per block and object; the coordinate and confidence sums in 64 bits all the way: sum of x reaches
+     *    H W (W - 1) / 2, beyond 2^32 from 513 x 4096 on): the table depends on the planes, the lists and the lut alone, not on launch
+     *    shape or timing.  The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, n outside
+     *    0 .. 255, with p0: P outside 1 .. 256, h, w < 1, h * w >= 2^31, a row stride below w; a null or misaligned pointer.  With n == 0
+     *    nothing is written (p6, p7 may be null). */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -615,7 +644,8 @@ int cutie_op_struct_size(void);
 /* bit 0: the library was built with -DCUTIE_DIAG (make DIAG=1): measured-and-lost kernel variants (ATTN_P2Q flags&32) are present.
  * The product library returns 0 and rejects those descriptors.
  * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
- * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present. */
+ * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present.
+ * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

@@ -87,6 +87,13 @@ def has_track_stats():
     return bool(load().cutie_hip_build_flags() & 16)
 
 
+def has_region_filter():
+    """Does the loaded library know PROB_TO_ID flags == 2048, the region filter (connected components of an id plane)?  Added without a
+    new ABI number; a library from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing
+    (ResultSaver min_region= / fill_holes=)."""
+    return bool(load().cutie_hip_build_flags() & 32)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

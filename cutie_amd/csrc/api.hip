@@ -28,6 +28,8 @@ static int dispatch(const cutie_op* op, hipStream_t s) {
             return launch_affinity(op, s);
         case CUTIE_OP_RANK_SELECT: case CUTIE_OP_GATHER_ROWS: case CUTIE_OP_CONSOL_AFF: case CUTIE_OP_CONSOL_READ:
             return launch_bank(op, s);
+        case CUTIE_OP_PROB_TO_ID:                               // flags == 2048: the region filter of an existing id plane (ABI 11, form added): a stage on its own
+            return op->flags == 2048 ? launch_region_filter(op, s) : launch_elementwise(op, s);
         default:
             if (op->kind > 0 && op->kind < CUTIE_OP__COUNT) return launch_elementwise(op, s);
             cutie_set_error("cutie_exec: unknown op kind %d", op->kind);
@@ -132,8 +134,9 @@ int cutie_hip_abi_version(void) { return 11; }
 int cutie_op_struct_size(void) { return (int)sizeof(cutie_op); }
 int cutie_hip_build_flags(void) {
     // bit 1: RESIZE flags 64 / 128, the PNG decode stages; bit 2: RESIZE flags 256, the batch forms of the JPEG decode (ABI 11, forms added);
-    // bit 3: the mixed forms of the lock-step ops (clips with different object counts); bit 4: PROB_TO_ID flags == 1024, the track statistics
-    const int forms = 2 | 4 | 8 | 16;
+    // bit 3: the mixed forms of the lock-step ops (clips with different object counts); bit 4: PROB_TO_ID flags == 1024, the track statistics;
+    // bit 5: PROB_TO_ID flags == 2048, the region filter
+    const int forms = 2 | 4 | 8 | 16 | 32;
 #ifdef CUTIE_DIAG
     return forms | 1;
 #else

@@ -17,6 +17,11 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
                                             counted on the GPU from the id planes while the videos run (inference/utils/davis_metrics.py); writes
                                             global_results-<dataset>.csv, per-sequence_results-<dataset>.csv and scores.json into --output;
                                             the first and last ground-truth frame of a video are left out unless --score-all-frames)
+        [--min-region N] [--fill-holes N] [--region-connectivity 4|8]
+                                           (the region filter, on the GPU, on the id plane before anything reads it: object components
+                                            below N pixels become background, then enclosed background components below N pixels get
+                                            the id left of their first pixel (csrc/regions.hip); masks, RLE strings, overlays, --tracks
+                                            and --score see the filtered plane, the model does not; not for long-id (RGB) masks)
         [--tracks]                         (one row per object and saved frame -- area, box, centroid, confidence -- counted on the GPU from the id
                                             plane and the probabilities (inference/utils/track_report.py): OUT/tracks/<video>/tracks.json and
                                             tracks_mot.txt; with --sizes the confidence is null; not for long-id (RGB) masks)
@@ -123,9 +128,13 @@ def _take(windows, dev, lookahead):
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
            score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', tracks=False,
-           tracks_output_root=None) -> ResultSaver:
+           tracks_output_root=None, regions=None) -> ResultSaver:
     """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer.
-    tracks (--tracks): the saver gets the video's own TrackReport and writes it into tracks_output_root/<video>/ when it ends."""
+    tracks (--tracks): the saver gets the video's own TrackReport and writes it into tracks_output_root/<video>/ when it ends.
+    regions (--min-region / --fill-holes / --region-connectivity): (min_region, fill_holes, connectivity) of the saver's region filter."""
+    min_region, fill_holes, connectivity = regions if regions is not None else (0, 0, 8)
+    if max(min_region, fill_holes) >= 2 and vid_reader.use_long_id:
+        raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no region filter')
     report = None
     if tracks:
         if vid_reader.use_long_id:
@@ -141,6 +150,7 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
                        visualize_output_root=visualize_output_root, processor=core, save_scores=save_scores,
                        score_output_root=score_output_root, egress=egress, scorer=scorer, overlay=overlay,
                        tracks=report, tracks_output_root=tracks_output_root,
+                       min_region=min_region, fill_holes=fill_holes, region_connectivity=connectivity,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -157,6 +167,8 @@ def _with_json(stats, saver):
         stats['scores'] = saver.scores
     if saver.tracks is not None:                 # --tracks: the video's report (what tracks.json holds), so that sharded ranks can gather them
         stats['tracks'] = saver.tracks.as_dict()
+    if saver.regions is not None:                # --min-region / --fill-holes: what the filter changed in the video
+        stats['regions'] = saver.regions
     return stats
 
 
@@ -206,7 +218,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                   read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                  tracks=False, tracks_output_root=None) -> Dict:
+                  tracks=False, tracks_output_root=None, regions=None) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -217,7 +229,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode,
-                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root)
+                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root, regions=regions)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         feeds = _feeds([vid_reader], network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
@@ -232,7 +244,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                              read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                             tracks=False, tracks_output_root=None) -> Dict:
+                             tracks=False, tracks_output_root=None, regions=None) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -258,7 +270,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay,
-                   tracks=tracks, tracks_output_root=tracks_output_root)
+                   tracks=tracks, tracks_output_root=tracks_output_root, regions=regions)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -323,7 +335,7 @@ def lockstep_groups(mine, readers, lockstep, mixed=False):
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
                             ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                            mixed_objects=False, tracks=False, tracks_output_root=None) -> Dict[int, Dict]:
+                            mixed_objects=False, tracks=False, tracks_output_root=None, regions=None) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key`` (mixed_objects: ``lockstep_key_mixed``
     -- their object counts may differ); they may differ in length -- the
@@ -337,7 +349,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
                      score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay, tracks=tracks,
-                     tracks_output_root=tracks_output_root) for c, rd in enumerate(vid_readers)]
+                     tracks_output_root=tracks_output_root, regions=regions) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -424,6 +436,14 @@ def arg_parser() -> argparse.ArgumentParser:
                     help='per video OUT/tracks/<video>/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every '
                          'saved frame, counted on the GPU (cutie_amd/inference/utils/track_report.py).  With --sizes the confidence is null.  '
                          'Not for long-id (RGB) masks')
+    ap.add_argument('--min-region', type=int, default=0, metavar='N',
+                    help='drop object components of fewer than N pixels from every result mask (on the GPU, before the mask is written, encoded, '
+                         'overlaid, tracked or scored; csrc/regions.hip).  0 or 1: off.  Not for long-id (RGB) masks')
+    ap.add_argument('--fill-holes', type=int, default=0, metavar='N',
+                    help='fill enclosed background components of fewer than N pixels with the id left of their first pixel, after --min-region '
+                         '(so a speck of one object inside another becomes the other).  0 or 1: off.  Not for long-id (RGB) masks')
+    ap.add_argument('--region-connectivity', type=int, choices=(4, 8), default=8,
+                    help='neighbours that connect the pixels of a component for --min-region and --fill-holes: 4 (edges) or 8 (edges and corners; default)')
     return ap
 
 
@@ -461,6 +481,10 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
         ap.error('--gt and --score-all-frames belong to --score')
     if getattr(args, 'tracks', False) and args.masks is not None and _long_id_masks(args.masks):
         ap.error('--tracks: long-id datasets (RGB masks) have no uint8 id plane to count on')
+    if getattr(args, 'min_region', 0) < 0 or getattr(args, 'fill_holes', 0) < 0:
+        ap.error('--min-region and --fill-holes are not negative')
+    if max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2 and args.masks is not None and _long_id_masks(args.masks):
+        ap.error('--min-region / --fill-holes: long-id datasets (RGB masks) have no uint8 id plane to label')
     if getattr(args, 'decode_batch', 1) < 1:
         ap.error('--decode-batch is at least 1')
     if args.sizes is not None:
@@ -504,6 +528,9 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
         common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames), gt_decode=args.gt_decode)
     if getattr(args, 'tracks', False):                        # (off: no argument is passed and no launch is issued)
         common.update(tracks=True, tracks_output_root=path.join(args.output, 'tracks'))
+    filtered = max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2
+    if filtered:                                              # (off: no argument is passed and no launch is issued)
+        common.update(regions=(args.min_region, args.fill_holes, getattr(args, 'region_connectivity', 8)))
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is
@@ -549,7 +576,17 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
         elif rank == 0:
             glob = write_results(args.output, args.dataset, seqs)
             print(f'{args.dataset}: {global_line(glob)}   ({sum(v is not None for v in seqs.values())} sequences)')
+    if filtered:                                              # what the filter changed, with the run's summary (this rank's videos)
+        print(f'rank {rank}: {region_line([r.get("regions") for r in res.values()])}')
     return res
+
+
+def region_line(reports) -> str:
+    """The totals of the videos' region-filter reports (``ResultSaver.regions``) as one line."""
+    reports = [r for r in reports if r]
+    t = {k: sum(r[k] for r in reports) for k in ('frames', 'islands_removed', 'pixels_cleared', 'holes_filled', 'pixels_filled')}
+    return (f"region filter: {t['islands_removed']} islands removed ({t['pixels_cleared']} pixels), {t['holes_filled']} holes filled "
+            f"({t['pixels_filled']} pixels) on {t['frames']} frames")
 
 
 def main():

@@ -44,7 +44,19 @@ confidence.  Behind the id stage of every path -- with egress='host' before the 
 csrc/tracks.hip) reads the uint8 id plane the PNG is written from and, where the frame has them, the probabilities ``step`` returned (at
 the model's resolution, in place); the table of 48 bytes per object rides a pinned copy with an event behind it, and the writer thread
 hands it to the ``TrackReport``.  ``end`` writes ``tracks.json`` and ``tracks_mot.txt`` into ``<tracks_output_root>/<video>/``.
-``process_merged`` has S probability sources and no single model resolution: it passes none, and the confidence is null there."""
+``process_merged`` has S probability sources and no single model resolution: it passes none, and the confidence is null there.
+
+``min_region`` / ``fill_holes`` (not in the reference): the region filter (PROB_TO_ID flags == 2048, csrc/regions.hip)
+rewrites the uint8 id plane on the device as soon as it exists and before anything reads it: object components below ``min_region`` pixels
+become background, then enclosed background components below ``fill_holes`` pixels get the id left of their first pixel.  With
+egress='host' it runs on the mask right behind the argmax; with egress='device' the id stage, the filter, the PNG stage and the RLE stage
+are one op list (the PNG stage then runs on its own on the filtered plane instead of fused with the argmax); ``process_merged`` does the
+same in both branches.  The PNG, the BURST RLE strings of either codec, the overlays, the id input of the vis modes, the track report and
+the scorer therefore all see the plane of the file that is written.  What comes from the probabilities does NOT change: the soft masks, the
+alpha matte, the soft vis modes and ``save_scores`` -- and the model never sees the filtered plane: the probabilities ``step`` returns, the
+memory bank and ``last_mask`` are untouched.  The four counts of a frame ride a 16-byte pinned copy with an event behind it; the writer
+thread sums them, and ``end`` leaves the video's totals in ``self.regions``.  With both thresholds below 2 nothing is launched and no
+byte changes."""
 import logging
 import os
 import shutil
@@ -159,6 +171,17 @@ class _TrackBuffers:
         self.event = torch.cuda.Event() if on_gpu else _NoEvent()
 
 
+class _RegionBuffers:
+    """What one frame in flight owns of the region filter: its four counts on the device, their pinned twin and the event recorded behind
+    the copy."""
+
+    def __init__(self, device):
+        on_gpu = torch.device(device).type == 'cuda'
+        self.dev = torch.empty(4, dtype=torch.int32, device=device)
+        self.host = torch.empty(4, dtype=torch.int32).pin_memory() if on_gpu else torch.empty(4, dtype=torch.int32)
+        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
+
+
 class _NoEvent:
     def record(self):
         pass
@@ -187,13 +210,14 @@ class _Job:
     matte_keep: Tuple = ()                   # ... what the launches read (planes, frame, tables), kept until the writer is done with the frame
     tracks: Optional[_TrackBuffers] = None   # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
     track_meta: Optional[Tuple] = None       # ... (frame index, object ids of the rows, H, W): the frame is reported
+    regions: Optional[_RegionBuffers] = None  # min_region / fill_holes: the frame's four counts arrive in these
 
 
 class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
-                 target_objects=None, layer=None, tracks=None, tracks_output_root=None):
+                 target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -217,7 +241,25 @@ class ResultSaver:
         to the output size with PIL and uploaded once.
         ``tracks`` (not in the reference; a utils/track_report.py TrackReport, see the module docstring): every frame's area, box,
         coordinate sums and confidence per object are counted on the device and reported to it; ``end`` writes its two files into
-        ``tracks_output_root``/<video>/ (default: <output_root>/tracks).  Needs ``processor``; long ids (RGB masks) have no uint8 plane."""
+        ``tracks_output_root``/<video>/ (default: <output_root>/tracks).  Needs ``processor``; long ids (RGB masks) have no uint8 plane.
+        ``min_region``, ``fill_holes``, ``region_connectivity`` (not in the reference; see the module docstring): object components of
+        fewer than ``min_region`` pixels are dropped from the id plane and enclosed background components of fewer than ``fill_holes``
+        pixels are filled, on the device, before anything reads the plane; components are connected under ``region_connectivity`` (4 |
+        8).  A threshold below 2 switches its stage off; with both off nothing changes anywhere.  ``end`` leaves the video's totals in
+        ``self.regions`` (None when off).  Needs ``processor``; long ids (RGB masks) have no uint8 plane."""
+        self.min_region, self.fill_holes, self.region_connectivity = int(min_region), int(fill_holes), int(region_connectivity)
+        if self.min_region < 0 or self.fill_holes < 0:
+            raise ValueError(f'min_region and fill_holes are not negative ({min_region}, {fill_holes})')
+        self._regions_on = self.min_region >= 2 or self.fill_holes >= 2
+        if self._regions_on and self.region_connectivity not in (4, 8):
+            raise ValueError(f'region_connectivity is 4 or 8, not {region_connectivity}')
+        if self._regions_on and use_long_id:
+            raise ValueError('min_region / fill_holes: components are labelled on uint8 id planes; a use_long_id saver (RGB masks) cannot filter them')
+        if self._regions_on and processor is None:
+            raise ValueError('min_region / fill_holes need the processor (its device)')
+        self.regions = None
+        self._region_free: Queue = Queue()
+        self._region_allocated, self._region_scratch, self._region_totals, self._region_frames = 0, None, np.zeros(4, dtype=np.int64), 0
         if tracks is not None and use_long_id:
             raise ValueError('tracks: the statistics are counted on uint8 id planes; a use_long_id saver (RGB masks) cannot report them')
         if tracks is not None and processor is None:
@@ -307,11 +349,16 @@ class ResultSaver:
                 if tmp_id < lut.shape[0]:
                     lut[tmp_id] = obj.id
             mask = lut[idx].to(out_dtype)
+        rg = {}
+        if self._regions_on:                     # before anything reads the plane: the scorer, the overlay, the vis modes, the tracks, the copy
+            mask = mask.contiguous()
+            rg = self._filter_plane(mask)
         if self.scorer is not None:
             self.scorer.add(frame_name, mask)
         q = (prob * 255).to(torch.uint8).cpu() if self.save_scores else None       # == numpy astype(uint8) of prob*255
         all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
         ov = self._queue_overlay(None, mask, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        ov.update(rg)
         if self._matte_on:
             ov.update(self._queue_matte(prob, tuple(prob.shape[1:]), mask, all_ids, path_to_image, image_u8))
         if self.tracks is not None:
@@ -319,6 +366,42 @@ class ResultSaver:
         self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, all_ids,
                             prob=q, last_frame=last_frame,
                             tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, **ov))
+
+    # ---- min_region / fill_holes -------------------------------------------------------------------------------------------------
+    def _add_regions(self, ol, ids) -> _RegionBuffers:
+        """Append the region filter of ``ids`` (uint8 [H, W] on the device, contiguous; rewritten in place) to the op list ``ol``.
+        -> the frame's count buffers: ``_copy_regions`` them once the list has been run."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        if self._region_scratch is None or self._region_scratch[0] != (H, W):
+            self._region_scratch = ((H, W), torch.empty(O.OpList.region_scratch_words(H, W), dtype=torch.int32, device=dev))
+        try:
+            b = self._region_free.get_nowait()
+        except Empty:
+            if self._region_allocated < self.queue.maxsize + 2:
+                self._region_allocated += 1
+                b = _RegionBuffers(dev)
+            else:
+                b = self._region_free.get()      # the next set the writer gives back
+        ol.region_filter(ids, self._region_scratch[1], b.dev, min_region=self.min_region, fill_holes=self.fill_holes,
+                         connectivity=self.region_connectivity)
+        return b
+
+    @staticmethod
+    def _copy_regions(b: _RegionBuffers) -> dict:
+        """The pinned copy of the frame's counts (16 bytes) and the event behind it.  -> the _Job field.  Nothing waits here."""
+        b.host.copy_(b.dev, non_blocking=True)
+        b.event.record()
+        return dict(regions=b)
+
+    def _filter_plane(self, ids) -> dict:
+        """The region filter of a finished plane as an op list of its own, on the current stream.  -> the _Job field"""
+        from ... import ops as O
+        ol = O.OpList()
+        b = self._add_regions(ol, ids)
+        ol.run()
+        return self._copy_regions(b)
 
     # ---- tracks -----------------------------------------------------------------------------------------------------------------
     def _lut_device(self, P, dev):
@@ -603,8 +686,15 @@ class ResultSaver:
             self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
         b = self._take(H, W, dev)
         ol = O.OpList()
-        ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
-                      out_hw=(H, W) if resize_needed else None, png=(b.stream, b.status, self._scratch[1]))
+        rb = None
+        if self._regions_on:                     # ids, then the filter, then the PNG stage on its own on the filtered plane
+            ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
+                          out_hw=(H, W) if resize_needed else None, png=None)
+            rb = self._add_regions(ol, b.ids)
+            ol.png_deflate(b.ids, b.stream, b.status, self._scratch[1], H=H, W=W)
+        else:
+            ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
+                          out_hw=(H, W) if resize_needed else None, png=(b.stream, b.status, self._scratch[1]))
         all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
         rle = self.json_style == 'burst' and frame_name in self.annotated_frames
         if rle:                                  # the objects' RLE strings of the finished plane, in the order of all_ids
@@ -619,6 +709,8 @@ class ResultSaver:
         if self.scorer is not None:              # (b.ids is not handed out again before the writer is done with the frame: same stream)
             self.scorer.add(frame_name, b.ids)
         ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        if rb is not None:
+            ov.update(self._copy_regions(rb))
         if self._matte_on:
             ov.update(self._queue_matte(prob, (H, W), b.ids, all_ids, path_to_image, image_u8))
         if self.tracks is not None:
@@ -684,10 +776,13 @@ class ResultSaver:
         if not device_egress:
             ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=dev)
             ol.prob_to_id_merged(probs, lut_dev, ids, out_hw=(H, W))
+            rb = self._add_regions(ol, ids) if self._regions_on else None
             ol.run()
             if self.scorer is not None:
                 self.scorer.add(frame_name, ids)
             ov = self._queue_overlay(None, ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+            if rb is not None:
+                ov.update(self._copy_regions(rb))
             if self.tracks is not None:
                 ov.update(self._queue_tracks(ids, all_ids, None, None, frame_index))
             self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame, **ov))
@@ -695,12 +790,20 @@ class ResultSaver:
         if self._scratch is None or self._scratch[0] != (H, W):
             self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
         b = self._take(H, W, dev)
-        ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W), png=(b.stream, b.status, self._scratch[1]))
+        rb = None
+        if self._regions_on:                     # as in _process_device: the PNG stage on its own, on the filtered plane
+            ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W))
+            rb = self._add_regions(ol, b.ids)
+            ol.png_deflate(b.ids, b.stream, b.status, self._scratch[1], H=H, W=W)
+        else:
+            ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W), png=(b.stream, b.status, self._scratch[1]))
         ol.run()
         if self.scorer is not None:
             self.scorer.add(frame_name, b.ids)
         ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
         has_overlay = bool(ov)
+        if rb is not None:
+            ov.update(self._copy_regions(rb))
         if self.tracks is not None:
             ov.update(self._queue_tracks(b.ids, all_ids, None, None, frame_index))
         b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
@@ -747,6 +850,11 @@ class ResultSaver:
         self._free, self._allocated, self._scratch = Queue(), 0, None
         self._matte_free, self._matte_allocated, self._matte_png_scratch = Queue(), 0, None
         self._track_free, self._track_allocated = Queue(), 0
+        self._region_free, self._region_allocated, self._region_scratch = Queue(), 0, None
+        if self._regions_on:
+            t = [int(v) for v in self._region_totals]
+            self.regions = dict(min_region=self.min_region, fill_holes=self.fill_holes, connectivity=self.region_connectivity,
+                                frames=self._region_frames, islands_removed=t[0], pixels_cleared=t[1], holes_filled=t[2], pixels_filled=t[3])
         if self.scorer is not None:
             self.scores = self.scorer.finish()
         if self.tracks is not None:
@@ -827,6 +935,10 @@ def _writer(queue: Queue):
                 else:
                     table = np.zeros((0, 12), dtype=np.int32)
                 s.tracks.add(job.frame_name, index, table, objs, H, W)
+            if job.regions is not None:                            # min_region / fill_holes: the frame's counts have landed behind their event
+                job.regions.event.synchronize()
+                s._region_totals += job.regions.host.numpy()
+                s._region_frames += 1
             segment =s._fetch_jpeg(job.overlay) if job.overlay is not None else None
             if segment is not None:                                # overlay='device': wrap the finished segment, no PIL
                 vis_dir = path.join(s.visualize_output_root, s.video_name)
@@ -861,6 +973,8 @@ def _writer(queue: Queue):
                 job.saver._matte_free.put(job.matte)
             if job.tracks is not None:
                 job.saver._track_free.put(job.tracks)
+            if job.regions is not None:
+                job.saver._region_free.put(job.regions)
         queue.task_done()
 
 

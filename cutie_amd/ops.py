@@ -1086,6 +1086,46 @@ class OpList:
             self.keep.append(objs)
         return self.add(PROB_TO_ID, 1024, ints, [], [prob, lut, ids_plane, None, None, None, objs if n else None, table if n else None])
 
+    REGION_TILE_H = 16        # the tile of the local labelling (csrc/regions.hip RGN_TH, RGN_TW): components are merged across its seams
+    REGION_TILE_W = 64
+
+    @staticmethod
+    def region_scratch_words(H, W):
+        """int32 words of the region filter's scratch: a label and a size word per pixel."""
+        return 2 * H * W
+
+    def region_filter(self, ids_plane, scratch, counts, *, min_region=0, fill_holes=0, connectivity=8):
+        """PROB_TO_ID flags == 2048 (ABI 11, form added; include/cutie_hip.h): ids_plane uint8 [H, W] (contiguous, any alignment) is
+        rewritten IN PLACE: object components (equal non-zero id, connected under ``connectivity`` 4 | 8) of fewer than ``min_region``
+        pixels become 0, then enclosed background components of fewer than ``fill_holes`` pixels get the id left of their first pixel.
+        Thresholds 0 and 1 switch a stage off.  ``scratch``: int32, at least ``region_scratch_words(H, W)`` words; ``counts``: int32
+        [4], WRITTEN by the launch: islands removed | pixels cleared | holes filled | pixels filled."""
+        # the form came without a new ABI number (an injected interpreter of the tests has no library; a missing library fails when the list runs)
+        if not getattr(_lib._executor, 'is_mock', False):
+            try:
+                known = _lib.has_region_filter()
+            except _lib.HipLibraryError:
+                known = True
+            if not known:
+                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no region filter, PROB_TO_ID flags == 2048); rebuild it.')
+        if ids_plane.dtype != torch.uint8 or ids_plane.dim() != 2 or not ids_plane.is_contiguous():
+            raise ValueError(f'region_filter: ids_plane is a contiguous uint8 [H, W], not {ids_plane.dtype} {tuple(ids_plane.shape)}')
+        H, W = int(ids_plane.shape[0]), int(ids_plane.shape[1])
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f'region_filter: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        min_region, fill_holes, connectivity = int(min_region), int(fill_holes), int(connectivity)
+        if min_region < 0 or fill_holes < 0 or max(min_region, fill_holes) >= 1 << 31:
+            raise ValueError(f'region_filter: min_region {min_region} and fill_holes {fill_holes} are 32-bit and not negative')
+        if connectivity not in (4, 8):
+            raise ValueError(f'region_filter: connectivity {connectivity}, 4 or 8')
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < self.region_scratch_words(H, W):
+            raise ValueError(f'region_filter: scratch is a contiguous int32 of at least {self.region_scratch_words(H, W)} words')
+        if counts.dtype != torch.int32 or counts.numel() != 4 or not counts.is_contiguous():
+            raise ValueError('region_filter: counts is a contiguous int32 [4]')
+        words = int(scratch.numel())
+        return self.add(PROB_TO_ID, 2048, [0, H, W, min_region, fill_holes, connectivity, 0, 0, words & 0x7fffffff, words >> 31], [],
+                        [None, None, ids_plane, None, None, scratch, None, counts])
+
     JPEG_ENC_BLOCK_WORDS = 52     # JPG_BLOCK_WORDS (csrc/jpeg_enc.hip): a coded block is at most 22 + 63 * 26 = 1660 bits
 
     @staticmethod

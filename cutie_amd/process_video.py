@@ -152,13 +152,17 @@ def check_to_clear_non_permanent_memory(processor: InferenceCore, mem_cleanup_ra
 def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, num_objects: int = -1,
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
-                  layer=None, decode_batch: int = 1, tracks: bool = False) -> Dict:
+                  layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
+                  region_connectivity: int = 8) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
     joins the result.  vis_modes / soft_masks / alpha_matte / target_objects / layer: ResultSaver's (the module docstring); 'folders' of
     the result names the folders they wrote.  tracks: area, box, centroid and confidence of every object on every frame, counted on the
-    device (inference/utils/track_report.py): output_dir/tracks/tracks.json and tracks_mot.txt, and 'tracks' (the json's content) in the result."""
+    device (inference/utils/track_report.py): output_dir/tracks/tracks.json and tracks_mot.txt, and 'tracks' (the json's content) in the result.
+    min_region / fill_holes / region_connectivity: ResultSaver's region filter -- small object components are dropped from every mask and
+    small enclosed holes filled, on the device, before the mask is written, composed, tracked or scored; 'regions' (the totals) joins the
+    result.  The model never sees the filtered plane."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -243,7 +247,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         saver = ResultSaver(output_dir, '', dataset='', object_manager=processor.object_manager, use_long_id=use_long_id,
                             palette=palette, processor=processor, egress=egress, scorer=scorer, vis_modes=vis_modes, soft_masks=soft_masks,
                             alpha_matte=alpha_matte, target_objects=target_objects, layer=layer,
-                            tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None)
+                            tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None,
+                            min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity)
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -268,6 +273,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         out['scores'] = saver.scores
     if tracks:
         out['tracks'] = saver.tracks.as_dict()
+    if saver.regions is not None:
+        out['regions'] = saver.regions
     if vis_modes or soft_masks or alpha_matte:
         out['folders'] = ([path.join(output_dir, 'visualization', m) for m in vis_modes] + ([path.join(output_dir, 'soft_masks')] if soft_masks else []) +
                           ([path.join(output_dir, 'alpha')] if alpha_matte else []))
@@ -300,6 +307,11 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
     ap.add_argument('--tracks', action='store_true',
                     help='OUT/tracks/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every frame, counted on the GPU')
+    ap.add_argument('--min-region', type=int, default=0, metavar='N',
+                    help='drop object components of fewer than N pixels from every mask, on the GPU, before it is written, composed, tracked or scored (0, 1: off)')
+    ap.add_argument('--fill-holes', type=int, default=0, metavar='N',
+                    help='then fill enclosed background components of fewer than N pixels with the id left of their first pixel (0, 1: off)')
+    ap.add_argument('--region-connectivity', type=int, choices=(4, 8), default=8, help='neighbours that connect a component: 4 or 8 (default)')
     return ap
 
 
@@ -323,10 +335,14 @@ def main():
     r = process_video(net, cfg, args.video, args.mask_dir, args.output_dir, num_objects=args.num_objects,
                       mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
-                      decode_batch=args.decode_batch, tracks=args.tracks)
+                      decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
+                      region_connectivity=args.region_connectivity)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))
+    if r.get('regions') is not None:
+        from .eval_vos import region_line
+        print(region_line([r['regions']]))
     print(f'Total processing time: {r["seconds"]}\nTotal processed frames: {r["frames"]}\n'
           f'FPS: {r["frames"] / max(r["seconds"], 1e-9)}\nMax allocated memory (MB): {torch.cuda.max_memory_allocated() / 2 ** 20}')
 

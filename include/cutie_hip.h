@@ -507,7 +507,37 @@ enum {
      *    H W (W - 1) / 2, beyond 2^32 from 513 x 4096 on): the table depends on the planes, the lists and the lut alone, not on launch
      *    shape or timing.  The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, n outside
      *    0 .. 255, with p0: P outside 1 .. 256, h, w < 1, h * w >= 2^31, a row stride below w; a null or misaligned pointer.  With n == 0
-     *    nothing is written (p6, p7 may be null). */
+     *    nothing is written (p6, p7 may be null).
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 5, value 32, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- the region filter (not in the reference; ResultSaver min_region= / fill_holes=,
+     *    eval_vos / process_video --min-region / --fill-holes):
+     *  flags == 2048, a stage ON ITS OWN (2048 combined with any other flag stays the "unknown flags" error): connected components of an
+     *    existing uint8 id plane p2 = [i1, i2] = [H, W], row-major and contiguous, any alignment, REWRITTEN IN PLACE: small object
+     *    components are dropped and small enclosed background components are filled (kernels in regions.hip; the numpy model:
+     *    tests/region_ref.py).  i0, i6, i7, p0, p1, p3, p4, p6 and the floats are unused.
+     *    i3 = min_region >= 0, i4 = fill_holes >= 0, i5 = connectivity, 4 (edge neighbours) or 8 (edge and corner neighbours); both
+     *    stages use the same one.
+     *    p5 = scratch int32, 4-byte aligned, of i8 + 2^31 * i9 words (i8, i9 >= 0): at least 2 * H * W (OpList.region_scratch_words).
+     *    Its content before and after the launch means nothing.
+     *    p7 = counts int32 [4], 4-byte aligned, WRITTEN by the launch (whatever it held before): 0 islands removed | 1 pixels cleared |
+     *    2 holes filled | 3 pixels filled.
+     *    Stage A, islands (runs when min_region >= 2): a component is a maximal set of pixels of one non-zero id, connected under i5.
+     *    Every id 1 .. 255 is an object, whether or not anyone lists it.  A component of fewer than min_region pixels becomes 0.  All
+     *    decisions are taken on the plane as it entered the stage.
+     *    Stage B, holes (runs when fill_holes >= 2, on A's result): a component is a maximal set of pixels of id 0, connected under
+     *    i5.  A component with a pixel in row 0, row H - 1, column 0 or column W - 1 is never a hole.  Every other component of fewer
+     *    than fill_holes pixels is filled with the id of the pixel left of its first pixel in raster order, (y0, x0 - 1) -- which
+     *    exists (x0 > 0: the component does not touch column 0) and is not 0 (it would belong to the component and precede (y0, x0)).
+     *    Thresholds 0 and 1 switch a stage off (no component has fewer than 1 pixel).  With both below 2 the launch zeroes counts and
+     *    does nothing else.
+     *    Islands run BEFORE holes, so that a speck of object B inside object A ends up as A: A's stage clears it to a hole, B's stage
+     *    fills the hole with A.  (Segment Anything's remove_small_regions, for binary masks, is called holes first, then islands; for
+     *    an id plane that order would leave the speck as background inside A, or keep it.)
+     *    Determinism: components are linked by atomicMin on linear pixel indices, so a component's root is its smallest linear index
+     *    whatever the arrival order -- which also makes the fill pixel root - 1; areas and counts are integer sums.  The plane and
+     *    counts after the launch depend on the plane before it and on i3 .. i5 alone.
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, a negative threshold, a
+     *    connectivity other than 4 or 8, a null p2, p5 or p7, p5 or p7 not 4-byte aligned, fewer scratch words than 2 * H * W. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -645,7 +675,8 @@ int cutie_op_struct_size(void);
  * The product library returns 0 and rejects those descriptors.
  * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
  * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present.
- * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present. */
+ * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
+ * filter, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

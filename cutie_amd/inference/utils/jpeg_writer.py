@@ -113,7 +113,7 @@ def wrap(stream: bytes, H: int, W: int, qtables: np.ndarray) -> bytes:
 
 def color_table(colors: np.ndarray, all_obj_ids) -> np.ndarray:
     """uint8 [256, 4]: entry id = colors[id % len(colors)] for the ids of ``all_obj_ids`` (1 .. 255), zero elsewhere -- the rgb mask
-    of the host overlay (results_utils.py ``_writer``), where a pixel whose id is not an object stays black and is still halved."""
+    of the host overlay (results_utils.py ``_write_overlay``), where a pixel whose id is not an object stays black and is still halved."""
     tab = np.zeros((256, 4), dtype=np.uint8)
     colors = np.asarray(colors, dtype=np.uint8).reshape(-1, 3)
     for oid in all_obj_ids:

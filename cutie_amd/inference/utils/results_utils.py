@@ -62,7 +62,7 @@ import os
 import shutil
 from dataclasses import dataclass
 from os import path
-from queue import Empty, Queue
+from queue import Queue
 from threading import Thread
 from typing import Optional, Tuple
 
@@ -75,6 +75,7 @@ from ...utils.pano_utils import ID2RGBConverter
 from . import coco_rle
 from . import jpeg_writer
 from . import png as png_container
+from .saver_buffers import RLE_TABLE, EgressBuffers, KeyedCache, MatteBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
 
 log = logging.getLogger()
 
@@ -99,118 +100,43 @@ davis_palette = davis_palette_np.tobytes()
 
 EGRESS_MODES = ('host', 'device')
 EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
-RLE_TABLE = 16 + 255 * 16   # BURST: bytes of the status block and the table of up to 255 objects in front of the RLE strings
 OVERLAY_MODES = ('host', 'device')
 JPEG_SLAB = 256 * 1024      # overlay='device': bytes of the first device-to-host copy of a frame's JPEG: status + the head of the stream (a 480p overlay is 30-120 KB)
+RLE_SLAB = 256 * 1024       # BURST: bytes of the whole device-to-host copy: status, table (RLE_TABLE) and the strings (a frame that needs more is encoded on the host)
 VIS_MODES = ('davis', 'light', 'fade', 'popup', 'layer')     # gui/interactive_utils.py get_visualization_torch ('mask', 'image': trivial; 'rgba': alpha_matte)
-RLE_SLAB = 256 * 1024       # ... and of the whole device-to-host copy: status, table and the strings (a frame that needs more is encoded on the host)
-
-
-class _EgressBuffers:
-    """What one frame in flight owns (egress='device'): the id plane, [status | stream] on the device, the pinned slab and the event
-    recorded behind the copy.  Recycled through ResultSaver's pool once the writer thread is done with them."""
-
-    def __init__(self, H, W, device, rle=False, png=True, jpeg=False):
-        from ... import ops as O
-        self.H, self.W, self.kinds = H, W, (rle, png, jpeg)
-        on_gpu = torch.device(device).type == 'cuda'
-        staging = (lambda n: torch.empty(n, dtype=torch.uint8).pin_memory()) if on_gpu else (lambda n: torch.empty(n, dtype=torch.uint8))
-        if rle:                                  # BURST: [status | table | strings] on the device and pinned
-            self.rle_dev = torch.empty(RLE_SLAB, dtype=torch.uint8, device=device)
-            self.rle_status, self.rle_table = self.rle_dev[:16].view(torch.int32), self.rle_dev[16:RLE_TABLE].view(torch.int32).view(-1, 4)
-            self.rle_stream = self.rle_dev[RLE_TABLE:]
-            self.rle_host = staging(RLE_SLAB)
-        if png:
-            cap = O.OpList.png_capacity(H, W)
-            self.ids = torch.empty((H, W), dtype=torch.uint8, device=device)
-            self.dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
-            self.status, self.stream = self.dev[:16].view(torch.int32), self.dev[16:]
-            self.host = staging(min(16 + cap, EGRESS_SLAB))
-        if jpeg:                                 # overlay='device': [status | entropy-coded segment]
-            cap = O.OpList.jpeg_enc_capacity(H, W)
-            self.jpeg_dev = torch.empty(16 + cap, dtype=torch.uint8, device=device)
-            self.jpeg_status, self.jpeg_stream = self.jpeg_dev[:16].view(torch.int32), self.jpeg_dev[16:]
-            self.jpeg_host = staging(min(16 + cap, JPEG_SLAB))
-        self.event = torch.cuda.Event() if on_gpu else _NoEvent()      # (a CPU device: the interpreter of the tests, everything is synchronous)
-
-
-class _MatteBuffers:
-    """What one frame in flight owns of the vis_modes / soft_masks / alpha_matte outputs: per mode the composed frame and its
-    [status | JPEG segment], the quantised planes (K soft masks, then the matte) and per plane its [status | zlib stream]; one pinned
-    slab per stream and one event behind all copies."""
-
-    def __init__(self, H, W, K, modes, alpha, device):
-        from ... import ops as O
-        self.H, self.W, self.K, self.modes, self.alpha = H, W, K, tuple(modes), alpha
-        on_gpu = torch.device(device).type == 'cuda'
-        staging = (lambda n: torch.empty(n, dtype=torch.uint8).pin_memory()) if on_gpu else (lambda n: torch.empty(n, dtype=torch.uint8))
-        cap = O.OpList.jpeg_enc_capacity(H, W)
-        # (one tensor per mode: the composite's dword stores need a 16-byte aligned frame, and H * W * 3 is rarely a multiple of 16)
-        self.frames = [torch.empty((H, W, 3), dtype=torch.uint8, device=device) for _ in self.modes]
-        self.jpeg_dev = [torch.empty(16 + cap, dtype=torch.uint8, device=device) for _ in self.modes]
-        self.jpeg_host = [staging(min(16 + cap, JPEG_SLAB)) for _ in self.modes]
-        n = K + (1 if alpha else 0)
-        cap = O.OpList.png_capacity(H, W)
-        self.planes = torch.empty((K, H, W), dtype=torch.uint8, device=device)               # the soft masks
-        self.matte = torch.empty((H, W), dtype=torch.uint8, device=device) if alpha else None # (a tensor of its own: 16-byte aligned)
-        self.png_dev = [torch.empty(16 + cap, dtype=torch.uint8, device=device) for _ in range(n)]
-        self.png_host = [staging(min(16 + cap, EGRESS_SLAB)) for _ in range(n)]
-        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
-
-
-class _TrackBuffers:
-    """What one frame in flight owns of the track report: the table of up to 255 objects on the device, its pinned twin and the event
-    recorded behind the copy."""
-
-    def __init__(self, device):
-        from ... import ops as O
-        words = O.OpList.TRACK_MAX_OBJECTS * O.OpList.TRACK_WORDS
-        on_gpu = torch.device(device).type == 'cuda'
-        self.dev = torch.empty(words, dtype=torch.int32, device=device)
-        self.host = torch.empty(words, dtype=torch.int32).pin_memory() if on_gpu else torch.empty(words, dtype=torch.int32)
-        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
-
-
-class _RegionBuffers:
-    """What one frame in flight owns of the region filter: its four counts on the device, their pinned twin and the event recorded behind
-    the copy."""
-
-    def __init__(self, device):
-        on_gpu = torch.device(device).type == 'cuda'
-        self.dev = torch.empty(4, dtype=torch.int32, device=device)
-        self.host = torch.empty(4, dtype=torch.int32).pin_memory() if on_gpu else torch.empty(4, dtype=torch.int32)
-        self.event = torch.cuda.Event() if on_gpu else _NoEvent()
-
-
-class _NoEvent:
-    def record(self):
-        pass
-
-    def synchronize(self):
-        pass
 
 
 @dataclass
 class _Job:
+    """One frame for the writer thread.  The buffer sets come from pools and go back to them (``held``); the tensors are kept alive until
+    the writer is done with the frame, so that what a launch reads outlives the launch on the stream that owns it, whoever made it."""
     saver: 'ResultSaver'
-    mask: torch.Tensor            # CPU uint8 / int32 [H,W], object ids
+    mask: Optional[torch.Tensor]  # CPU uint8 / int32 [H,W], object ids (None with egress='device': the mask arrives in `egress`)
     frame_name: str
     path_to_image: Optional[str]
     all_obj_ids: list
     prob: Optional[torch.Tensor] = None      # CPU uint8 [K+1,H,W] (save_scores)
     last_frame: bool = False
     tmp_to_obj: Optional[dict] = None        # {tmp_id: object id} at the time of the frame
-    egress: Optional[_EgressBuffers] = None  # egress='device': the mask arrives in these (mask is None)
+    egress: Optional[EgressBuffers] = None   # egress='device': the mask's zlib stream arrives in these
     rle: bool = False                        # egress='device', BURST: the objects' RLE strings arrive in them as well
-    overlay: Optional[_EgressBuffers] = None  # overlay='device': the JPEG's entropy-coded segment arrives in these (the same set as `egress` when both are on)
-    frame: Optional[torch.Tensor] = None     # overlay='device': the uint8 frame the stage read (kept until the writer is done: see _queue_overlay)
+    overlay: Optional[EgressBuffers] = None  # overlay='device': the JPEG's entropy-coded segment arrives in these (the same set as `egress` when both are on)
+    frame: Optional[torch.Tensor] = None     # overlay='device': the uint8 frame the stage read
     ids: Optional[torch.Tensor] = None       # overlay='device': the id plane on the device (a frame whose stream overflowed is blended on the host)
-    matte: Optional[_MatteBuffers] = None    # vis_modes / soft_masks / alpha_matte: the frame's composed outputs arrive in these
+    matte: Optional[MatteBuffers] = None     # vis_modes / soft_masks / alpha_matte: the frame's composed outputs arrive in these
     matte_objects: Tuple = ()                # ... the object id of every soft-mask plane, in plane order
-    matte_keep: Tuple = ()                   # ... what the launches read (planes, frame, tables), kept until the writer is done with the frame
-    tracks: Optional[_TrackBuffers] = None   # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
+    matte_keep: Tuple = ()                   # ... what the launches read (planes, frame, tables)
+    tracks: Optional[TrackBuffers] = None    # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
     track_meta: Optional[Tuple] = None       # ... (frame index, object ids of the rows, H, W): the frame is reported
-    regions: Optional[_RegionBuffers] = None  # min_region / fill_holes: the frame's four counts arrive in these
+    regions: Optional[RegionBuffers] = None  # min_region / fill_holes: the frame's four counts arrive in these
+
+    def held(self) -> list:
+        """the pooled buffer sets of the frame, each once"""
+        sets = []
+        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions):
+            if b is not None and not any(b is s for s in sets):
+                sets.append(b)
+        return sets
 
 
 class ResultSaver:
@@ -258,16 +184,14 @@ class ResultSaver:
         if self._regions_on and processor is None:
             raise ValueError('min_region / fill_holes need the processor (its device)')
         self.regions = None
-        self._region_free: Queue = Queue()
-        self._region_allocated, self._region_scratch, self._region_totals, self._region_frames = 0, None, np.zeros(4, dtype=np.int64), 0
+        self._region_totals, self._region_frames = np.zeros(4, dtype=np.int64), 0
         if tracks is not None and use_long_id:
             raise ValueError('tracks: the statistics are counted on uint8 id planes; a use_long_id saver (RGB masks) cannot report them')
         if tracks is not None and processor is None:
             raise ValueError('tracks needs the processor (its device and object table)')
         self.tracks = tracks
         self.tracks_output_root = tracks_output_root if tracks_output_root is not None else path.join(output_root, 'tracks')
-        self._track_free: Queue = Queue()
-        self._track_allocated, self._track_objs, self._track_count = 0, {}, 0
+        self._track_count = 0
         if tracks is not None and not tracks.video_name:
             tracks.video_name = video_name
         vis_modes = tuple(vis_modes)
@@ -284,9 +208,7 @@ class ResultSaver:
         if 'layer' in vis_modes and layer is None:
             raise ValueError("vis mode 'layer' needs layer (an RGBA image)")
         self.target_objects = None if target_objects is None else [int(v) for v in target_objects]
-        self._layer_src, self._layer_dev = layer, None
-        self._matte_free: Queue = Queue()
-        self._matte_allocated, self._matte_png_scratch, self._matte_colors = 0, None, {}
+        self._layer_src = layer
         if scorer is not None and use_long_id:
             raise ValueError('scorer: J&F is counted on uint8 id planes; long ids (RGB masks) cannot be scored')
         self.scorer, self.scores = scorer, None
@@ -312,30 +234,71 @@ class ResultSaver:
             self.video_json = {k: v for k, v in init_json.items() if k != 'segmentations'}
             self.video_json['segmentations'] = self.segmentations
             self.json_style = 'burst'
-        self._rle_objs, self._rle_scratch, self._rle_warned = {}, None, False
+        self._rle_warned = self._jpeg_warned = False
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
         self.overlay = 'device' if (overlay == 'device' and visualize and not use_long_id) else 'host'
         self.egress = 'device' if (egress == 'device' and not use_long_id and (not visualize or self.overlay == 'device') and save_mask) else 'host'
-        self._jpeg_scratch, self._jpeg_tables, self._jpeg_colors, self._jpeg_warned = None, None, {}, False
-        self._free: Queue = Queue()              # recycled _EgressBuffers
-        self._allocated, self._luts, self._scratch, self._wstream = 0, {}, None, None
+        self._jpeg_tables = None                 # (quantisation tables on the host, on the device)
+        self._copies = WriterCopies()
+        self._scratch = KeyedCache(latest=True)  # per stage the scratch tensor of the current geometry
+        self._tables = KeyedCache(latest=False)  # per stage the small device tables of an object set (they change when objects come or go, not per frame)
         if self.visualize:
             self.colors = np.array(self.palette, dtype=np.uint8).reshape(-1, 3) if self.palette is not None else davis_palette_np
         self.need_remapping = True
         self.id2rgb_converter = ID2RGBConverter()
         self.queue: Queue = Queue(maxsize=10)
+        # buffer sets in flight: what the queue can hold + the one in the writer's hands + the one being filled
+        limit, dev = self.queue.maxsize + 2, lambda: self.processor.network.device
+        self._pools = dict(
+            egress=Pool(limit, lambda H, W, png: EgressBuffers(H, W, dev(), self._slab, rle=self.json_style == 'burst' and png, png=png,
+                                                               jpeg=self.overlay == 'device')),
+            matte=Pool(limit, lambda H, W, K: MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev(), self._slab)),
+            tracks=Pool(limit, lambda: TrackBuffers(dev())),
+            regions=Pool(limit, lambda: RegionBuffers(dev())))
         self.thread = Thread(target=_writer, args=(self.queue,), daemon=True)
         self.thread.start()
 
+    def _slab(self, kind, H, W) -> Slab:
+        """A [status | stream] slab of this saver for a plane of H x W: 'png' (an error word raises in the writer thread), 'jpeg' and
+        'rle' (a frame that did not fit its stream is warned about once per saver, and the writer thread takes its other route)."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        if kind == 'png':
+            return Slab(O.OpList.png_capacity(H, W), EGRESS_SLAB, dev, self._copies)
+        flag = f'_{kind}_warned'
+
+        def overflow(length, capacity):
+            if not getattr(self, flag):
+                setattr(self, flag, True)
+                log.warning(f'device {kind.upper()} encoder: a frame of {self.video_name} needs {length} bytes, the stream holds {capacity}; '
+                            f'such frames are encoded on the host')
+        if kind == 'jpeg':
+            return Slab(O.OpList.jpeg_enc_capacity(H, W), JPEG_SLAB, dev, self._copies, what='JPEG', overflow=overflow)
+        return Slab(RLE_SLAB - RLE_TABLE, RLE_SLAB, dev, self._copies, what='RLE', error_word=1, fixed=RLE_TABLE - 16, overflow=overflow)
+
+    # ---- the three id sources ---------------------------------------------------------------------------------------------------
     def process(self, prob: torch.Tensor, frame_name: str, resize_needed: bool = False, shape: Optional[Tuple[int, int]] = None,
                 last_frame: bool = False, path_to_image: str = None, image_u8: Optional[torch.Tensor] = None, *, frame_index: Optional[int] = None):
         """``image_u8`` (overlay='device'): the frame as uint8 [H, W, 3] at the output size, on the device or on the host; without it
         ``path_to_image`` is decoded with PIL and uploaded (slow: see the module docstring).
         ``frame_index`` (tracks): the frame's 1-based position in the video; without it the running count of reported frames."""
-        if self.egress == 'device':
-            return self._process_device(prob, frame_name, resize_needed, shape, last_frame, path_to_image, image_u8, frame_index=frame_index)
+        rest = dict(last_frame=last_frame, path_to_image=path_to_image, image_u8=image_u8, frame_index=frame_index)
+        if self.egress == 'device':              # one probability tensor, resampled inside the id stage: the full-size planes never exist
+            dev = self.processor.network.device
+            P, h, w = prob.shape
+            out_hw = (int(shape[0]), int(shape[1])) if resize_needed else (h, w)
+            lut_dev = self._lut_device(P, dev, uint8=True)
+            prob = self._planes_f32(prob, dev)
+
+            def id_stage(ol, ids, png):
+                ol.prob_to_id(prob, lut_dev, ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
+                              out_hw=out_hw if resize_needed else None, png=png)
+
+            def full_size():                     # (save_scores, as the host path: the scores of the output size)
+                return F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
+            return self._frame(frame_name, out_hw, id_stage, planes=prob, confidence=prob, scores=full_size, **rest)
         model_prob = prob                        # (tracks: the confidence is taken at the model's resolution)
         if resize_needed:
             prob = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0]
@@ -349,382 +312,7 @@ class ResultSaver:
                 if tmp_id < lut.shape[0]:
                     lut[tmp_id] = obj.id
             mask = lut[idx].to(out_dtype)
-        rg = {}
-        if self._regions_on:                     # before anything reads the plane: the scorer, the overlay, the vis modes, the tracks, the copy
-            mask = mask.contiguous()
-            rg = self._filter_plane(mask)
-        if self.scorer is not None:
-            self.scorer.add(frame_name, mask)
-        q = (prob * 255).to(torch.uint8).cpu() if self.save_scores else None       # == numpy astype(uint8) of prob*255
-        all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
-        ov = self._queue_overlay(None, mask, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
-        ov.update(rg)
-        if self._matte_on:
-            ov.update(self._queue_matte(prob, tuple(prob.shape[1:]), mask, all_ids, path_to_image, image_u8))
-        if self.tracks is not None:
-            ov.update(self._queue_tracks(mask, all_ids, model_prob, None, frame_index))
-        self.queue.put(_Job(self, mask.cpu(), frame_name, path_to_image, all_ids,
-                            prob=q, last_frame=last_frame,
-                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, **ov))
-
-    # ---- min_region / fill_holes -------------------------------------------------------------------------------------------------
-    def _add_regions(self, ol, ids) -> _RegionBuffers:
-        """Append the region filter of ``ids`` (uint8 [H, W] on the device, contiguous; rewritten in place) to the op list ``ol``.
-        -> the frame's count buffers: ``_copy_regions`` them once the list has been run."""
-        from ... import ops as O
-        dev = self.processor.network.device
-        H, W = int(ids.shape[0]), int(ids.shape[1])
-        if self._region_scratch is None or self._region_scratch[0] != (H, W):
-            self._region_scratch = ((H, W), torch.empty(O.OpList.region_scratch_words(H, W), dtype=torch.int32, device=dev))
-        try:
-            b = self._region_free.get_nowait()
-        except Empty:
-            if self._region_allocated < self.queue.maxsize + 2:
-                self._region_allocated += 1
-                b = _RegionBuffers(dev)
-            else:
-                b = self._region_free.get()      # the next set the writer gives back
-        ol.region_filter(ids, self._region_scratch[1], b.dev, min_region=self.min_region, fill_holes=self.fill_holes,
-                         connectivity=self.region_connectivity)
-        return b
-
-    @staticmethod
-    def _copy_regions(b: _RegionBuffers) -> dict:
-        """The pinned copy of the frame's counts (16 bytes) and the event behind it.  -> the _Job field.  Nothing waits here."""
-        b.host.copy_(b.dev, non_blocking=True)
-        b.event.record()
-        return dict(regions=b)
-
-    def _filter_plane(self, ids) -> dict:
-        """The region filter of a finished plane as an op list of its own, on the current stream.  -> the _Job field"""
-        from ... import ops as O
-        ol = O.OpList()
-        b = self._add_regions(ol, ids)
-        ol.run()
-        return self._copy_regions(b)
-
-    # ---- tracks -----------------------------------------------------------------------------------------------------------------
-    def _lut_device(self, P, dev):
-        """plane -> object id as int32 [P] on the device (PROB_TO_ID's lut; changes when objects come or go, not per frame)"""
-        lut = [0] * P
-        for tmp_id, obj in self.object_manager.tmp_id_to_obj.items():
-            if tmp_id < P:
-                lut[tmp_id] = int(obj.id)
-        lut_dev = self._luts.get(tuple(lut))
-        if lut_dev is None:
-            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
-        return lut_dev
-
-    def _queue_tracks(self, ids, all_ids, prob, lut_dev, frame_index) -> dict:
-        """Queue the track statistics of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
-        device), the pinned copy of the table (48 bytes per object) and an event.  ``prob``: f32 [P, h, w] as ``step`` returned it, or
-        None (no confidence); ``lut_dev``: its lut on the device when the caller has it.  -> the _Job fields.  Nothing waits here."""
-        from ... import ops as O
-        dev = self.processor.network.device
-        H, W = int(ids.shape[0]), int(ids.shape[1])
-        self._track_count += 1
-        meta = (self._track_count if frame_index is None else int(frame_index), list(all_ids), H, W)
-        n = len(all_ids)
-        if n == 0:                               # a frame without objects is reported with no rows: nothing to launch
-            return dict(track_meta=meta)
-        if n > O.OpList.TRACK_MAX_OBJECTS:
-            raise ValueError(f'tracks: {n} objects, at most {O.OpList.TRACK_MAX_OBJECTS} per frame')
-        objs = self._track_objs.get(tuple(all_ids))
-        if objs is None:                         # (changes when objects come or go, not per frame)
-            objs = self._track_objs[tuple(all_ids)] = torch.tensor(list(all_ids), dtype=torch.int32).to(dev)
-        if prob is not None:
-            if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
-                prob = prob.to(device=dev, dtype=torch.float32).contiguous()
-            if lut_dev is None:
-                lut_dev = self._lut_device(int(prob.shape[0]), dev)
-        try:
-            b = self._track_free.get_nowait()
-        except Empty:
-            if self._track_allocated < self.queue.maxsize + 2:
-                self._track_allocated += 1
-                b = _TrackBuffers(dev)
-            else:
-                b = self._track_free.get()       # the next set the writer gives back
-        words = n * O.OpList.TRACK_WORDS
-        ol = O.OpList()
-        ol.track_stats(ids, objs, b.dev[:words], prob=prob, lut=lut_dev if prob is not None else None)
-        ol.run()
-        b.host[:words].copy_(b.dev[:words], non_blocking=True)
-        b.event.record()
-        return dict(tracks=b, track_meta=meta)
-
-    # ---- egress='device' --------------------------------------------------------------------------------------------------------
-    def _take(self, H, W, device, png=True) -> _EgressBuffers:
-        """Buffers for one frame: a recycled set, a new one while fewer than the queue can hold (+ the one in the writer's hands and
-        this one) exist, else the next set the writer gives back."""
-        while True:
-            try:
-                b = self._free.get_nowait()
-            except Empty:
-                if self._allocated < self.queue.maxsize + 2:
-                    self._allocated += 1
-                    return _EgressBuffers(H, W, device, rle=self.json_style == 'burst' and png, png=png, jpeg=self.overlay == 'device')
-                b = self._free.get()
-            if (b.H, b.W) == (H, W) and b.kinds[1] == png:
-                return b
-            self._allocated -= 1                 # another geometry: dropped
-
-    # ---- overlay='device' -------------------------------------------------------------------------------------------------------
-    def _queue_overlay(self, b, ids, all_ids, path_to_image, image_u8) -> dict:
-        """Queue the blend + JPEG stage of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
-        device), and the pinned copy of its status and stream head.  ``b``: the frame's buffers (egress='device'; its event is recorded
-        by the caller behind everything) or None: a set of its own is taken and its event recorded here.  -> the _Job fields.
-        The frame tensor: the op list holds it while the stage is being queued, and the job holds it (and the id plane) until the
-        writer thread is done with the frame -- so it outlives the launch that reads it on the stream that owns it, whoever made it."""
-        from ... import ops as O
-        dev = self.processor.network.device
-        H, W = int(ids.shape[0]), int(ids.shape[1])
-        image_u8 = self._frame_u8(H, W, dev, path_to_image, image_u8)
-        self._jpeg_setup(H, W, dev)
-        colors = self._jpeg_colors.get(tuple(all_ids))
-        if colors is None:                       # (changes when objects come or go, not per frame)
-            colors = self._jpeg_colors[tuple(all_ids)] = torch.from_numpy(jpeg_writer.color_table(self.colors, all_ids)).to(dev)
-        own = b is None
-        if own:
-            b = self._take(H, W, dev, png=False)
-        ol = O.OpList()
-        ol.jpeg_encode(image_u8, ids, colors, self._jpeg_tables[1], b.jpeg_stream, b.jpeg_status, self._jpeg_scratch[1], H=H, W=W)
-        ol.run()
-        b.jpeg_host.copy_(b.jpeg_dev[:b.jpeg_host.numel()], non_blocking=True)
-        if own:
-            b.event.record()
-        return dict(overlay=b, frame=image_u8, ids=ids)
-
-    def _fetch_jpeg(self, b: _EgressBuffers):
-        """Writer thread: the frame's entropy-coded segment once its copy has landed, or None when it did not fit the device stream."""
-        return self._fetch_segment(b.event, b.jpeg_host, b.jpeg_stream)
-
-    def _fetch_segment(self, event, host, stream):
-        event.synchronize()
-        length, _, err, _ = (int(v) for v in host[:16].view(torch.int32))
-        if err != 0:
-            if not self._jpeg_warned:
-                self._jpeg_warned = True
-                log.warning(f'device JPEG encoder: a frame of {self.video_name} needs {length} bytes, the stream holds {stream.numel()}; '
-                            f'such frames are encoded on the host')
-            return None
-        have = host.numel() - 16
-        head = host[16:16 + min(length, have)].numpy().tobytes()
-        if length <= have:
-            return head
-        return head + self._rest(stream[have:length])
-
-    # ---- vis_modes / soft_masks / alpha_matte -------------------------------------------------------------------------------------
-    def _frame_u8(self, H, W, dev, path_to_image, image_u8):
-        """The frame as packed uint8 [H, W, 3] on the device (overlay='device' and the vis modes read it)."""
-        if image_u8 is None:
-            if path_to_image is None:
-                raise ValueError('Cannot visualize without path_to_image or image_u8')
-            image_u8 = torch.from_numpy(np.array(Image.open(path_to_image).convert('RGB')))
-        if image_u8.dtype != torch.uint8 or tuple(image_u8.shape) != (H, W, 3):
-            raise ValueError(f'image_u8 is uint8 [{H}, {W}, 3] (the output size), not {image_u8.dtype} {tuple(image_u8.shape)}')
-        if image_u8.device != dev or image_u8.stride(2) != 1 or image_u8.stride(1) != 3:
-            image_u8 = image_u8.to(dev).contiguous()
-        return image_u8
-
-    def _jpeg_setup(self, H, W, dev):
-        from ... import ops as O
-        if self._jpeg_tables is None:
-            qt = jpeg_writer.quant_tables(jpeg_writer.QUALITY)
-            self._jpeg_tables = (qt, torch.from_numpy(qt.view(np.int16)).to(dev))
-        if self._jpeg_scratch is None or self._jpeg_scratch[0] != (H, W):
-            self._jpeg_scratch = ((H, W), torch.empty(O.OpList.jpeg_enc_scratch_words(H, W), dtype=torch.int32, device=dev))
-
-    def _take_matte(self, H, W, K, dev) -> _MatteBuffers:
-        """As _take: a recycled set of the same geometry and plane count, a new one while few exist, else the next one given back."""
-        while True:
-            try:
-                b = self._matte_free.get_nowait()
-            except Empty:
-                if self._matte_allocated < self.queue.maxsize + 2:
-                    self._matte_allocated += 1
-                    return _MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev)
-                b = self._matte_free.get()
-            if (b.H, b.W, b.K) == (H, W, K):
-                return b
-            self._matte_allocated -= 1               # another geometry or object count: dropped
-
-    def _layer(self, H, W, dev):
-        """The RGBA layer at the output size on the device: resized with PIL and uploaded once per geometry."""
-        if self._layer_dev is None or self._layer_dev[0] != (H, W):
-            src = self._layer_src
-            if isinstance(src, (str, os.PathLike)):
-                src = Image.open(src)
-            if not isinstance(src, Image.Image):
-                src = Image.fromarray(np.asarray(src, dtype=np.uint8))
-            rgba = np.ascontiguousarray(np.array(src.convert('RGBA').resize((W, H))))
-            self._layer_dev = ((H, W), torch.from_numpy(rgba).to(dev))
-        return self._layer_dev[1]
-
-    def _queue_matte(self, prob, out_hw, ids, all_ids, path_to_image, image_u8) -> dict:
-        """Queue the composite launches of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
-        device), each followed by the JPEG stage on the composed frame, the soft-mask launch and the PNG stage per plane, the pinned
-        copies of every status block and stream head, and one event.  ``prob``: f32 [P, h, w] as ``step`` returned it, sampled at
-        ``out_hw`` inside the launches.  -> the _Job fields.  Nothing waits here."""
-        from ... import ops as O
-        dev = self.processor.network.device
-        H, W = int(out_hw[0]), int(out_hw[1])
-        P = int(prob.shape[0])
-        if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
-            prob = prob.to(device=dev, dtype=torch.float32).contiguous()
-        tmp_to_obj = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items() if int(t) < P}
-        K = P - 1 if self.soft_masks else 0
-        b = self._take_matte(H, W, K, dev)
-        wanted = all_ids if self.target_objects is None else self.target_objects
-        obj_to_tmp = {o: t for t, o in tmp_to_obj.items()}
-        targets = [obj_to_tmp[o] for o in wanted if o in obj_to_tmp]
-        ol = O.OpList()
-        if self.vis_modes:
-            frame = self._frame_u8(H, W, dev, path_to_image, image_u8)
-            self._jpeg_setup(H, W, dev)
-            colors = None
-            if any(m in ('davis', 'light', 'fade') for m in self.vis_modes):
-                colors = self._matte_colors.get(tuple(all_ids))
-                if colors is None:                   # the reference's colour map: the palette scaled by 1.5 (gui/interactive_utils.py:42-44)
-                    pal = np.array(self.palette, dtype=np.uint8).reshape(-1, 3) if self.palette is not None else davis_palette_np
-                    pal = (pal.astype(np.float32) * 1.5).clip(0, 255).astype(np.uint8)
-                    colors = self._matte_colors[tuple(all_ids)] = torch.from_numpy(jpeg_writer.color_table(pal, all_ids)).to(dev)
-            for k, mode in enumerate(self.vis_modes):
-                soft = mode in ('popup', 'layer')
-                with_matte = self.alpha_matte and soft and not any(m in ('popup', 'layer') for m in self.vis_modes[:k])
-                ol.matte_composite(mode, b.frames[k], out_hw=(H, W), frame=frame, planes=prob if soft else None, targets=targets,
-                                   ids=None if soft else ids, colors=None if soft else colors,
-                                   layer=self._layer(H, W, dev) if mode == 'layer' else None, matte=b.matte if with_matte else None)
-                ol.jpeg_encode(b.frames[k], None, None, self._jpeg_tables[1], b.jpeg_dev[k][16:], b.jpeg_dev[k][:16].view(torch.int32),
-                               self._jpeg_scratch[1], H=H, W=W)
-        if self.alpha_matte and not any(m in ('popup', 'layer') for m in self.vis_modes):
-            ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=targets, matte=b.matte)
-        if K > 0:
-            ol.matte_soft(prob, b.planes[:K], out_hw=(H, W))
-        if self._matte_png_scratch is None or self._matte_png_scratch[0] != (H, W):
-            self._matte_png_scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
-        for k in range(len(b.png_dev)):
-            ol.png_deflate(b.planes[k] if k < K else b.matte, b.png_dev[k][16:], b.png_dev[k][:16].view(torch.int32), self._matte_png_scratch[1], H=H, W=W)
-        ol.run()
-        for d, h in zip(b.jpeg_dev + b.png_dev, b.jpeg_host + b.png_host):
-            h.copy_(d[:h.numel()], non_blocking=True)
-        b.event.record()
-        return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep))
-
-    def _write_matte(self, job):
-        """Writer thread: the files of one frame's vis modes, soft masks and matte."""
-        b, base, stem = job.matte, path.join(self.output_root, self.video_name), job.frame_name[:-4]
-
-        def put(folder, name, data):
-            os.makedirs(path.join(base, folder), exist_ok=True)
-            with open(path.join(base, folder, name), 'wb') as f:
-                f.write(data)
-        for k, mode in enumerate(b.modes):
-            segment = self._fetch_segment(b.event, b.jpeg_host[k], b.jpeg_dev[k][16:])
-            if segment is not None:
-                put(path.join('visualization', mode), stem + '.jpg', jpeg_writer.wrap(segment, b.H, b.W, self._jpeg_tables[0]))
-            else:                                    # the segment did not fit the device stream: the composed frame through PIL
-                os.makedirs(path.join(base, 'visualization', mode), exist_ok=True)
-                Image.fromarray(self._to_host(b.frames[k])).save(path.join(base, 'visualization', mode, stem + '.jpg'))
-        for k in range(len(b.png_dev)):
-            b.event.synchronize()
-            host = b.png_host[k]
-            length, _, err, _ = (int(v) for v in host[:16].view(torch.int32))
-            if err != 0:
-                raise RuntimeError(f'device PNG encoder: error bits {err} (stream of {length} bytes, capacity {b.png_dev[k].numel() - 16})')
-            have = host.numel() - 16
-            stream = host[16:16 + min(length, have)].numpy().tobytes()
-            if length > have:
-                stream += self._rest(b.png_dev[k][16 + have:16 + length])
-            data = png_container.assemble(stream, b.H, b.W, None)
-            if k < b.K:
-                if job.matte_objects[k] is not None:
-                    put(path.join('soft_masks', str(job.matte_objects[k])), stem + '.png', data)
-            else:
-                put('alpha', stem + '.png', data)
-
-    def _to_host(self, t: torch.Tensor) -> np.ndarray:
-        """Writer thread: a device tensor as a numpy array, copied on a stream of the writer's own."""
-        if t.device.type != 'cuda':
-            return t.numpy()
-        if self._wstream is None:
-            self._wstream = torch.cuda.Stream(device=t.device)
-        with torch.cuda.stream(self._wstream):
-            out = t.to('cpu', non_blocking=False)
-        return out.numpy()
-
-    def _rest(self, tail: torch.Tensor) -> bytes:
-        """Writer thread: the part of a long stream behind the first slab, on a stream of the writer's own."""
-        if tail.device.type != 'cuda':
-            return tail.numpy().tobytes()
-        if self._wstream is None:
-            self._wstream = torch.cuda.Stream(device=tail.device)
-        rest = torch.empty(tail.numel(), dtype=torch.uint8).pin_memory()
-        with torch.cuda.stream(self._wstream):
-            rest.copy_(tail, non_blocking=True)
-        self._wstream.synchronize()
-        return rest.numpy().tobytes()
-
-    def _process_device(self, prob, frame_name, resize_needed, shape, last_frame, path_to_image=None, image_u8=None, *, frame_index=None):
-        from ... import ops as O
-        core = self.processor
-        dev = core.network.device
-        P, h, w = prob.shape
-        H, W = (int(shape[0]), int(shape[1])) if resize_needed else (h, w)
-        lut = [0] * P
-        for tmp_id, obj in self.object_manager.tmp_id_to_obj.items():
-            if tmp_id < P:
-                lut[tmp_id] = int(obj.id)
-        if max(lut) > 255:
-            raise ValueError('object ids above 255 need use_long_id')
-        lut_dev = self._luts.get(tuple(lut))
-        if lut_dev is None:                      # (changes when objects come or go, not per frame)
-            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
-        if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
-            prob = prob.to(device=dev, dtype=torch.float32).contiguous()
-        if self._scratch is None or self._scratch[0] != (H, W):
-            self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
-        b = self._take(H, W, dev)
-        ol = O.OpList()
-        rb = None
-        if self._regions_on:                     # ids, then the filter, then the PNG stage on its own on the filtered plane
-            ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
-                          out_hw=(H, W) if resize_needed else None, png=None)
-            rb = self._add_regions(ol, b.ids)
-            ol.png_deflate(b.ids, b.stream, b.status, self._scratch[1], H=H, W=W)
-        else:
-            ol.prob_to_id(prob, lut_dev, b.ids, P=P, H=h, W=w, plane=prob.stride(0), ldrow=prob.stride(1),
-                          out_hw=(H, W) if resize_needed else None, png=(b.stream, b.status, self._scratch[1]))
-        all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
-        rle = self.json_style == 'burst' and frame_name in self.annotated_frames
-        if rle:                                  # the objects' RLE strings of the finished plane, in the order of all_ids
-            n = len(all_ids)
-            objs = self._rle_objs.get(tuple(all_ids))
-            if objs is None:
-                objs = self._rle_objs[tuple(all_ids)] = torch.tensor(all_ids or [0], dtype=torch.int32).to(dev)
-            if self._rle_scratch is None or self._rle_scratch[0] != (H, W, n):
-                self._rle_scratch = ((H, W, n), torch.empty(O.OpList.rle_scratch_words(H, W, n), dtype=torch.int32, device=dev))
-            ol.rle_encode(b.ids, objs, b.rle_stream, b.rle_table, b.rle_status, self._rle_scratch[1], H=H, W=W, n_objects=n)
-        ol.run()
-        if self.scorer is not None:              # (b.ids is not handed out again before the writer is done with the frame: same stream)
-            self.scorer.add(frame_name, b.ids)
-        ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
-        if rb is not None:
-            ov.update(self._copy_regions(rb))
-        if self._matte_on:
-            ov.update(self._queue_matte(prob, (H, W), b.ids, all_ids, path_to_image, image_u8))
-        if self.tracks is not None:
-            ov.update(self._queue_tracks(b.ids, all_ids, prob, lut_dev, frame_index))
-        b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
-        if rle:
-            b.rle_host.copy_(b.rle_dev, non_blocking=True)
-        b.event.record()
-        q = None
-        if self.save_scores:                     # as the host path: the scores of the output size
-            full = F.interpolate(prob.unsqueeze(1), shape, mode='bilinear', align_corners=False)[:, 0] if resize_needed else prob
-            q = (full * 255).to(torch.uint8).cpu()
-        self.queue.put(_Job(self, None, frame_name, path_to_image if 'overlay' in ov else None, all_ids, prob=q, last_frame=last_frame,
-                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None, egress=b, rle=rle, **ov))
+        return self._frame(frame_name, tuple(prob.shape[1:]), None, mask=mask, planes=prob, confidence=model_prob, scores=lambda: prob, **rest)
 
     # ---- multi-scale merge on the device -------------------------------------------------------------------------------------------
     def process_merged(self, probs, frame_name: str, shape: Tuple[int, int], last_frame: bool = False, path_to_image: str = None, *,
@@ -758,99 +346,250 @@ class ResultSaver:
         P = int(probs[0].shape[0])
         if any(int(p.shape[0]) != P for p in probs):
             raise ValueError('process_merged: the members disagree on the number of planes')
-        H, W = int(shape[0]), int(shape[1])
-        lut = [0] * P
-        for tmp_id, obj_id in own.items():
-            if tmp_id < P:
-                lut[tmp_id] = obj_id
-        device_egress = self.egress == 'device'
-        if max(lut) > 255 and (device_egress or not self.use_long_id):
-            raise ValueError('object ids above 255 need use_long_id')
-        lut_dev = self._luts.get(tuple(lut))
-        if lut_dev is None:                      # (changes when objects come or go, not per frame)
-            lut_dev = self._luts[tuple(lut)] = torch.tensor(lut, dtype=torch.int32).to(dev)
-        probs = [p if (p.dtype == torch.float32 and p.device == dev and p.stride(2) == 1) else p.to(device=dev, dtype=torch.float32).contiguous()
-                 for p in probs]
-        ol = O.OpList()
+        out_hw = (int(shape[0]), int(shape[1]))
+        lut_dev = self._lut_device(P, dev, uint8=self.egress == 'device' or not self.use_long_id)
+        probs = [self._planes_f32(p, dev) for p in probs]
+
+        def id_stage(ol, ids, png):              # S merged sources
+            ol.prob_to_id_merged(probs, lut_dev, ids, out_hw=out_hw, png=png)
+        return self._frame(frame_name, out_hw, id_stage, last_frame=last_frame, path_to_image=path_to_image, image_u8=image_u8, frame_index=frame_index)
+
+    # ---- the frame path -----------------------------------------------------------------------------------------------------------
+    def _frame(self, frame_name, out_hw, id_stage, *, mask=None, planes=None, confidence=None, scores=None, last_frame=False,
+               path_to_image=None, image_u8=None, frame_index=None):
+        """One frame, whatever its id source.  ``id_stage(ol, ids, png)`` appends the stage that writes the id plane ``ids`` to the op
+        list -- fused with the PNG stage when ``png`` = (stream, status, scratch) is given --; None: ``mask`` is the finished plane (the
+        host path's torch argmax / ``output_prob_to_mask``) and nothing is appended.  ``planes``: the probabilities the vis modes and
+        soft masks sample at ``out_hw``; ``confidence``: those the track report reads, at the model's resolution (None: a merge);
+        ``scores()``: those ``save_scores`` keeps, at the output size.  Nothing waits here but the host path's copy of the plane (and
+        of the scores).
+        1. ONE op list: the id stage, the region filter -- before anything reads the plane --, with egress='device' the PNG stage
+           (fused with the id stage when no filter stands between them) and, on an annotated BURST frame, the RLE stage;
+        2. the scorer sees the plane on the device (a pooled plane is not handed out again before the writer is done with the frame);
+        3. the overlay, the copy of the filter's counts, the vis modes / soft masks / matte and the track report, each an op list of
+           its own behind the plane, each followed by its pinned copies;
+        4. the frame's own pinned copies with the event behind every copy, and the job -- which keeps alive what the launches read
+           until the writer has released the frame."""
+        from ... import ops as O
+        H, W = out_hw
+        on_device = self.egress == 'device'
         all_ids = [o.id for o in self.object_manager.obj_to_tmp_id]
-        if not device_egress:
-            ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=dev)
-            ol.prob_to_id_merged(probs, lut_dev, ids, out_hw=(H, W))
-            rb = self._add_regions(ol, ids) if self._regions_on else None
-            ol.run()
-            if self.scorer is not None:
-                self.scorer.add(frame_name, ids)
-            ov = self._queue_overlay(None, ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
-            if rb is not None:
-                ov.update(self._copy_regions(rb))
-            if self.tracks is not None:
-                ov.update(self._queue_tracks(ids, all_ids, None, None, frame_index))
-            self.queue.put(_Job(self, ids.cpu(), frame_name, path_to_image, all_ids, last_frame=last_frame, **ov))
-            return
-        if self._scratch is None or self._scratch[0] != (H, W):
-            self._scratch = ((H, W), torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
-        b = self._take(H, W, dev)
-        rb = None
-        if self._regions_on:                     # as in _process_device: the PNG stage on its own, on the filtered plane
-            ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W))
-            rb = self._add_regions(ol, b.ids)
-            ol.png_deflate(b.ids, b.stream, b.status, self._scratch[1], H=H, W=W)
+        ol, b, png = O.OpList(), None, None
+        if on_device:
+            dev = self.processor.network.device
+            b = self._pools['egress'].take(H, W, True)
+            ids = b.ids
+            png = (b.png.stream, b.png.status,
+                   self._scratch.get('png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev)))
+        elif id_stage is not None:
+            ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=self.processor.network.device)
         else:
-            ol.prob_to_id_merged(probs, lut_dev, b.ids, out_hw=(H, W), png=(b.stream, b.status, self._scratch[1]))
-        ol.run()
+            ids = mask.contiguous() if self._regions_on else mask
+        fused = None if self._regions_on else png
+        if id_stage is not None:
+            id_stage(ol, ids, fused)
+        rb = self._add_regions(ol, ids) if self._regions_on else None
+        if png is not None and fused is None:    # the PNG stage on its own, on the filtered plane
+            ol.png_deflate(ids, *png, H=H, W=W)
+        rle = on_device and self.json_style == 'burst' and frame_name in self.annotated_frames
+        if rle:                                  # the objects' RLE strings of the finished plane, in the order of all_ids
+            n = len(all_ids)
+            objs = self._tables.get('rle', tuple(all_ids), lambda: torch.tensor(all_ids or [0], dtype=torch.int32).to(dev))
+            scratch = self._scratch.get('rle', (H, W, n), lambda: torch.empty(O.OpList.rle_scratch_words(H, W, n), dtype=torch.int32, device=dev))
+            ol.rle_encode(ids, objs, b.rle.stream, b.rle_table, b.rle.status, scratch, H=H, W=W, n_objects=n)
+        if len(ol):
+            ol.run()
         if self.scorer is not None:
-            self.scorer.add(frame_name, b.ids)
-        ov = self._queue_overlay(b, b.ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
-        has_overlay = bool(ov)
-        if rb is not None:
-            ov.update(self._copy_regions(rb))
+            self.scorer.add(frame_name, ids)
+        fields = self._queue_overlay(b, ids, all_ids, path_to_image, image_u8) if self.overlay == 'device' else {}
+        job_image = path_to_image if (fields or not on_device) else None    # (the writer reads the file again only for a host overlay)
+        if rb is not None:                      # the pinned copy of the frame's counts (16 bytes) and the event behind it
+            rb.host.copy_(rb.dev, non_blocking=True)
+            rb.event.record()
+            fields['regions'] = rb
+        if self._matte_on:
+            fields.update(self._queue_matte(planes, out_hw, ids, all_ids, path_to_image, image_u8))
         if self.tracks is not None:
-            ov.update(self._queue_tracks(b.ids, all_ids, None, None, frame_index))
-        b.host.copy_(b.dev[:b.host.numel()], non_blocking=True)
+            fields.update(self._queue_tracks(ids, all_ids, confidence, None, frame_index))
+        if on_device:
+            b.png.copy()
+            if rle:
+                b.rle.copy()
+            b.event.record()
+        q = (scores() * 255).to(torch.uint8).cpu() if self.save_scores else None   # == numpy astype(uint8) of prob*255
+        self.queue.put(_Job(self, None if on_device else ids.cpu(), frame_name, job_image, all_ids, prob=q, last_frame=last_frame,
+                            tmp_to_obj={t: o.id for t, o in self.object_manager.tmp_id_to_obj.items()} if last_frame else None,
+                            egress=b, rle=rle, **fields))
+
+    def _lut_device(self, P, dev, uint8=False):
+        """plane -> object id as int32 [P] on the device (PROB_TO_ID's lut).  ``uint8``: the ids go into a uint8 plane."""
+        lut = [0] * P
+        for tmp_id, obj in self.object_manager.tmp_id_to_obj.items():
+            if tmp_id < P:
+                lut[tmp_id] = int(obj.id)
+        if uint8 and max(lut) > 255:
+            raise ValueError('object ids above 255 need use_long_id')
+        return self._tables.get('lut', tuple(lut), lambda: torch.tensor(lut, dtype=torch.int32).to(dev))
+
+    @staticmethod
+    def _planes_f32(prob, dev):
+        """probabilities as the launches read them: f32, on the device, last dimension contiguous (the view ``step`` returns is)"""
+        if prob.dtype != torch.float32 or prob.device != dev or prob.stride(2) != 1:
+            prob = prob.to(device=dev, dtype=torch.float32).contiguous()
+        return prob
+
+    # ---- min_region / fill_holes -------------------------------------------------------------------------------------------------
+    def _add_regions(self, ol, ids) -> RegionBuffers:
+        """Append the region filter of ``ids`` (uint8 [H, W] on the device, contiguous; rewritten in place) to the op list ``ol``.
+        -> the frame's count buffers, copied once the list has been run."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        scratch = self._scratch.get('regions', (H, W), lambda: torch.empty(O.OpList.region_scratch_words(H, W), dtype=torch.int32, device=dev))
+        b = self._pools['regions'].take()
+        ol.region_filter(ids, scratch, b.dev, min_region=self.min_region, fill_holes=self.fill_holes, connectivity=self.region_connectivity)
+        return b
+
+    # ---- tracks -----------------------------------------------------------------------------------------------------------------
+    def _queue_tracks(self, ids, all_ids, prob, lut_dev, frame_index) -> dict:
+        """Queue the track statistics of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), the pinned copy of the table (48 bytes per object) and an event.  ``prob``: f32 [P, h, w] as ``step`` returned it, or
+        None (no confidence); ``lut_dev``: its lut on the device, or None: ``_lut_device``'s.  -> the _Job fields.  Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        self._track_count += 1
+        meta = (self._track_count if frame_index is None else int(frame_index), list(all_ids), H, W)
+        n = len(all_ids)
+        if n == 0:                               # a frame without objects is reported with no rows: nothing to launch
+            return dict(track_meta=meta)
+        if n > O.OpList.TRACK_MAX_OBJECTS:
+            raise ValueError(f'tracks: {n} objects, at most {O.OpList.TRACK_MAX_OBJECTS} per frame')
+        objs = self._tables.get('tracks', tuple(all_ids), lambda: torch.tensor(list(all_ids), dtype=torch.int32).to(dev))
+        if prob is not None:
+            prob = self._planes_f32(prob, dev)
+            lut_dev = lut_dev if lut_dev is not None else self._lut_device(int(prob.shape[0]), dev)
+        b = self._pools['tracks'].take()
+        words = n * O.OpList.TRACK_WORDS
+        ol = O.OpList()
+        ol.track_stats(ids, objs, b.dev[:words], prob=prob, lut=lut_dev if prob is not None else None)
+        ol.run()
+        b.host[:words].copy_(b.dev[:words], non_blocking=True)
         b.event.record()
-        self.queue.put(_Job(self, None, frame_name, path_to_image if has_overlay else None, all_ids, last_frame=last_frame, egress=b, **ov))
+        return dict(tracks=b, track_meta=meta)
 
-    def _fetch(self, b: _EgressBuffers) -> bytes:
-        """Writer thread: the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
-        b.event.synchronize()
-        length, _, err, _ = (int(v) for v in b.host[:16].view(torch.int32))
-        if err != 0:
-            raise RuntimeError(f'device PNG encoder: error bits {err} (stream of {length} bytes, capacity {b.stream.numel()})')
-        have = b.host.numel() - 16
-        head = b.host[16:16 + min(length, have)].numpy().tobytes()
-        if length <= have:
-            return head
-        return head + self._rest(b.stream[have:length])      # the rare long stream
+    # ---- overlay='device' -------------------------------------------------------------------------------------------------------
+    def _queue_overlay(self, b, ids, all_ids, path_to_image, image_u8) -> dict:
+        """Queue the blend + JPEG stage of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), and the pinned copy of its status and stream head.  ``b``: the frame's buffers (egress='device'; its event is recorded
+        by the caller behind everything) or None: a set of its own is taken and its event recorded here.  -> the _Job fields.
+        The frame tensor: the op list holds it while the stage is being queued, and the job holds it (and the id plane) until the
+        writer thread is done with the frame -- so it outlives the launch that reads it on the stream that owns it, whoever made it."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        image_u8 = self._frame_u8(H, W, dev, path_to_image, image_u8)
+        qtables, scratch = self._jpeg_setup(H, W, dev)
+        colors = self._tables.get('overlay colors', tuple(all_ids), lambda: torch.from_numpy(jpeg_writer.color_table(self.colors, all_ids)).to(dev))
+        own = b is None
+        if own:
+            b = self._pools['egress'].take(H, W, False)
+        ol = O.OpList()
+        ol.jpeg_encode(image_u8, ids, colors, qtables, b.jpeg.stream, b.jpeg.status, scratch, H=H, W=W)
+        ol.run()
+        b.jpeg.copy()
+        if own:
+            b.event.record()
+        return dict(overlay=b, frame=image_u8, ids=ids)
 
-    def _fetch_rle(self, b: _EgressBuffers, all_obj_ids) -> dict:
-        """Writer thread, BURST: {object id: RLE string} of the frame's non-empty objects from the device encoder (its copy has
-        landed: the event is behind it).  If the strings did not fit the device stream, the frame is encoded here from a copy of the id
-        plane (logged once)."""
-        b.event.synchronize()
-        total, err, _, _ = (int(v) for v in b.rle_host[:16].view(torch.int32))
-        if err != 0:
-            if not self._rle_warned:
-                self._rle_warned = True
-                log.warning(f'device RLE encoder: a frame of {self.video_name} needs {total} bytes, the stream holds {b.rle_stream.numel()}; '
-                            f'such frames are encoded on the host')
-            if self._wstream is None:
-                self._wstream = torch.cuda.Stream(device=b.dev.device)
-            with torch.cuda.stream(self._wstream):
-                ids = b.ids.to('cpu', non_blocking=False).numpy()
-            return _host_rle(ids, all_obj_ids)
-        n = len(all_obj_ids)
-        table = b.rle_host[16:16 + 16 * n].view(torch.int32).view(-1, 4).numpy()
-        raw = b.rle_host[RLE_TABLE:RLE_TABLE + total].numpy().tobytes()
-        return {oid: raw[off:off + ln].decode('ascii') for oid, (off, ln, _, area) in zip(all_obj_ids, table.tolist()) if area > 0}
+    # ---- vis_modes / soft_masks / alpha_matte -------------------------------------------------------------------------------------
+    def _frame_u8(self, H, W, dev, path_to_image, image_u8):
+        """The frame as packed uint8 [H, W, 3] on the device (overlay='device' and the vis modes read it)."""
+        if image_u8 is None:
+            if path_to_image is None:
+                raise ValueError('Cannot visualize without path_to_image or image_u8')
+            image_u8 = torch.from_numpy(np.array(Image.open(path_to_image).convert('RGB')))
+        if image_u8.dtype != torch.uint8 or tuple(image_u8.shape) != (H, W, 3):
+            raise ValueError(f'image_u8 is uint8 [{H}, {W}, 3] (the output size), not {image_u8.dtype} {tuple(image_u8.shape)}')
+        if image_u8.device != dev or image_u8.stride(2) != 1 or image_u8.stride(1) != 3:
+            image_u8 = image_u8.to(dev).contiguous()
+        return image_u8
+
+    def _jpeg_setup(self, H, W, dev):
+        """-> the quantisation tables on the device (made once) and the JPEG stage's scratch for this geometry"""
+        from ... import ops as O
+        if self._jpeg_tables is None:
+            qt = jpeg_writer.quant_tables(jpeg_writer.QUALITY)
+            self._jpeg_tables = (qt, torch.from_numpy(qt.view(np.int16)).to(dev))
+        return self._jpeg_tables[1], self._scratch.get('jpeg', (H, W), lambda: torch.empty(O.OpList.jpeg_enc_scratch_words(H, W), dtype=torch.int32, device=dev))
+
+    def _layer(self, H, W, dev):
+        """The RGBA layer at the output size on the device: resized with PIL and uploaded once per geometry."""
+        def make():
+            src = self._layer_src
+            if isinstance(src, (str, os.PathLike)):
+                src = Image.open(src)
+            if not isinstance(src, Image.Image):
+                src = Image.fromarray(np.asarray(src, dtype=np.uint8))
+            return torch.from_numpy(np.ascontiguousarray(np.array(src.convert('RGBA').resize((W, H))))).to(dev)
+        return self._scratch.get('layer', (H, W), make)
+
+    def _matte_colors(self, all_ids, dev):
+        """the reference's colour map of the hard vis modes: the palette scaled by 1.5 (gui/interactive_utils.py:42-44)"""
+        def make():
+            pal = np.array(self.palette, dtype=np.uint8).reshape(-1, 3) if self.palette is not None else davis_palette_np
+            pal = (pal.astype(np.float32) * 1.5).clip(0, 255).astype(np.uint8)
+            return torch.from_numpy(jpeg_writer.color_table(pal, all_ids)).to(dev)
+        return self._tables.get('matte colors', tuple(all_ids), make)
+
+    def _queue_matte(self, prob, out_hw, ids, all_ids, path_to_image, image_u8) -> dict:
+        """Queue the composite launches of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
+        device), each followed by the JPEG stage on the composed frame, the soft-mask launch and the PNG stage per plane, the pinned
+        copies of every status block and stream head, and one event.  ``prob``: f32 [P, h, w] as ``step`` returned it, sampled at
+        ``out_hw`` inside the launches.  -> the _Job fields.  Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(out_hw[0]), int(out_hw[1])
+        P = int(prob.shape[0])
+        prob = self._planes_f32(prob, dev)
+        tmp_to_obj = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items() if int(t) < P}
+        K = P - 1 if self.soft_masks else 0
+        b = self._pools['matte'].take(H, W, K)
+        wanted = all_ids if self.target_objects is None else self.target_objects
+        obj_to_tmp = {o: t for t, o in tmp_to_obj.items()}
+        targets = [obj_to_tmp[o] for o in wanted if o in obj_to_tmp]
+        ol = O.OpList()
+        if self.vis_modes:
+            frame = self._frame_u8(H, W, dev, path_to_image, image_u8)
+            qtables, scratch = self._jpeg_setup(H, W, dev)
+            colors = self._matte_colors(all_ids, dev) if any(m in ('davis', 'light', 'fade') for m in self.vis_modes) else None
+            for k, mode in enumerate(self.vis_modes):
+                soft = mode in ('popup', 'layer')
+                with_matte = self.alpha_matte and soft and not any(m in ('popup', 'layer') for m in self.vis_modes[:k])
+                ol.matte_composite(mode, b.frames[k], out_hw=(H, W), frame=frame, planes=prob if soft else None, targets=targets,
+                                   ids=None if soft else ids, colors=None if soft else colors,
+                                   layer=self._layer(H, W, dev) if mode == 'layer' else None, matte=b.matte if with_matte else None)
+                ol.jpeg_encode(b.frames[k], None, None, qtables, b.jpeg[k].stream, b.jpeg[k].status, scratch, H=H, W=W)
+        if self.alpha_matte and not any(m in ('popup', 'layer') for m in self.vis_modes):
+            ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=targets, matte=b.matte)
+        if K > 0:
+            ol.matte_soft(prob, b.planes[:K], out_hw=(H, W))
+        scratch = self._scratch.get('matte png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+        for k, slab in enumerate(b.png):
+            ol.png_deflate(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch, H=H, W=W)
+        ol.run()
+        for slab in b.jpeg + b.png:
+            slab.copy()
+        b.event.record()
+        return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep))
 
     def end(self):
         self.queue.put(None)
         self.queue.join()
         self.thread.join()
-        self._free, self._allocated, self._scratch = Queue(), 0, None
-        self._matte_free, self._matte_allocated, self._matte_png_scratch = Queue(), 0, None
-        self._track_free, self._track_allocated = Queue(), 0
-        self._region_free, self._region_allocated, self._region_scratch = Queue(), 0, None
+        for pool in self._pools.values():
+            pool.reset()
+        self._scratch.clear()
         if self._regions_on:
             t = [int(v) for v in self._region_totals]
             self.regions = dict(min_region=self.min_region, fill_holes=self.fill_holes, connectivity=self.region_connectivity,
@@ -859,6 +598,145 @@ class ResultSaver:
             self.scores = self.scorer.finish()
         if self.tracks is not None:
             self.tracks.write(path.join(self.tracks_output_root, self.video_name))
+
+    # ---- the writer thread: one function per output family, called by _writer in this order ---------------------------------------
+    def _put(self, root, folder, name, data: bytes):
+        os.makedirs(path.join(root, self.video_name, folder), exist_ok=True)
+        with open(path.join(root, self.video_name, folder, name), 'wb') as f:
+            f.write(data)
+
+    def _mask_stream(self, b: EgressBuffers) -> bytes:
+        """egress='device': the frame's zlib stream, once its copy has landed.  Raises when the device set the error word."""
+        return b.png.fetch(b.event)
+
+    def _write_mask(self, job):
+        """``<frame>.png``: the device's stream wrapped (egress='device'; no PIL), or the id plane through PIL.
+        -> the RGB mask of a long-id frame (the host overlay blends it)"""
+        stem, rgb_mask = job.frame_name[:-4], None
+        if job.egress is not None:
+            b = job.egress
+            self._put(self.output_root, '', stem + '.png', png_container.assemble(self._mask_stream(b), b.H, b.W, self.palette))
+        elif self.save_mask:
+            out_mask = job.mask.numpy()
+            if self.use_long_id:
+                m = out_mask.astype(np.uint32)
+                rgb_mask = np.zeros((*m.shape[-2:], 3), dtype=np.uint8)
+                for oid in job.all_obj_ids:
+                    rgb_mask[m == oid] = self.id2rgb_converter.convert(oid)[1]
+                out_img = Image.fromarray(rgb_mask)
+            else:
+                out_img = Image.fromarray(out_mask.astype(np.uint8))
+                if self.palette is not None:
+                    out_img.putpalette(self.palette)
+            out_dir = path.join(self.output_root, self.video_name)
+            os.makedirs(out_dir, exist_ok=True)
+            out_img.save(path.join(out_dir, stem + '.png'))
+        return rgb_mask
+
+    def _device_rle(self, b: EgressBuffers, all_obj_ids) -> dict:
+        """BURST, egress='device': {object id: RLE string} of the frame's non-empty objects from the device encoder.  If the strings
+        did not fit the device stream, the frame is encoded here from a copy of the id plane (logged once)."""
+        raw = b.rle.fetch(b.event)
+        if raw is None:
+            return _host_rle(self._copies.to_host(b.ids), all_obj_ids)
+        table = np.frombuffer(raw, dtype=np.int32, count=4 * len(all_obj_ids)).reshape(-1, 4)
+        raw = raw[RLE_TABLE - 16:]
+        return {oid: raw[off:off + ln].decode('ascii') for oid, (off, ln, _, area) in zip(all_obj_ids, table.tolist()) if area > 0}
+
+    def _write_burst(self, job):
+        """BURST, an annotated frame: the objects' segmentations into ``self.segmentations`` (results_utils.py:153-171)"""
+        if self.json_style != 'burst' or job.frame_name not in self.annotated_frames:
+            return
+        index = self.annotated_frames.index(job.frame_name)
+        input_segments, frame_segments = self.input_segmentations[index], self.segmentations[index]
+        if job.rle:
+            strings = self._device_rle(job.egress, job.all_obj_ids)
+        else:
+            strings = _host_rle(job.mask.numpy(), [i for i in job.all_obj_ids if i not in input_segments])
+        for oid in job.all_obj_ids:
+            # (as executed: the object ids are ints, the keys of a json that was loaded from a file are strings, so the copy
+            # only happens for an init_json whose keys are ints; everything else is encoded.  Keys turn into strings at json.dump)
+            if oid in input_segments:
+                frame_segments[oid] = input_segments[oid]
+            elif oid in strings:
+                frame_segments[oid] = {'rle': strings[oid]}
+
+    def _write_scores(self, job):
+        if not self.save_scores:
+            return
+        sc_dir = path.join(self.score_output_root, self.video_name)
+        os.makedirs(sc_dir, exist_ok=True)
+        if job.last_frame:                                     # the reference's backward.hkl: {object id: tmp id}
+            ids = sorted(job.tmp_to_obj.items())
+            np.savez(path.join(sc_dir, 'backward.npz'), obj_ids=np.array([o for _, o in ids], dtype=np.int64),
+                     tmp_ids=np.array([t for t, _ in ids], dtype=np.int64))
+        np.savez_compressed(path.join(sc_dir, job.frame_name[:-4] + '.npz'), prob=job.prob.numpy())
+
+    def _write_matte(self, job):
+        """The files of one frame's vis modes, soft masks and matte."""
+        b, stem = job.matte, job.frame_name[:-4]
+        if b is None:
+            return
+        for k, mode in enumerate(b.modes):
+            segment = b.jpeg[k].fetch(b.event)
+            if segment is not None:
+                self._put(self.output_root, path.join('visualization', mode), stem + '.jpg', jpeg_writer.wrap(segment, b.H, b.W, self._jpeg_tables[0]))
+            else:                                    # the segment did not fit the device stream: the composed frame through PIL
+                folder = path.join(self.output_root, self.video_name, 'visualization', mode)
+                os.makedirs(folder, exist_ok=True)
+                Image.fromarray(self._copies.to_host(b.frames[k])).save(path.join(folder, stem + '.jpg'))
+        for k, slab in enumerate(b.png):
+            data = png_container.assemble(slab.fetch(b.event), b.H, b.W, None)
+            if k >= b.K:
+                self._put(self.output_root, 'alpha', stem + '.png', data)
+            elif job.matte_objects[k] is not None:
+                self._put(self.output_root, path.join('soft_masks', str(job.matte_objects[k])), stem + '.png', data)
+
+    def _write_tracks(self, job):
+        """The frame's rows to the track report: its table has landed behind its event (no table: a frame without objects)."""
+        if job.track_meta is None:
+            return
+        index, objs, H, W = job.track_meta
+        if job.tracks is not None:
+            job.tracks.event.synchronize()
+            table = job.tracks.host[:len(objs) * 12].numpy().reshape(-1, 12).copy()
+        else:
+            table = np.zeros((0, 12), dtype=np.int32)
+        self.tracks.add(job.frame_name, index, table, objs, H, W)
+
+    def _write_regions(self, job):
+        """min_region / fill_holes: the frame's counts, landed behind their event, to the video's totals"""
+        if job.regions is not None:
+            job.regions.event.synchronize()
+            self._region_totals += job.regions.host.numpy()
+            self._region_frames += 1
+
+    def _write_overlay(self, job, rgb_mask):
+        """``<frame>.jpg`` of ``visualize``: the device's segment wrapped (overlay='device'; no PIL), else the host's blend through PIL
+        -- also for a frame whose segment did not fit the device stream."""
+        stem = job.frame_name[:-4]
+        segment = job.overlay.jpeg.fetch(job.overlay.event) if job.overlay is not None else None
+        if segment is not None:
+            self._put(self.visualize_output_root, '', stem + '.jpg', jpeg_writer.wrap(segment, job.overlay.H, job.overlay.W, self._jpeg_tables[0]))
+        elif self.visualize:
+            out_mask = job.mask.numpy() if job.mask is not None else None
+            if job.overlay is not None:                        # the segment did not fit the device stream: this frame on the host
+                if out_mask is None:
+                    out_mask = job.ids.cpu().numpy()
+                image_np = np.array(Image.open(job.path_to_image).convert('RGB')) if job.path_to_image is not None else job.frame.cpu().numpy()
+            elif job.path_to_image is None:
+                raise ValueError('Cannot visualize without path_to_image')
+            else:
+                image_np = np.array(Image.open(job.path_to_image).convert('RGB'))
+            if rgb_mask is None:
+                rgb_mask = np.zeros((*out_mask.shape, 3), dtype=np.uint8)
+                for oid in job.all_obj_ids:
+                    rgb_mask[out_mask == oid] = self.colors[oid % len(self.colors)]
+            alpha = ((out_mask == 0).astype(np.float32) * 0.5 + 0.5)[:, :, None]
+            blend = (image_np * alpha + rgb_mask * (1 - alpha)).astype(np.uint8)
+            vis_dir = path.join(self.visualize_output_root, self.video_name)
+            os.makedirs(vis_dir, exist_ok=True)
+            Image.fromarray(blend).save(path.join(vis_dir, stem + '.jpg'))
 
 
 def _host_rle(ids: np.ndarray, all_obj_ids) -> dict:
@@ -879,102 +757,18 @@ def _writer(queue: Queue):
             break
         try:
             s = job.saver
-            strings = None
-            if job.egress is not None:                             # egress='device': wrap the finished stream, no PIL
-                b = job.egress
-                if job.rle:
-                    strings = s._fetch_rle(b, job.all_obj_ids)
-                data = png_container.assemble(s._fetch(b), b.H, b.W, s.palette)
-                out_dir = path.join(s.output_root, s.video_name)
-                os.makedirs(out_dir, exist_ok=True)
-                with open(path.join(out_dir, job.frame_name[:-4] + '.png'), 'wb') as f:
-                    f.write(data)
-            out_mask = job.mask.numpy() if job.mask is not None else None
-            if s.json_style == 'burst' and job.frame_name in s.annotated_frames:      # results_utils.py:153-171
-                index = s.annotated_frames.index(job.frame_name)
-                input_segments, frame_segments = s.input_segmentations[index], s.segmentations[index]
-                if strings is None:
-                    strings = _host_rle(out_mask, [i for i in job.all_obj_ids if i not in input_segments])
-                for oid in job.all_obj_ids:
-                    # (as executed: the object ids are ints, the keys of a json that was loaded from a file are strings, so the copy
-                    # only happens for an init_json whose keys are ints; everything else is encoded.  Keys turn into strings at json.dump)
-                    if oid in input_segments:
-                        frame_segments[oid] = input_segments[oid]
-                    elif oid in strings:
-                        frame_segments[oid] = {'rle': strings[oid]}
-            rgb_mask = None
-            if s.save_mask and job.egress is None:
-                if s.use_long_id:
-                    m = out_mask.astype(np.uint32)
-                    rgb_mask = np.zeros((*m.shape[-2:], 3), dtype=np.uint8)
-                    for oid in job.all_obj_ids:
-                        rgb_mask[m == oid] = s.id2rgb_converter.convert(oid)[1]
-                    out_img = Image.fromarray(rgb_mask)
-                else:
-                    out_img = Image.fromarray(out_mask.astype(np.uint8))
-                    if s.palette is not None:
-                        out_img.putpalette(s.palette)
-                out_dir = path.join(s.output_root, s.video_name)
-                os.makedirs(out_dir, exist_ok=True)
-                out_img.save(path.join(out_dir, job.frame_name[:-4] + '.png'))
-            if s.save_scores:
-                sc_dir = path.join(s.score_output_root, s.video_name)
-                os.makedirs(sc_dir, exist_ok=True)
-                if job.last_frame:                                 # the reference's backward.hkl: {object id: tmp id}
-                    ids = sorted(job.tmp_to_obj.items())
-                    np.savez(path.join(sc_dir, 'backward.npz'), obj_ids=np.array([o for _, o in ids], dtype=np.int64),
-                             tmp_ids=np.array([t for t, _ in ids], dtype=np.int64))
-                np.savez_compressed(path.join(sc_dir, job.frame_name[:-4] + '.npz'), prob=job.prob.numpy())
-            if job.matte is not None:
-                s._write_matte(job)
-            if job.track_meta is not None:                         # tracks: the frame's table has landed behind its event
-                index, objs, H, W = job.track_meta
-                if job.tracks is not None:
-                    job.tracks.event.synchronize()
-                    table = job.tracks.host[:len(objs) * 12].numpy().reshape(-1, 12).copy()
-                else:
-                    table = np.zeros((0, 12), dtype=np.int32)
-                s.tracks.add(job.frame_name, index, table, objs, H, W)
-            if job.regions is not None:                            # min_region / fill_holes: the frame's counts have landed behind their event
-                job.regions.event.synchronize()
-                s._region_totals += job.regions.host.numpy()
-                s._region_frames += 1
-            segment =s._fetch_jpeg(job.overlay) if job.overlay is not None else None
-            if segment is not None:                                # overlay='device': wrap the finished segment, no PIL
-                vis_dir = path.join(s.visualize_output_root, s.video_name)
-                os.makedirs(vis_dir, exist_ok=True)
-                with open(path.join(vis_dir, job.frame_name[:-4] + '.jpg'), 'wb') as f:
-                    f.write(jpeg_writer.wrap(segment, job.overlay.H, job.overlay.W, s._jpeg_tables[0]))
-            elif s.visualize:
-                if job.overlay is not None:                        # the segment did not fit the device stream: this frame on the host
-                    if out_mask is None:
-                        out_mask = job.ids.cpu().numpy()
-                    image_np = np.array(Image.open(job.path_to_image).convert('RGB')) if job.path_to_image is not None else job.frame.cpu().numpy()
-                elif job.path_to_image is None:
-                    raise ValueError('Cannot visualize without path_to_image')
-                else:
-                    image_np = np.array(Image.open(job.path_to_image).convert('RGB'))
-                if rgb_mask is None:
-                    rgb_mask = np.zeros((*out_mask.shape, 3), dtype=np.uint8)
-                    for oid in job.all_obj_ids:
-                        rgb_mask[out_mask == oid] = s.colors[oid % len(s.colors)]
-                alpha = ((out_mask == 0).astype(np.float32) * 0.5 + 0.5)[:, :, None]
-                blend = (image_np * alpha + rgb_mask * (1 - alpha)).astype(np.uint8)
-                vis_dir = path.join(s.visualize_output_root, s.video_name)
-                os.makedirs(vis_dir, exist_ok=True)
-                Image.fromarray(blend).save(path.join(vis_dir, job.frame_name[:-4] + '.jpg'))
+            rgb_mask = s._write_mask(job)
+            s._write_burst(job)
+            s._write_scores(job)
+            s._write_matte(job)
+            s._write_tracks(job)
+            s._write_regions(job)
+            s._write_overlay(job, rgb_mask)
         except Exception as e:                                 # keep the queue draining; surface the problem
             log.error(f'result writer failed on {job.frame_name}: {e}')
         finally:
-            b = job.egress if job.egress is not None else job.overlay
-            if b is not None:                                  # the frame's buffers go back to the pool
-                job.saver._free.put(b)
-            if job.matte is not None:
-                job.saver._matte_free.put(job.matte)
-            if job.tracks is not None:
-                job.saver._track_free.put(job.tracks)
-            if job.regions is not None:
-                job.saver._region_free.put(job.regions)
+            for b in job.held():                               # the frame's buffers go back to their pools
+                b.pool.put(b)
         queue.task_done()
 
 

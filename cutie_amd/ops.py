@@ -330,6 +330,40 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _need_form(has, words):
+    """A form that came without a new ABI number: a library built before it (``has``: its _lib.has_* probe) is named as stale, in
+    ``words``.  (An injected interpreter of the tests has no library; a missing library fails when the list runs.)"""
+    try:
+        known = getattr(_lib._executor, 'is_mock', False) or has()
+    except _lib.HipLibraryError:
+        known = True
+    if not known:
+        raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale ({words}); rebuild it.')
+
+
+def _u8_plane(who, name, t, hw=None):
+    """``t`` is a contiguous uint8 [H, W] -- of the size ``hw`` when given -- with H, W >= 1 and H * W < 2^31.  -> (H, W)"""
+    shaped = t.dim() == 2 if hw is None else tuple(t.shape) == tuple(hw)
+    if t.dtype != torch.uint8 or not shaped or not t.is_contiguous():
+        if hw is None or (min(hw) >= 1 and hw[0] * hw[1] < 1 << 31):        # (a size given apart is judged first)
+            raise ValueError(f"{who}: {name} is a contiguous uint8 {'[H, W]' if hw is None else list(hw)}, not {t.dtype} {tuple(t.shape)}")
+    H, W = hw if hw is not None else (int(t.shape[0]), int(t.shape[1]))
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError(f'{who}: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+    return H, W
+
+
+def _object_ids(who, name, objects):
+    """Object ids as a sequence of ints or as an int32 tensor of them on the device, which is not inspected.
+    -> (n, the tensor or None, the list or None)"""
+    if torch.is_tensor(objects):
+        if objects.dtype != torch.int32 or objects.dim() != 1 or not objects.is_contiguous():
+            raise ValueError(f'{who}: {name} on the device are a contiguous int32 [n]')
+        return int(objects.numel()), objects, None
+    listed = [int(v) for v in objects]
+    return len(listed), None, listed
+
+
 JPEG_SYNC_ROUNDS = 4        # sync rounds of the speculative Huffman decode before a segment is finished serially (jpeg.hip)
 
 
@@ -996,27 +1030,18 @@ class OpList:
         (inference/utils/davis_metrics.py).  scratch int32 [>= jf_scratch_words(H, W, n)], 16-byte aligned (allocated here when not
         given); counts 16-byte aligned."""
         H, W, radius = int(H), int(W), int(radius)
-        if torch.is_tensor(objects):
-            if objects.dtype != torch.int32 or objects.dim() != 1 or not objects.is_contiguous():
-                raise ValueError('jf_counts: objects on the device are a contiguous int32 [n]')
-            n, objs = int(objects.numel()), objects
-        else:
-            ids = [int(v) for v in objects]
-            n = len(ids)
+        n, objs, ids = _object_ids('jf_counts', 'objects', objects)
+        if ids is not None:
             if any(v < 1 or v >= 255 for v in ids):
                 raise ValueError(f'jf_counts: object ids are 1 .. 254 (0 is the background, 255 the void label), not {ids}')
             if len(set(ids)) != n:
                 raise ValueError(f'jf_counts: duplicate object ids in {ids}')
-            objs = None
         if not 1 <= n <= self.JF_MAX_OBJECTS:
             raise ValueError(f'jf_counts: {n} objects, 1 .. {self.JF_MAX_OBJECTS}')
-        if H < 1 or W < 1 or H * W >= 1 << 31:
-            raise ValueError(f'jf_counts: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        for name, t in (('pred', pred), ('gt', gt)):
+            _u8_plane('jf_counts', name, t, (H, W))
         if not 1 <= radius <= self.JF_MAX_RADIUS:
             raise ValueError(f'jf_counts: radius {radius}, 1 .. {self.JF_MAX_RADIUS}')
-        for name, t in (('pred', pred), ('gt', gt)):
-            if t.dtype != torch.uint8 or tuple(t.shape) != (H, W) or not t.is_contiguous():
-                raise ValueError(f'jf_counts: {name} is a contiguous uint8 [{H}, {W}], not {t.dtype} {tuple(t.shape)}')
         if counts.dtype != torch.int32 or counts.numel() != n * 8 or not counts.is_contiguous():
             raise ValueError(f'jf_counts: counts is a contiguous int32 [{n}, 8]')
         need = self.jf_scratch_words(H, W, n)
@@ -1043,26 +1068,9 @@ class OpList:
         (64-bit).  Entries outside 1 .. 255 are absent objects, a repeated entry gets the first one's row; an object without a pixel
         has area 0, xmin = W, ymin = H, xmax = ymax = -1.  table 16-byte aligned.  The caller keeps ``prob`` alive until the launch
         has run (the list holds it)."""
-        # the form came without a new ABI number (an injected interpreter of the tests has no library; a missing library fails when the list runs)
-        if not getattr(_lib._executor, 'is_mock', False):
-            try:
-                known = _lib.has_track_stats()
-            except _lib.HipLibraryError:
-                known = True
-            if not known:
-                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no track statistics, PROB_TO_ID flags == 1024); rebuild it.')
-        if ids_plane.dtype != torch.uint8 or ids_plane.dim() != 2 or not ids_plane.is_contiguous():
-            raise ValueError(f'track_stats: ids_plane is a contiguous uint8 [H, W], not {ids_plane.dtype} {tuple(ids_plane.shape)}')
-        H, W = int(ids_plane.shape[0]), int(ids_plane.shape[1])
-        if H < 1 or W < 1 or H * W >= 1 << 31:
-            raise ValueError(f'track_stats: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
-        if torch.is_tensor(obj_ids):
-            if obj_ids.dtype != torch.int32 or obj_ids.dim() != 1 or not obj_ids.is_contiguous():
-                raise ValueError('track_stats: obj_ids on the device are a contiguous int32 [n]')
-            n, objs = int(obj_ids.numel()), obj_ids
-        else:
-            listed = [int(v) for v in obj_ids]
-            n, objs = len(listed), None
+        _need_form(_lib.has_track_stats, 'no track statistics, PROB_TO_ID flags == 1024')
+        H, W = _u8_plane('track_stats', 'ids_plane', ids_plane)
+        n, objs, listed = _object_ids('track_stats', 'obj_ids', obj_ids)
         if not 0 <= n <= self.TRACK_MAX_OBJECTS:
             raise ValueError(f'track_stats: {n} objects, 0 .. {self.TRACK_MAX_OBJECTS}')
         if table.dtype != torch.int32 or table.numel() != n * self.TRACK_WORDS or not table.is_contiguous():
@@ -1100,19 +1108,8 @@ class OpList:
         pixels become 0, then enclosed background components of fewer than ``fill_holes`` pixels get the id left of their first pixel.
         Thresholds 0 and 1 switch a stage off.  ``scratch``: int32, at least ``region_scratch_words(H, W)`` words; ``counts``: int32
         [4], WRITTEN by the launch: islands removed | pixels cleared | holes filled | pixels filled."""
-        # the form came without a new ABI number (an injected interpreter of the tests has no library; a missing library fails when the list runs)
-        if not getattr(_lib._executor, 'is_mock', False):
-            try:
-                known = _lib.has_region_filter()
-            except _lib.HipLibraryError:
-                known = True
-            if not known:
-                raise _lib.HipLibraryError(f'{_lib.LIB_PATH} is stale (no region filter, PROB_TO_ID flags == 2048); rebuild it.')
-        if ids_plane.dtype != torch.uint8 or ids_plane.dim() != 2 or not ids_plane.is_contiguous():
-            raise ValueError(f'region_filter: ids_plane is a contiguous uint8 [H, W], not {ids_plane.dtype} {tuple(ids_plane.shape)}')
-        H, W = int(ids_plane.shape[0]), int(ids_plane.shape[1])
-        if H < 1 or W < 1 or H * W >= 1 << 31:
-            raise ValueError(f'region_filter: a plane of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        _need_form(_lib.has_region_filter, 'no region filter, PROB_TO_ID flags == 2048')
+        H, W = _u8_plane('region_filter', 'ids_plane', ids_plane)
         min_region, fill_holes, connectivity = int(min_region), int(fill_holes), int(connectivity)
         if min_region < 0 or fill_holes < 0 or max(min_region, fill_holes) >= 1 << 31:
             raise ValueError(f'region_filter: min_region {min_region} and fill_holes {fill_holes} are 32-bit and not negative')

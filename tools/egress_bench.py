@@ -78,9 +78,10 @@ class CountingSaver(ResultSaver):
             self.copied += int(h) * int(w)
         return super().process(prob, frame_name, resize_needed=resize_needed, shape=shape, **kw)
 
-    def _fetch(self, b):
-        data = super()._fetch(b)
-        self.copied += b.host.numel() + max(0, len(data) - (b.host.numel() - 16))
+    def _mask_stream(self, b):
+        data = super()._mask_stream(b)
+        head = b.png.host.numel()
+        self.copied += head + max(0, len(data) - (head - 16))
         return data
 
 

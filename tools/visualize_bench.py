@@ -45,7 +45,7 @@ def overlay_inputs(H, W):
 
 
 def host_blend(image_np, out_mask, all_obj_ids, colors):
-    """results_utils.py _writer: the host overlay's blend."""
+    """results_utils.py _write_overlay: the host overlay's blend."""
     rgb_mask = np.zeros((*out_mask.shape, 3), dtype=np.uint8)
     for oid in all_obj_ids:
         rgb_mask[out_mask == oid] = colors[oid % len(colors)]

@@ -94,6 +94,13 @@ def has_region_filter():
     return bool(load().cutie_hip_build_flags() & 32)
 
 
+def has_edt_band():
+    """Does the loaded library know PROB_TO_ID flags == 4096, the exact distance transform of an id plane and its bands?  Added without a
+    new ABI number; a library from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing
+    (ResultSaver trimap= / trimap_objects= / dilate_mask=)."""
+    return bool(load().cutie_hip_build_flags() & 64)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

@@ -22,6 +22,12 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
                                             below N pixels become background, then enclosed background components below N pixels get
                                             the id left of their first pixel (csrc/regions.hip); masks, RLE strings, overlays, --tracks
                                             and --score see the filtered plane, the model does not; not for long-id (RGB) masks)
+        [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
+                                           (what matting and inpainting models take: OUT/<video>/trimap/*.png (0 | 128 | 255: the band
+                                            of R_IN pixels inside and R_OUT pixels outside the edge of all objects is unknown), one
+                                            trimap per object in trimap_objects/<id>/, and all objects dilated by the disk of R pixels in
+                                            dilated/*.png; exact Euclidean distances, measured on the GPU on the plane of the mask that is
+                                            written (csrc/edt.hip); not for long-id (RGB) masks)
         [--tracks]                         (one row per object and saved frame -- area, box, centroid, confidence -- counted on the GPU from the id
                                             plane and the probabilities (inference/utils/track_report.py): OUT/tracks/<video>/tracks.json and
                                             tracks_mot.txt; with --sizes the confidence is null; not for long-id (RGB) masks)
@@ -128,10 +134,14 @@ def _take(windows, dev, lookahead):
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
            score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', tracks=False,
-           tracks_output_root=None, regions=None) -> ResultSaver:
+           tracks_output_root=None, regions=None, bands=None) -> ResultSaver:
     """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer.
     tracks (--tracks): the saver gets the video's own TrackReport and writes it into tracks_output_root/<video>/ when it ends.
-    regions (--min-region / --fill-holes / --region-connectivity): (min_region, fill_holes, connectivity) of the saver's region filter."""
+    regions (--min-region / --fill-holes / --region-connectivity): (min_region, fill_holes, connectivity) of the saver's region filter.
+    bands (--trimap / --trimap-objects / --dilate-mask): (trimap, trimap_objects, dilate_mask) of the saver, over all objects."""
+    trimap, trimap_objects, dilate_mask = bands if bands is not None else (None, False, 0.0)
+    if bands is not None and vid_reader.use_long_id:
+        raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no trimap, no dilated mask')
     min_region, fill_holes, connectivity = regions if regions is not None else (0, 0, 8)
     if max(min_region, fill_holes) >= 2 and vid_reader.use_long_id:
         raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no region filter')
@@ -151,6 +161,7 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
                        score_output_root=score_output_root, egress=egress, scorer=scorer, overlay=overlay,
                        tracks=report, tracks_output_root=tracks_output_root,
                        min_region=min_region, fill_holes=fill_holes, region_connectivity=connectivity,
+                       trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -218,7 +229,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                   read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                  tracks=False, tracks_output_root=None, regions=None) -> Dict:
+                  tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -229,7 +240,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode,
-                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root, regions=regions)
+                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         feeds = _feeds([vid_reader], network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
@@ -244,7 +255,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                              read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                             tracks=False, tracks_output_root=None, regions=None) -> Dict:
+                             tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -270,7 +281,7 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay,
-                   tracks=tracks, tracks_output_root=tracks_output_root, regions=regions)
+                   tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -335,7 +346,7 @@ def lockstep_groups(mine, readers, lockstep, mixed=False):
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
                             ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                            mixed_objects=False, tracks=False, tracks_output_root=None, regions=None) -> Dict[int, Dict]:
+                            mixed_objects=False, tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key`` (mixed_objects: ``lockstep_key_mixed``
     -- their object counts may differ); they may differ in length -- the
@@ -349,7 +360,7 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
                      score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay, tracks=tracks,
-                     tracks_output_root=tracks_output_root, regions=regions) for c, rd in enumerate(vid_readers)]
+                     tracks_output_root=tracks_output_root, regions=regions, bands=bands) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -442,6 +453,14 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument('--fill-holes', type=int, default=0, metavar='N',
                     help='fill enclosed background components of fewer than N pixels with the id left of their first pixel, after --min-region '
                          '(so a speck of one object inside another becomes the other).  0 or 1: off.  Not for long-id (RGB) masks')
+    ap.add_argument('--trimap', nargs=2, type=float, metavar=('R_IN', 'R_OUT'),
+                    help='per frame OUT/<video>/trimap/<frame>.png, an 8-bit grey PNG: 255 sure foreground (all objects), 0 sure background, 128 '
+                         'the unknown band of R_IN pixels inside and R_OUT pixels outside the edge; exact Euclidean distances, measured on '
+                         'the GPU on the plane of the written mask (csrc/edt.hip); radii 0 .. 255.  Not for long-id (RGB) masks')
+    ap.add_argument('--trimap-objects', action='store_true', help='with --trimap: one trimap per object as well, OUT/<video>/trimap_objects/<object id>/<frame>.png')
+    ap.add_argument('--dilate-mask', type=float, default=0.0, metavar='R',
+                    help='per frame OUT/<video>/dilated/<frame>.png (0 | 255): all objects dilated by the disk of R pixels (what inpainting and '
+                         'object-removal models take); 0 .. 255.  Not for long-id (RGB) masks')
     ap.add_argument('--region-connectivity', type=int, choices=(4, 8), default=8,
                     help='neighbours that connect the pixels of a component for --min-region and --fill-holes: 4 (edges) or 8 (edges and corners; default)')
     return ap
@@ -485,6 +504,13 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
         ap.error('--min-region and --fill-holes are not negative')
     if max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2 and args.masks is not None and _long_id_masks(args.masks):
         ap.error('--min-region / --fill-holes: long-id datasets (RGB masks) have no uint8 id plane to label')
+    radii = list(getattr(args, 'trimap', None) or ()) + [getattr(args, 'dilate_mask', 0.0)]
+    if not all(0.0 <= r <= 255.0 for r in radii):
+        ap.error('--trimap and --dilate-mask take radii of 0 .. 255 pixels')
+    if getattr(args, 'trimap_objects', False) and max(getattr(args, 'trimap', None) or (0.0,)) <= 0.0:
+        ap.error('--trimap-objects belongs to --trimap')
+    if max(radii) > 0.0 and args.masks is not None and _long_id_masks(args.masks):
+        ap.error('--trimap / --dilate-mask: long-id datasets (RGB masks) have no uint8 id plane to measure on')
     if getattr(args, 'decode_batch', 1) < 1:
         ap.error('--decode-batch is at least 1')
     if args.sizes is not None:
@@ -531,6 +557,9 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
     filtered = max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2
     if filtered:                                              # (off: no argument is passed and no launch is issued)
         common.update(regions=(args.min_region, args.fill_holes, getattr(args, 'region_connectivity', 8)))
+    trimap = tuple(getattr(args, 'trimap', None) or (0.0, 0.0))
+    if max(trimap) > 0.0 or getattr(args, 'dilate_mask', 0.0) > 0.0:      # (off: no argument is passed and no launch is issued)
+        common.update(bands=(trimap, bool(getattr(args, 'trimap_objects', False)), float(getattr(args, 'dilate_mask', 0.0))))
     run = lambda view, c: process_video(view, cfg, readers[c], mask_root, **common)
     if args.sizes is not None:
         # one dataset per scale over the same folders (`readers`, from --size -1, only counts the videos): member s of video c is

@@ -56,7 +56,17 @@ the scorer therefore all see the plane of the file that is written.  What comes 
 alpha matte, the soft vis modes and ``save_scores`` -- and the model never sees the filtered plane: the probabilities ``step`` returns, the
 memory bank and ``last_mask`` are untouched.  The four counts of a frame ride a 16-byte pinned copy with an event behind it; the writer
 thread sums them, and ``end`` leaves the video's totals in ``self.regions``.  With both thresholds below 2 nothing is launched and no
-byte changes."""
+byte changes.
+
+``trimap`` / ``trimap_objects`` / ``dilate_mask`` (not in the reference): what matting and inpainting models take
+next to the frame.  Behind the id plane -- and behind the region filter, so on the plane of the file that is written -- one op list of
+its own (PROB_TO_ID flags == 4096, csrc/edt.hip: the exact squared Euclidean distance of every pixel to the edge of a set of ids, and
+the band byte that is a compare of it) writes one uint8 plane per output: the trimap of the union of the target objects (0 sure
+background | 128 within r_out outside or r_in inside the edge | 255 sure foreground), with ``trimap_objects`` one trimap per object of
+the frame, and the union dilated by the disk of radius ``dilate_mask`` (0 | 255).  Nothing exists outside the frame: an object cut by
+the frame's border is not eroded from there.  The planes go through the PNG stage and leave as 8-bit grey PNGs, like the soft masks:
+``<output_root>/<video>/trimap/<frame>.png``, ``.../trimap_objects/<object id>/<frame>.png``, ``.../dilated/<frame>.png``.  The stage
+reads nothing but the plane, so it runs under both egress modes and in ``process_merged``.  Off: no launch, no file."""
 import logging
 import os
 import shutil
@@ -75,7 +85,7 @@ from ...utils.pano_utils import ID2RGBConverter
 from . import coco_rle
 from . import jpeg_writer
 from . import png as png_container
-from .saver_buffers import RLE_TABLE, EgressBuffers, KeyedCache, MatteBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
+from .saver_buffers import RLE_TABLE, BandBuffers, EgressBuffers, KeyedCache, MatteBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
 
 log = logging.getLogger()
 
@@ -129,11 +139,13 @@ class _Job:
     tracks: Optional[TrackBuffers] = None    # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
     track_meta: Optional[Tuple] = None       # ... (frame index, object ids of the rows, H, W): the frame is reported
     regions: Optional[RegionBuffers] = None  # min_region / fill_holes: the frame's four counts arrive in these
+    bands: Optional[BandBuffers] = None      # trimap / trimap_objects / dilate_mask: the frame's band planes arrive in these
+    band_planes: Tuple = ()                  # ... (folder, object id or None) of every plane, in plane order
 
     def held(self) -> list:
         """the pooled buffer sets of the frame, each once"""
         sets = []
-        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions):
+        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions, self.bands):
             if b is not None and not any(b is s for s in sets):
                 sets.append(b)
         return sets
@@ -143,7 +155,8 @@ class ResultSaver:
     def __init__(self, output_root, video_name, *, dataset, object_manager, use_long_id, palette=None, save_mask=True,
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
-                 target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8):
+                 target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8,
+                 trimap=None, trimap_objects=False, dilate_mask=0.0):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -172,7 +185,31 @@ class ResultSaver:
         fewer than ``min_region`` pixels are dropped from the id plane and enclosed background components of fewer than ``fill_holes``
         pixels are filled, on the device, before anything reads the plane; components are connected under ``region_connectivity`` (4 |
         8).  A threshold below 2 switches its stage off; with both off nothing changes anywhere.  ``end`` leaves the video's totals in
-        ``self.regions`` (None when off).  Needs ``processor``; long ids (RGB masks) have no uint8 plane."""
+        ``self.regions`` (None when off).  Needs ``processor``; long ids (RGB masks) have no uint8 plane.
+        ``trimap`` = (r_in, r_out), ``trimap_objects``, ``dilate_mask`` = r (not in the reference; see the module docstring): radii in
+        pixels, floats, 0 <= r <= 255; (0, 0), None and 0.0 mean off.  The union outputs take the ids of ``target_objects`` (default:
+        all objects of the frame; ids that are not objects of the frame are left out, and a frame without any gets all-zero files);
+        ``trimap_objects`` adds one trimap per object of the frame and needs ``trimap``.  Exact Euclidean distances: a pixel is in the
+        band iff dx^2 + dy^2 <= r^2 to the nearest pixel across the edge.  Needs ``processor``; long ids have no uint8 plane."""
+        def radius(name, r):
+            r = float(r)
+            if not 0.0 <= r <= 255.0:                          # (also refuses nan)
+                raise ValueError(f'{name}: a radius of {r} pixels, 0 .. 255')
+            return r
+        if trimap is not None:
+            if len(tuple(trimap)) != 2:
+                raise ValueError(f'trimap is (r_in, r_out), not {trimap!r}')
+            trimap = tuple(radius('trimap', r) for r in trimap)
+            trimap = trimap if max(trimap) > 0.0 else None
+        dilate_mask = radius('dilate_mask', dilate_mask)
+        if trimap_objects and trimap is None:
+            raise ValueError('trimap_objects: one trimap per object needs trimap=(r_in, r_out)')
+        self.trimap, self.trimap_objects, self.dilate_mask = trimap, bool(trimap_objects), dilate_mask
+        self._bands_on = trimap is not None or dilate_mask > 0.0
+        if self._bands_on and use_long_id:
+            raise ValueError('trimap / dilate_mask: distances are measured on uint8 id planes; a use_long_id saver (RGB masks) cannot write them')
+        if self._bands_on and processor is None:
+            raise ValueError('trimap / dilate_mask need the processor (its device)')
         self.min_region, self.fill_holes, self.region_connectivity = int(min_region), int(fill_holes), int(region_connectivity)
         if self.min_region < 0 or self.fill_holes < 0:
             raise ValueError(f'min_region and fill_holes are not negative ({min_region}, {fill_holes})')
@@ -256,7 +293,8 @@ class ResultSaver:
                                                                jpeg=self.overlay == 'device')),
             matte=Pool(limit, lambda H, W, K: MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev(), self._slab)),
             tracks=Pool(limit, lambda: TrackBuffers(dev())),
-            regions=Pool(limit, lambda: RegionBuffers(dev())))
+            regions=Pool(limit, lambda: RegionBuffers(dev())),
+            bands=Pool(limit, lambda H, W, S: BandBuffers(H, W, S, dev(), self._slab)))
         self.thread = Thread(target=_writer, args=(self.queue,), daemon=True)
         self.thread.start()
 
@@ -366,7 +404,8 @@ class ResultSaver:
         1. ONE op list: the id stage, the region filter -- before anything reads the plane --, with egress='device' the PNG stage
            (fused with the id stage when no filter stands between them) and, on an annotated BURST frame, the RLE stage;
         2. the scorer sees the plane on the device (a pooled plane is not handed out again before the writer is done with the frame);
-        3. the overlay, the copy of the filter's counts, the vis modes / soft masks / matte and the track report, each an op list of
+        3. the overlay, the copy of the filter's counts, the vis modes / soft masks / matte, the track report and the trimaps /
+           dilated mask, each an op list of
            its own behind the plane, each followed by its pinned copies;
         4. the frame's own pinned copies with the event behind every copy, and the job -- which keeps alive what the launches read
            until the writer has released the frame."""
@@ -384,7 +423,7 @@ class ResultSaver:
         elif id_stage is not None:
             ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=self.processor.network.device)
         else:
-            ids = mask.contiguous() if self._regions_on else mask
+            ids = mask.contiguous() if self._regions_on or self._bands_on else mask
         fused = None if self._regions_on else png
         if id_stage is not None:
             id_stage(ol, ids, fused)
@@ -411,6 +450,8 @@ class ResultSaver:
             fields.update(self._queue_matte(planes, out_hw, ids, all_ids, path_to_image, image_u8))
         if self.tracks is not None:
             fields.update(self._queue_tracks(ids, all_ids, confidence, None, frame_index))
+        if self._bands_on:
+            fields.update(self._queue_bands(ids, all_ids))
         if on_device:
             b.png.copy()
             if rle:
@@ -449,6 +490,50 @@ class ResultSaver:
         b = self._pools['regions'].take()
         ol.region_filter(ids, scratch, b.dev, min_region=self.min_region, fill_holes=self.fill_holes, connectivity=self.region_connectivity)
         return b
+
+    # ---- trimap / trimap_objects / dilate_mask ------------------------------------------------------------------------------------
+    def _queue_bands(self, ids, all_ids) -> dict:
+        """Queue the distance stage of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the device)
+        and behind the region filter: one op per threshold pair (the trimaps: the union first, then one set per object, split over ops
+        of at most EDT_MAX_SETS sets; the dilated union), the PNG stage per plane, the pinned copies and one event.  -> the _Job fields.
+        Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        union = tuple(all_ids) if self.target_objects is None else tuple(o for o in self.target_objects if o in all_ids)
+        groups, planes = [], []                  # the trimaps' sets of ids; (folder, object id) of every plane
+        if self.trimap is not None:
+            objects = list(all_ids) if self.trimap_objects else []
+            groups = [union] + [(o,) for o in objects]
+            planes = [('trimap', None)] + [('trimap_objects', o) for o in objects]
+        n = len(groups)
+        if self.dilate_mask > 0.0:
+            planes.append(('dilated', None))
+
+        def table():
+            t = np.zeros((max(n, 1), 256), dtype=np.uint8)
+            for s, group in enumerate(groups or [union]):
+                t[s, list(group)] = 1
+            return torch.from_numpy(t).to(dev)
+        sets = self._tables.get('bands', (union, tuple(all_ids) if n > 1 else None), table)
+        b = self._pools['bands'].take(H, W, len(planes))
+        most = min(max(n, 1), O.OpList.EDT_MAX_SETS)
+        scratch = self._scratch.get('bands', (H, W, most), lambda: torch.empty(O.OpList.edt_scratch_words(most, H, W), dtype=torch.int32, device=dev))
+        ol = O.OpList()
+        if n:
+            inner, outer = (int(r * r) for r in self.trimap)   # floor(r^2): dx^2 + dy^2 is an integer
+            for a in range(0, n, most):
+                ol.edt_band(ids, sets[a:a + most], scratch, band=b.band[a:min(a + most, n)], inner=inner, outer=outer, mid=128)
+        if self.dilate_mask > 0.0:
+            ol.edt_band(ids, sets[:1], scratch, band=b.band[n:n + 1], inner=0, outer=int(self.dilate_mask * self.dilate_mask), mid=255)
+        png_scratch = self._scratch.get('bands png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+        for k, slab in enumerate(b.png):
+            ol.png_deflate(b.band[k], slab.stream, slab.status, png_scratch, H=H, W=W)
+        ol.run()
+        for slab in b.png:
+            slab.copy()
+        b.event.record()
+        return dict(bands=b, band_planes=tuple(planes))
 
     # ---- tracks -----------------------------------------------------------------------------------------------------------------
     def _queue_tracks(self, ids, all_ids, prob, lut_dev, frame_index) -> dict:
@@ -711,6 +796,15 @@ class ResultSaver:
             self._region_totals += job.regions.host.numpy()
             self._region_frames += 1
 
+    def _write_bands(self, job):
+        """trimap / trimap_objects / dilate_mask: the frame's planes as 8-bit grey PNGs"""
+        b = job.bands
+        if b is None:
+            return
+        for (folder, oid), slab in zip(job.band_planes, b.png):
+            data = png_container.assemble(slab.fetch(b.event), b.H, b.W, None)
+            self._put(self.output_root, folder if oid is None else path.join(folder, str(oid)), job.frame_name[:-4] + '.png', data)
+
     def _write_overlay(self, job, rgb_mask):
         """``<frame>.jpg`` of ``visualize``: the device's segment wrapped (overlay='device'; no PIL), else the host's blend through PIL
         -- also for a frame whose segment did not fit the device stream."""
@@ -763,6 +857,7 @@ def _writer(queue: Queue):
             s._write_matte(job)
             s._write_tracks(job)
             s._write_regions(job)
+            s._write_bands(job)
             s._write_overlay(job, rgb_mask)
         except Exception as e:                                 # keep the queue draining; surface the problem
             log.error(f'result writer failed on {job.frame_name}: {e}')

@@ -1,5 +1,5 @@
 """What a ``ResultSaver`` (results_utils.py) keeps per frame in flight and per geometry: the ``[status | stream]`` slab with its pinned
-head and its reader, the four buffer sets, the pool that recycles them between the stepping thread and the writer thread, and the keyed
+head and its reader, the five buffer sets, the pool that recycles them between the stepping thread and the writer thread, and the keyed
 cache of the scratch tensors and the small device tables."""
 from queue import Empty, Queue
 
@@ -149,6 +149,17 @@ class RegionBuffers(_Buffers):
         super().__init__(device)
         self.dev = torch.empty(4, dtype=torch.int32, device=device)
         self.host = self.twin(self.dev)
+
+
+class BandBuffers(_Buffers):
+    """What one frame in flight owns of the trimaps and dilated masks: the S band planes of the distance stage, per plane the slab of its
+    zlib stream, and the event behind their copies."""
+
+    def __init__(self, H, W, S, device, slab):
+        super().__init__(device)
+        self.H, self.W, self.S = H, W, S
+        self.band = torch.empty((S, H, W), dtype=torch.uint8, device=device)
+        self.png = [slab('png', H, W) for _ in range(S)]
 
 
 class Pool:

@@ -1123,6 +1123,54 @@ class OpList:
         return self.add(PROB_TO_ID, 2048, [0, H, W, min_region, fill_holes, connectivity, 0, 0, words & 0x7fffffff, words >> 31], [],
                         [None, None, ids_plane, None, None, scratch, None, counts])
 
+    EDT_MAX_LIMIT = 65536     # CUTIE_EDT_MAX_LIMIT (include/cutie_hip.h): distances are exact below it; radii up to 255
+    EDT_MAX_SETS = 16         # CUTIE_EDT_MAX_SETS
+    EDT_COL_GROUP = 64        # columns per block of the column pass (csrc/edt.hip EDT_CW)
+    EDT_ROW_CHUNK = 32        # least rows per thread of the column pass (EDT_CH; max(EDT_CH, ceil(sqrt(limit))) rows)
+    EDT_ROW_SEGMENT = 256     # pixels per block of the row pass (EDT_T)
+
+    @staticmethod
+    def edt_scratch_words(S, H, W):
+        """int32 words of the scratch of edt_band: one uint16 per set and pixel."""
+        return (S * H * W + 1) // 2
+
+    def edt_band(self, ids_plane, sets, scratch, *, band=None, dist2=None, inner=0, outer=0, mid=128, limit=None):
+        """PROB_TO_ID flags == 4096 (ABI 11, form added; include/cutie_hip.h): ids_plane uint8 [H, W] (contiguous, any alignment, read
+        only) and ``sets`` uint8 [S, 256] on the device (id v is in set s iff sets[s, v] != 0) -> per set the exact squared Euclidean
+        distance of every pixel to the nearest pixel of the other class inside the frame, D = min(d2, limit) (``dist2`` int32 [S, H, W])
+        and the band byte (``band`` uint8 [S, H, W]): inside the set 255 where D > ``inner`` else ``mid``, outside it ``mid`` where D <=
+        ``outer`` else 0.  Either output may be None, not both.  ``limit`` defaults to max(inner, outer) + 1.  ``scratch``: int32, at
+        least ``edt_scratch_words(S, H, W)`` words."""
+        _need_form(_lib.has_edt_band, 'no distance transform, PROB_TO_ID flags == 4096')
+        H, W = _u8_plane('edt_band', 'ids_plane', ids_plane)
+        if sets.dtype != torch.uint8 or sets.dim() != 2 or sets.shape[1] != 256 or not sets.is_contiguous():
+            raise ValueError(f'edt_band: sets is a contiguous uint8 [S, 256], not {sets.dtype} {tuple(sets.shape)}')
+        S = int(sets.shape[0])
+        if not 1 <= S <= self.EDT_MAX_SETS:
+            raise ValueError(f'edt_band: {S} sets, 1 .. {self.EDT_MAX_SETS} (split more over several ops)')
+        inner, outer, mid = int(inner), int(outer), int(mid)
+        limit = max(inner, outer) + 1 if limit is None else int(limit)
+        if inner < 0 or outer < 0:
+            raise ValueError(f'edt_band: inner {inner} and outer {outer} are not negative')
+        if not max(inner, outer) < limit <= self.EDT_MAX_LIMIT:
+            raise ValueError(f'edt_band: limit {limit}: max(inner, outer) = {max(inner, outer)} < limit <= {self.EDT_MAX_LIMIT}')
+        if not 0 <= mid <= 255:
+            raise ValueError(f'edt_band: mid {mid} is a byte')
+        if band is None and dist2 is None:
+            raise ValueError('edt_band: band, dist2 or both')
+        for name, t, dtype in (('band', band, torch.uint8), ('dist2', dist2, torch.int32)):
+            if t is not None and (t.dtype != dtype or tuple(t.shape) != (S, H, W) or not t.is_contiguous()):
+                raise ValueError(f'edt_band: {name} is a contiguous {dtype} [{S}, {H}, {W}], not {t.dtype} {tuple(t.shape)}')
+        need = self.edt_scratch_words(S, H, W)
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < need:
+            raise ValueError(f'edt_band: scratch is a contiguous int32 of at least {need} words')
+        for name, t in (('sets', sets), ('scratch', scratch), ('band', band), ('dist2', dist2)):
+            if t is not None and t.device != ids_plane.device:
+                raise ValueError(f'edt_band: {name} is on {t.device}, ids_plane on {ids_plane.device}')
+        words = int(scratch.numel())
+        return self.add(PROB_TO_ID, 4096, [0, H, W, inner, outer, limit, mid, words >> 31, words & 0x7fffffff, S], [],
+                        [None, None, ids_plane, band, None, scratch, sets, dist2])
+
     JPEG_ENC_BLOCK_WORDS = 52     # JPG_BLOCK_WORDS (csrc/jpeg_enc.hip): a coded block is at most 22 + 63 * 26 = 1660 bits
 
     @staticmethod

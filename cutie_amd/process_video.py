@@ -17,6 +17,7 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
         [--vis MODE [MODE ...]] [--soft-masks] [--alpha] [--target-objects ID [ID ...]] [--layer FILE]
+        [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
         [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
                             has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
 
@@ -26,6 +27,12 @@ the GPU (ResultSaver vis_modes / soft_masks / alpha_matte) into OUT/visualizatio
 OUT/alpha/*.png.  ``--target-objects``: the objects that popup, layer and the matte keep (default all); ``--layer``: the RGBA image of
 mode layer.  The uint8 frame the modes read is the one device ingest uploaded or decoded; with ``--ingest host`` it is made from the
 float frame on the device, once per frame.
+
+``--trimap R_IN R_OUT``, ``--trimap-objects``, ``--dilate-mask R``: what matting and inpainting models take next to the frame, as 8-bit
+grey PNGs: OUT/trimap/*.png (255 sure foreground, 0 sure background, 128 the band of R_IN pixels inside and R_OUT pixels outside the edge
+of the ``--target-objects``), one trimap per object in OUT/trimap_objects/<object id>/*.png, and the target objects dilated by the disk of
+R pixels in OUT/dilated/*.png (0 | 255).  Exact Euclidean distances, measured on the GPU on the plane of the mask that is written
+(ResultSaver trimap / trimap_objects / dilate_mask, csrc/edt.hip).
 
 ``--ingest device``: frames are read as uint8 and uploaded as such; ToTensor runs on the GPU (one RESIZE launch with flags 4,
 cutie_amd/inference/data/device_ingest.py).  ``--ingest device-decode``: JPEG frames of a directory are parsed on the host and
@@ -153,7 +160,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
-                  region_connectivity: int = 8) -> Dict:
+                  region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
@@ -162,7 +169,9 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     device (inference/utils/track_report.py): output_dir/tracks/tracks.json and tracks_mot.txt, and 'tracks' (the json's content) in the result.
     min_region / fill_holes / region_connectivity: ResultSaver's region filter -- small object components are dropped from every mask and
     small enclosed holes filled, on the device, before the mask is written, composed, tracked or scored; 'regions' (the totals) joins the
-    result.  The model never sees the filtered plane."""
+    result.  The model never sees the filtered plane.
+    trimap = (r_in, r_out) / trimap_objects / dilate_mask = r: ResultSaver's -- output_dir/trimap/*.png (0 | 128 | 255) of the target objects
+    (default all), one per object in trimap_objects/<id>/, and the target objects dilated by the disk of r pixels in dilated/*.png."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -248,7 +257,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             palette=palette, processor=processor, egress=egress, scorer=scorer, vis_modes=vis_modes, soft_masks=soft_masks,
                             alpha_matte=alpha_matte, target_objects=target_objects, layer=layer,
                             tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None,
-                            min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity)
+                            min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity,
+                            trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask)
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -312,6 +322,11 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--fill-holes', type=int, default=0, metavar='N',
                     help='then fill enclosed background components of fewer than N pixels with the id left of their first pixel (0, 1: off)')
     ap.add_argument('--region-connectivity', type=int, choices=(4, 8), default=8, help='neighbours that connect a component: 4 or 8 (default)')
+    ap.add_argument('--trimap', nargs=2, type=float, metavar=('R_IN', 'R_OUT'),
+                    help='OUT/trimap/*.png (0 | 128 | 255): the band of R_IN pixels inside and R_OUT pixels outside the edge of the --target-objects '
+                         '(default all) is unknown; exact Euclidean distances, measured on the GPU; radii 0 .. 255')
+    ap.add_argument('--trimap-objects', action='store_true', help='with --trimap: one trimap per object as well, OUT/trimap_objects/<object id>/*.png')
+    ap.add_argument('--dilate-mask', type=float, default=0.0, metavar='R', help='OUT/dilated/*.png (0 | 255): the --target-objects (default all) dilated by the disk of R pixels; 0 .. 255')
     return ap
 
 
@@ -336,7 +351,7 @@ def main():
                       mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
                       decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
-                      region_connectivity=args.region_connectivity)
+                      region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

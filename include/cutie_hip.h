@@ -28,6 +28,8 @@ extern "C" {
 #define CUTIE_OP_NF 6
 #define CUTIE_OP_NP 16
 #define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
+#define CUTIE_EDT_MAX_LIMIT 65536   /* PROB_TO_ID flags == 4096 (ABI 11, form added): distances are exact below it; radii up to 255 (255^2 = 65025) */
+#define CUTIE_EDT_MAX_SETS 16       /* ... sets of ids per op; the host splits more over several ops */
 #define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
 
 /* Mixed forms (added without a new ABI number: cutie_hip_build_flags() bit 3, value 8, says they are present -- a library from before
@@ -537,7 +539,33 @@ enum {
      *    whatever the arrival order -- which also makes the fill pixel root - 1; areas and counts are integer sums.  The plane and
      *    counts after the launch depend on the plane before it and on i3 .. i5 alone.
      *    The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, a negative threshold, a
-     *    connectivity other than 4 or 8, a null p2, p5 or p7, p5 or p7 not 4-byte aligned, fewer scratch words than 2 * H * W. */
+     *    connectivity other than 4 or 8, a null p2, p5 or p7, p5 or p7 not 4-byte aligned, fewer scratch words than 2 * H * W.
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 6, value 64, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- the exact squared Euclidean distance transform and its bands (not in the
+     *    reference; ResultSaver trimap= / trimap_objects= / dilate_mask=, eval_vos / process_video --trimap / --trimap-objects /
+     *    --dilate-mask):
+     *  flags == 4096, a stage ON ITS OWN (4096 combined with any other flag stays the "unknown flags" error): for each of S sets of ids,
+     *    how far every pixel of an existing uint8 id plane p2 = [i1, i2] = [H, W] (row-major and contiguous, any alignment, READ ONLY)
+     *    is from the set's edge (kernels in edt.hip; the numpy model: tests/edt_ref.py).  i0, p0, p1, p4 and the floats are unused.
+     *    p6 = sets uint8 [S][256], i9 = S, 1 <= S <= CUTIE_EDT_MAX_SETS: id v belongs to set s iff sets[s][v] != 0; an id may be in
+     *    several sets or in none.  F_s = the pixels whose id is in set s.
+     *    i3 = inner >= 0, i4 = outer >= 0, i5 = limit with max(inner, outer) < limit <= CUTIE_EDT_MAX_LIMIT, i6 = mid, a byte.
+     *    Per set: d2(p) = the smallest dx^2 + dy^2, an integer, from p to a pixel of the OTHER class inside the frame -- a pixel of F
+     *    looks for one outside F and the reverse.  NOTHING EXISTS OUTSIDE THE FRAME: an object cut by the frame's border is not
+     *    eroded from there (the object goes on beyond the picture; scipy's binary_erosion border_value=1).  D(p) = min(d2(p), limit),
+     *    and D = limit everywhere when the frame holds no pixel of the other class.  D >= 1.
+     *    p7 = dist2 int32 [S, H, W], 4-byte aligned, or null: D(p); any value below limit is the exact d2.
+     *    p3 = band uint8 [S, H, W], any alignment, or null: for p in F 255 if D > inner, else mid; for p outside F mid if D <= outer,
+     *    else 0.  (Trimap: mid = 128, inner = floor(r_in^2), outer = floor(r_out^2); dilation by the disk dx^2 + dy^2 <= r^2: inner =
+     *    0, mid = 255, outer = floor(r^2); erosion: outer = 0, mid = 0.  inner = 0 erodes nothing, outer = 0 dilates nothing.)
+     *    Not both null.
+     *    p5 = scratch int32, 4-byte aligned, of i8 + 2^31 * i7 words (i7, i8 >= 0): at least ceil(S * H * W / 2)
+     *    (OpList.edt_scratch_words).  Its content before and after the launch means nothing.
+     *    Determinism: integers only, no atomics, every word written once by one thread and read behind a kernel boundary: the outputs
+     *    depend on the plane, the sets and i3 .. i6 alone.
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, S outside 1 ..
+     *    CUTIE_EDT_MAX_SETS, a negative inner or outer, a limit outside max(inner, outer) + 1 .. CUTIE_EDT_MAX_LIMIT, mid outside 0 ..
+     *    255, a null p2, p6 or p5, p3 and p7 both null, p5 or p7 not 4-byte aligned, fewer scratch words than needed. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -676,7 +704,7 @@ int cutie_op_struct_size(void);
  * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
  * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present.
  * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
- * filter, is present. */
+ * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

@@ -101,6 +101,12 @@ def has_edt_band():
     return bool(load().cutie_hip_build_flags() & 64)
 
 
+def has_polygons():
+    """Does the loaded library know PROB_TO_ID flags == 8192, the polygon trace of an id plane?  Added without a new ABI number; a library
+    from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing (OpList.polygon_trace)."""
+    return bool(load().cutie_hip_build_flags() & 128)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

@@ -131,4 +131,5 @@ int launch_matte_soft(const cutie_op* op, hipStream_t s);                  // ma
 int launch_track_stats(const cutie_op* op, hipStream_t s);                 // tracks.hip: PROB_TO_ID with flags == 1024 (ABI 11, form added)
 int launch_region_filter(const cutie_op* op, hipStream_t s);               // regions.hip: PROB_TO_ID with flags == 2048 (ABI 11, form added)
 int launch_edt_band(const cutie_op* op, hipStream_t s);                    // edt.hip: PROB_TO_ID with flags == 4096 (ABI 11, form added)
+int launch_polygon_trace(const cutie_op* op, hipStream_t s);               // polygons.hip: PROB_TO_ID with flags == 8192 (ABI 11, form added)
 void cutie_set_error(const char* fmt, ...);

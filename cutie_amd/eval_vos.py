@@ -31,6 +31,9 @@ member cores -- the whole of the first two drivers and the tail of a lock-step g
         [--tracks]                         (one row per object and saved frame -- area, box, centroid, confidence -- counted on the GPU from the id
                                             plane and the probabilities (inference/utils/track_report.py): OUT/tracks/<video>/tracks.json and
                                             tracks_mot.txt; with --sizes the confidence is null; not for long-id (RGB) masks)
+        [--polygons]                       (every object of every saved frame as exact rings of lattice corners, traced on the GPU on the plane of
+                                            the written mask (csrc/polygons.hip, inference/utils/polygons.py): OUT/polygons/<video>/polygons.json;
+                                            --region-connectivity 8 joins diagonal pixels into one ring; not for long-id (RGB) masks)
 
 BURST (a --dataset name containing "burst", e.g. burst-val | burst-test; eval_vos.py:42-54,108,156-157,171-172 of the reference):
     python -m cutie_amd.eval_vos --dataset burst-val --images DIR/frames/val --json DIR/val/first_frame_annotations.json --output OUT
@@ -58,6 +61,7 @@ from .inference.inference_core import InferenceCore
 from .inference.utils.burst_utils import BURSTResultHandler
 from .inference.utils.davis_metrics import SequenceScorer, global_line, write_results
 from .inference.utils.results_utils import EGRESS_MODES, OVERLAY_MODES, ResultSaver, make_zip
+from .inference.utils.polygons import PolygonReport
 from .inference.utils.track_report import TrackReport
 
 log = logging.getLogger()
@@ -134,11 +138,17 @@ def _take(windows, dev, lookahead):
 
 def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_output_root, egress, save_scores=False,
            score_output_root=None, score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', tracks=False,
-           tracks_output_root=None, regions=None, bands=None) -> ResultSaver:
+           tracks_output_root=None, regions=None, bands=None, polygons=False, polygons_output_root=None) -> ResultSaver:
     """score_gt: the ground-truth root of a scored run (--score): the saver gets the video's SequenceScorer.
     tracks (--tracks): the saver gets the video's own TrackReport and writes it into tracks_output_root/<video>/ when it ends.
     regions (--min-region / --fill-holes / --region-connectivity): (min_region, fill_holes, connectivity) of the saver's region filter.
-    bands (--trimap / --trimap-objects / --dilate-mask): (trimap, trimap_objects, dilate_mask) of the saver, over all objects."""
+    bands (--trimap / --trimap-objects / --dilate-mask): (trimap, trimap_objects, dilate_mask) of the saver, over all objects.
+    polygons (--polygons): the saver gets the video's own PolygonReport and writes it into polygons_output_root/<video>/ when it ends."""
+    outlines = None
+    if polygons:
+        if vid_reader.use_long_id:
+            raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no polygons')
+        outlines = PolygonReport(vid_reader.vid_name)
     trimap, trimap_objects, dilate_mask = bands if bands is not None else (None, False, 0.0)
     if bands is not None and vid_reader.use_long_id:
         raise ValueError(f'{vid_reader.vid_name}: long ids (RGB masks) have no uint8 id plane: no trimap, no dilated mask')
@@ -162,6 +172,7 @@ def _saver(core, vid_reader, mask_output_root, *, dataset, visualize, visualize_
                        tracks=report, tracks_output_root=tracks_output_root,
                        min_region=min_region, fill_holes=fill_holes, region_connectivity=connectivity,
                        trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
+                       polygons=outlines, polygons_output_root=polygons_output_root,
                        init_json=vid_reader.sequence_json if is_burst(dataset) else None)       # (eval_vos.py:108)
 
 
@@ -178,6 +189,8 @@ def _with_json(stats, saver):
         stats['scores'] = saver.scores
     if saver.tracks is not None:                 # --tracks: the video's report (what tracks.json holds), so that sharded ranks can gather them
         stats['tracks'] = saver.tracks.as_dict()
+    if saver.polygons is not None:               # --polygons: the video's report (what polygons.json holds)
+        stats['polygons'] = saver.polygons.as_dict()
     if saver.regions is not None:                # --min-region / --fill-holes: what the filter changed in the video
         stats['regions'] = saver.regions
     return stats
@@ -193,7 +206,7 @@ def _frame_kw(saver, info) -> Dict:
     """overlay='device': the frame's uint8 original on the device, when the ingest kept it (``_feeds(keep_u8s=...)``).
     tracks: the frame's 1-based position in the video as the reader orders it."""
     kw = {'image_u8': info.get('image_u8')} if saver.overlay == 'device' else {}
-    if saver.tracks is not None and info.get('time_index') is not None:
+    if (saver.tracks is not None or saver.polygons is not None) and info.get('time_index') is not None:
         kw['frame_index'] = int(info['time_index']) + 1
     return kw
 
@@ -229,7 +242,7 @@ def _run_video(members, feeds, n, start, stats, save, *, dev, lookahead):
 def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                   visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                   read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                  tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict:
+                  tracks=False, tracks_output_root=None, regions=None, bands=None, polygons=False, polygons_output_root=None) -> Dict:
     """One video through a fresh InferenceCore (eval_vos.py:97-151).  Returns {'frames', 'seconds'} (time around step).
     ingest: 'host' | 'device' | 'device-decode' (VideoReader(ingest=...); default: the reader's own mode).
     egress: 'host' | 'device' (``ResultSaver``'s ``egress``: the GPU writes the masks' PNG streams).
@@ -240,7 +253,8 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
     processor = InferenceCore(network, cfg=cfg)
     saver = _saver(processor, vid_reader, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode,
-                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands)
+                   overlay=overlay, tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands,
+                   polygons=polygons, polygons_output_root=polygons_output_root)
     stats = {'frames': 0, 'seconds': 0.0}
     try:
         feeds = _feeds([vid_reader], network.device, (IC.WINDOW + IC.WINDOW_LEAD + 1) if lookahead else 1, read_workers, ingest,
@@ -255,7 +269,7 @@ def process_video(network, cfg, vid_reader, mask_output_root, *, dataset='generi
 def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                              visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None,
                              read_workers=4, ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                             tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict:
+                             tracks=False, tracks_output_root=None, regions=None, bands=None, polygons=False, polygons_output_root=None) -> Dict:
     """Multi-scale testing of ONE video in one pass (the reference: one eval_vos run per size with save_scores, then
     scripts/merge_multi_scale.py over the score dumps).  ``vid_readers``: S readers of the SAME video from S ``VOSTestDataset(size=s)``.
     One InferenceCore per member on the one network, stepped one after another per frame -- each with its own look-ahead window, memory
@@ -281,7 +295,8 @@ def process_video_multiscale(network, cfg, vid_readers, mask_output_root, *, dat
     members = ClipCores(network, cfg, S)
     saver = _saver(members.cores[0], rd0, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                    egress=egress, score_gt=score_gt, score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay,
-                   tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands)
+                   tracks=tracks, tracks_output_root=tracks_output_root, regions=regions, bands=bands,
+                   polygons=polygons, polygons_output_root=polygons_output_root)
 
     def save(probs, info, last_frame):
         if save_all or info['save']:
@@ -346,7 +361,8 @@ def lockstep_groups(mine, readers, lockstep, mixed=False):
 def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, dataset='generic', save_all=True, visualize=False,
                             visualize_output_root=None, lookahead=True, save_scores=False, score_output_root=None, read_workers=4,
                             ingest=None, egress='host', score_gt=None, score_all_frames=False, overlay='host', gt_decode='host', decode_batch=1,
-                            mixed_objects=False, tracks=False, tracks_output_root=None, regions=None, bands=None) -> Dict[int, Dict]:
+                            mixed_objects=False, tracks=False, tracks_output_root=None, regions=None, bands=None, polygons=False,
+                            polygons_output_root=None) -> Dict[int, Dict]:
     """``process_video`` for a GROUP of videos advanced in lock step (``LockstepCores``: one launch plan per stage for the objects of all
     videos; per video the results of its own ``InferenceCore``).  The videos should share ``lockstep_key`` (mixed_objects: ``lockstep_key_mixed``
     -- their object counts may differ); they may differ in length -- the
@@ -360,7 +376,8 @@ def process_videos_lockstep(network, cfg, vid_readers, mask_output_root, *, data
     savers = [_saver(ls.cores[c], rd, mask_output_root, dataset=dataset, visualize=visualize, visualize_output_root=visualize_output_root,
                      egress=egress, save_scores=save_scores, score_output_root=score_output_root, score_gt=score_gt,
                      score_all_frames=score_all_frames, gt_decode=gt_decode, overlay=overlay, tracks=tracks,
-                     tracks_output_root=tracks_output_root, regions=regions, bands=bands) for c, rd in enumerate(vid_readers)]
+                     tracks_output_root=tracks_output_root, regions=regions, bands=bands, polygons=polygons,
+                     polygons_output_root=polygons_output_root) for c, rd in enumerate(vid_readers)]
     lens = [len(rd) for rd in vid_readers]
     T = min(lens)
     stats = {c: {'frames': 0, 'seconds': 0.0} for c in range(C)}
@@ -447,6 +464,10 @@ def arg_parser() -> argparse.ArgumentParser:
                     help='per video OUT/tracks/<video>/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every '
                          'saved frame, counted on the GPU (cutie_amd/inference/utils/track_report.py).  With --sizes the confidence is null.  '
                          'Not for long-id (RGB) masks')
+    ap.add_argument('--polygons', action='store_true',
+                    help='per video OUT/polygons/<video>/polygons.json: every object of every saved frame as exact rings of lattice corners '
+                         '(outer rings and holes), traced on the GPU on the plane of the written mask (csrc/polygons.hip; '
+                         'cutie_amd/inference/utils/polygons.py); diagonal pixels join under --region-connectivity 8.  Not for long-id (RGB) masks')
     ap.add_argument('--min-region', type=int, default=0, metavar='N',
                     help='drop object components of fewer than N pixels from every result mask (on the GPU, before the mask is written, encoded, '
                          'overlaid, tracked or scored; csrc/regions.hip).  0 or 1: off.  Not for long-id (RGB) masks')
@@ -500,6 +521,8 @@ def check_args(ap: argparse.ArgumentParser, args) -> None:
         ap.error('--gt and --score-all-frames belong to --score')
     if getattr(args, 'tracks', False) and args.masks is not None and _long_id_masks(args.masks):
         ap.error('--tracks: long-id datasets (RGB masks) have no uint8 id plane to count on')
+    if getattr(args, 'polygons', False) and args.masks is not None and _long_id_masks(args.masks):
+        ap.error('--polygons: long-id datasets (RGB masks) have no uint8 id plane to trace')
     if getattr(args, 'min_region', 0) < 0 or getattr(args, 'fill_holes', 0) < 0:
         ap.error('--min-region and --fill-holes are not negative')
     if max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2 and args.masks is not None and _long_id_masks(args.masks):
@@ -554,6 +577,9 @@ def run_dataset(net, cfg, args, rank=0, world=1) -> Dict[int, Dict]:
         common.update(score_gt=args.gt or args.masks, score_all_frames=bool(args.score_all_frames), gt_decode=args.gt_decode)
     if getattr(args, 'tracks', False):                        # (off: no argument is passed and no launch is issued)
         common.update(tracks=True, tracks_output_root=path.join(args.output, 'tracks'))
+    if getattr(args, 'polygons', False):                      # (off: no argument is passed and no launch is issued)
+        common.update(polygons=True, polygons_output_root=path.join(args.output, 'polygons'),
+                      regions=(0, 0, getattr(args, 'region_connectivity', 8)))             # (the connectivity of the rings; thresholds 0: no filter)
     filtered = max(getattr(args, 'min_region', 0), getattr(args, 'fill_holes', 0)) >= 2
     if filtered:                                              # (off: no argument is passed and no launch is issued)
         common.update(regions=(args.min_region, args.fill_holes, getattr(args, 'region_connectivity', 8)))

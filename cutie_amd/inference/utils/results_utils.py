@@ -85,7 +85,8 @@ from ...utils.pano_utils import ID2RGBConverter
 from . import coco_rle
 from . import jpeg_writer
 from . import png as png_container
-from .saver_buffers import RLE_TABLE, BandBuffers, EgressBuffers, KeyedCache, MatteBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
+from .polygons import trace_rings
+from .saver_buffers import POLY_TABLE, RLE_TABLE, BandBuffers, EgressBuffers, KeyedCache, MatteBuffers, PolygonBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
 
 log = logging.getLogger()
 
@@ -113,6 +114,15 @@ EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame:
 OVERLAY_MODES = ('host', 'device')
 JPEG_SLAB = 256 * 1024      # overlay='device': bytes of the first device-to-host copy of a frame's JPEG: status + the head of the stream (a 480p overlay is 30-120 KB)
 RLE_SLAB = 256 * 1024       # BURST: bytes of the whole device-to-host copy: status, table (RLE_TABLE) and the strings (a frame that needs more is encoded on the host)
+# polygons: the stage's edge capacity and the bytes of its stream.  The worst case of a plane is 32 bytes per lattice vertex (13 MB at 480p)
+# per buffer in flight; outlines of video objects are far from it: a boundary edge costs at most one vertex of 4 bytes and a ring of 16 bytes
+# has at least 4 edges, so 4 bytes per edge hold every frame whose edges fit (a staircase: every edge a corner) unless it also has many
+# rings.  65536 edges are 16 times the 4096 of the stage's one-workgroup path; the bike example's frames (speckled masks of random weights) have 300 .. 3450 edges and
+# streams of 0.9 .. 8.5 KB, 5 % and 3 % of the bounds.  A frame beyond either bound is traced on the host (warned once).  POLY_HEAD: the pinned head
+# copied every frame -- status, table and the first 12 KB of the stream; the writer thread fetches the rest of a longer one.
+POLY_EDGES = 65536
+POLY_STREAM = 4 * POLY_EDGES
+POLY_HEAD = 16 + POLY_TABLE + 12 * 1024
 VIS_MODES = ('davis', 'light', 'fade', 'popup', 'layer')     # gui/interactive_utils.py get_visualization_torch ('mask', 'image': trivial; 'rgba': alpha_matte)
 
 
@@ -139,13 +149,15 @@ class _Job:
     tracks: Optional[TrackBuffers] = None    # tracks: the frame's table arrives in these (None with track_meta: a frame without objects)
     track_meta: Optional[Tuple] = None       # ... (frame index, object ids of the rows, H, W): the frame is reported
     regions: Optional[RegionBuffers] = None  # min_region / fill_holes: the frame's four counts arrive in these
+    polygons: Optional[PolygonBuffers] = None  # polygons: the frame's table, rings and vertices arrive in these (None with poly_meta: a frame without objects)
+    poly_meta: Optional[Tuple] = None        # ... (frame index, object ids of the table's rows, H, W): the frame is reported
     bands: Optional[BandBuffers] = None      # trimap / trimap_objects / dilate_mask: the frame's band planes arrive in these
     band_planes: Tuple = ()                  # ... (folder, object id or None) of every plane, in plane order
 
     def held(self) -> list:
         """the pooled buffer sets of the frame, each once"""
         sets = []
-        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions, self.bands):
+        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions, self.bands, self.polygons):
             if b is not None and not any(b is s for s in sets):
                 sets.append(b)
         return sets
@@ -156,7 +168,7 @@ class ResultSaver:
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
                  target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8,
-                 trimap=None, trimap_objects=False, dilate_mask=0.0):
+                 trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -190,7 +202,25 @@ class ResultSaver:
         pixels, floats, 0 <= r <= 255; (0, 0), None and 0.0 mean off.  The union outputs take the ids of ``target_objects`` (default:
         all objects of the frame; ids that are not objects of the frame are left out, and a frame without any gets all-zero files);
         ``trimap_objects`` adds one trimap per object of the frame and needs ``trimap``.  Exact Euclidean distances: a pixel is in the
-        band iff dx^2 + dy^2 <= r^2 to the nearest pixel across the edge.  Needs ``processor``; long ids have no uint8 plane."""
+        band iff dx^2 + dy^2 <= r^2 to the nearest pixel across the edge.  Needs ``processor``; long ids have no uint8 plane.
+        ``polygons`` (not in the reference; a utils/polygons.py PolygonReport): every object's outline on every frame
+        is traced on the device into exact rings of lattice corners (PROB_TO_ID flags == 8192), on the plane the PNG is written from --
+        behind the region filter, connected under ``region_connectivity`` -- and reported to it; ``end`` writes
+        ``polygons_output_root``/<video>/polygons.json (default root: <output_root>/polygons).  A frame beyond the stage's bounded
+        capacities is traced on the host (one warning).  Needs ``processor``; long ids have no uint8 plane."""
+        if polygons is not None and use_long_id:
+            raise ValueError('polygons: outlines are traced on uint8 id planes; a use_long_id saver (RGB masks) cannot report them')
+        if polygons is not None and processor is None:
+            raise ValueError('polygons needs the processor (its device)')
+        if polygons is not None and int(region_connectivity) not in (4, 8):
+            raise ValueError(f'region_connectivity is 4 or 8, not {region_connectivity}')
+        self.polygons = polygons
+        self.polygons_output_root = polygons_output_root if polygons_output_root is not None else path.join(output_root, 'polygons')
+        self._polygon_count = 0
+        if polygons is not None:
+            polygons.connectivity = int(region_connectivity)
+            if not polygons.video:
+                polygons.video = video_name
         def radius(name, r):
             r = float(r)
             if not 0.0 <= r <= 255.0:                          # (also refuses nan)
@@ -271,7 +301,7 @@ class ResultSaver:
             self.video_json = {k: v for k, v in init_json.items() if k != 'segmentations'}
             self.video_json['segmentations'] = self.segmentations
             self.json_style = 'burst'
-        self._rle_warned = self._jpeg_warned = False
+        self._rle_warned = self._jpeg_warned = self._polygons_warned = False
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
@@ -294,6 +324,7 @@ class ResultSaver:
             matte=Pool(limit, lambda H, W, K: MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev(), self._slab)),
             tracks=Pool(limit, lambda: TrackBuffers(dev())),
             regions=Pool(limit, lambda: RegionBuffers(dev())),
+            polygons=Pool(limit, lambda H, W: PolygonBuffers(H, W, dev(), self._slab)),
             bands=Pool(limit, lambda H, W, S: BandBuffers(H, W, S, dev(), self._slab)))
         self.thread = Thread(target=_writer, args=(self.queue,), daemon=True)
         self.thread.start()
@@ -305,6 +336,14 @@ class ResultSaver:
         dev = self.processor.network.device
         if kind == 'png':
             return Slab(O.OpList.png_capacity(H, W), EGRESS_SLAB, dev, self._copies)
+        if kind == 'polygons':
+            def beyond(length, capacity):
+                if not self._polygons_warned:
+                    self._polygons_warned = True
+                    log.warning(f'polygon trace: a frame of {self.video_name} is beyond the stage\'s capacities ({POLY_EDGES} boundary edges, a stream '
+                                f'of {capacity} bytes; it needs {length} bytes); such frames are traced on the host')
+            return Slab(min(POLY_STREAM, O.OpList.polygon_capacity(H, W)[0]), POLY_HEAD, dev, self._copies, what='polygon', error_word=1,
+                        fixed=POLY_TABLE, overflow=beyond)
         flag = f'_{kind}_warned'
 
         def overflow(length, capacity):
@@ -423,7 +462,7 @@ class ResultSaver:
         elif id_stage is not None:
             ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=self.processor.network.device)
         else:
-            ids = mask.contiguous() if self._regions_on or self._bands_on else mask
+            ids = mask.contiguous() if self._regions_on or self._bands_on or self.polygons is not None else mask
         fused = None if self._regions_on else png
         if id_stage is not None:
             id_stage(ol, ids, fused)
@@ -452,6 +491,8 @@ class ResultSaver:
             fields.update(self._queue_tracks(ids, all_ids, confidence, None, frame_index))
         if self._bands_on:
             fields.update(self._queue_bands(ids, all_ids))
+        if self.polygons is not None:
+            fields.update(self._queue_polygons(ids, all_ids, frame_index))
         if on_device:
             b.png.copy()
             if rle:
@@ -562,6 +603,31 @@ class ResultSaver:
         b.host[:words].copy_(b.dev[:words], non_blocking=True)
         b.event.record()
         return dict(tracks=b, track_meta=meta)
+
+    # ---- polygons ---------------------------------------------------------------------------------------------------------------
+    def _queue_polygons(self, ids, all_ids, frame_index) -> dict:
+        """Queue the polygon trace of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the device)
+        and behind the region filter, the pinned copy of the slab's head and an event.  -> the _Job fields.  Nothing waits here."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(ids.shape[0]), int(ids.shape[1])
+        self._polygon_count += 1
+        meta = (self._polygon_count if frame_index is None else int(frame_index), list(all_ids), H, W)
+        n = len(all_ids)
+        if n == 0:                               # a frame without objects is reported with no entries: nothing to launch
+            return dict(poly_meta=meta)
+        if n > O.OpList.POLY_MAX_OBJECTS:
+            raise ValueError(f'polygons: {n} objects, at most {O.OpList.POLY_MAX_OBJECTS} per frame')
+        objs = self._tables.get('polygons', tuple(all_ids), lambda: torch.tensor(list(all_ids), dtype=torch.int32).to(dev))
+        edges = min(POLY_EDGES, O.OpList.polygon_capacity(H, W)[1])
+        scratch = self._scratch.get('polygons', (H, W), lambda: torch.empty(O.OpList.polygon_scratch_words(H, W, n, edges), dtype=torch.int32, device=dev))
+        b = self._pools['polygons'].take(H, W)
+        ol = O.OpList()
+        ol.polygon_trace(ids, objs, b.slab.stream, b.table[:4 * n], b.slab.status, scratch, connectivity=self.region_connectivity, edge_capacity=edges)
+        ol.run()
+        b.slab.copy()
+        b.event.record()
+        return dict(polygons=b, poly_meta=meta)
 
     # ---- overlay='device' -------------------------------------------------------------------------------------------------------
     def _queue_overlay(self, b, ids, all_ids, path_to_image, image_u8) -> dict:
@@ -683,6 +749,8 @@ class ResultSaver:
             self.scores = self.scorer.finish()
         if self.tracks is not None:
             self.tracks.write(path.join(self.tracks_output_root, self.video_name))
+        if self.polygons is not None:
+            self.polygons.write(path.join(self.polygons_output_root, self.video_name))
 
     # ---- the writer thread: one function per output family, called by _writer in this order ---------------------------------------
     def _put(self, root, folder, name, data: bytes):
@@ -789,6 +857,24 @@ class ResultSaver:
             table = np.zeros((0, 12), dtype=np.int32)
         self.tracks.add(job.frame_name, index, table, objs, H, W)
 
+    def _write_polygons(self, job):
+        """The frame's rings to the polygon report: its slab has landed behind its event (no slab: a frame without objects).  A frame that
+        did not fit the stage's capacities is traced here from the id plane (the host's copy, or a copy of the device's)."""
+        if job.poly_meta is None:
+            return
+        index, objs, H, W = job.poly_meta
+        n, b = len(objs), job.polygons
+        raw = b.slab.fetch(b.event) if b is not None else b''
+        if raw is None:
+            plane = job.mask.numpy() if job.mask is not None else self._copies.to_host(job.egress.ids)
+            rings, verts, table = trace_rings(np.ascontiguousarray(plane, dtype=np.uint8), objs, self.region_connectivity)
+        else:
+            R = int(b.slab.host[:16].view(torch.int32)[2]) if b is not None else 0
+            table = np.frombuffer(raw, dtype=np.int32, count=4 * n).reshape(-1, 4).copy()
+            rings = np.frombuffer(raw, dtype=np.int32, count=4 * R, offset=POLY_TABLE if R else 0).reshape(-1, 4).copy()
+            verts = np.frombuffer(raw, dtype=np.uint32, offset=POLY_TABLE + 16 * R).copy() if b is not None else np.zeros(0, dtype=np.uint32)
+        self.polygons.add(job.frame_name[:-4], index, rings, verts, table, objs, H, W)
+
     def _write_regions(self, job):
         """min_region / fill_holes: the frame's counts, landed behind their event, to the video's totals"""
         if job.regions is not None:
@@ -856,6 +942,7 @@ def _writer(queue: Queue):
             s._write_scores(job)
             s._write_matte(job)
             s._write_tracks(job)
+            s._write_polygons(job)
             s._write_regions(job)
             s._write_bands(job)
             s._write_overlay(job, rgb_mask)

@@ -6,6 +6,7 @@ from queue import Empty, Queue
 import numpy as np
 import torch
 
+POLY_TABLE = 255 * 16       # polygons: bytes of the object table of up to 255 objects between the status block and the stream
 RLE_TABLE = 16 + 255 * 16   # BURST: bytes of the status block and the table of up to 255 objects in front of the RLE strings
 
 
@@ -140,6 +141,17 @@ class TrackBuffers(_Buffers):
         super().__init__(device)
         self.dev = torch.empty(O.OpList.TRACK_MAX_OBJECTS * O.OpList.TRACK_WORDS, dtype=torch.int32, device=device)
         self.host = self.twin(self.dev)
+
+
+class PolygonBuffers(_Buffers):
+    """What one frame in flight owns of the polygon report: the [status | object table | rings and vertices] slab with its pinned head,
+    and the event behind its copy."""
+
+    def __init__(self, H, W, device, slab):
+        super().__init__(device)
+        self.H, self.W = H, W
+        self.slab = slab('polygons', H, W)
+        self.table = self.slab.dev[16:16 + POLY_TABLE].view(torch.int32)
 
 
 class RegionBuffers(_Buffers):

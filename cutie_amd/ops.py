@@ -1171,6 +1171,78 @@ class OpList:
         return self.add(PROB_TO_ID, 4096, [0, H, W, inner, outer, limit, mid, words >> 31, words & 0x7fffffff, S], [],
                         [None, None, ids_plane, band, None, scratch, sets, dist2])
 
+    POLY_MAX_OBJECTS = 255
+    POLY_VERTEX_BLOCK = 1024  # lattice vertices per block of the edge sweeps (csrc/polygons.hip PLY_VPB)
+    POLY_SLOT_BLOCK = 256     # edge slots per block of the ring-head tables (PLY_T)
+    POLY_SMALL_EDGES = 4096   # up to this many boundary edges one workgroup traces in LDS (PLY_SMALL); more take the general chain
+
+    @classmethod
+    def polygon_scratch_words(cls, H, W, n, edge_capacity):
+        """int32 words of the scratch of polygon_trace (csrc/polygons.hip ply_layout), with NV = (H + 1)(W + 1) lattice vertices and C =
+        edge_capacity, every array rounded up to 4 words: 64 of header, a total per block of 1024 vertices, the first slot per vertex
+        (NV), per edge slot its edge index, object row and predecessor (3 C), two buffers of the pointer-jumping state (2 x 5 C), the
+        ring's vertex offset (C), two tables of 256 rows per block of 256 slots, and 512 row offsets.  ``n`` does not enter."""
+        NV, C = (H + 1) * (W + 1), int(edge_capacity)
+        up4 = lambda v: (v + 3) & ~3
+        return 64 + up4(-(-NV // cls.POLY_VERTEX_BLOCK)) + up4(NV) + 14 * up4(C) + 512 * -(-C // cls.POLY_SLOT_BLOCK) + 512
+
+    @staticmethod
+    def polygon_capacity(H, W):
+        """(stream bytes, edge capacity) that hold ANY plane of H x W: V <= 4 (H + 1)(W + 1) corners and R <= V / 4 rings of 16 bytes, so
+        32 bytes per lattice vertex; E <= 2 (H (W + 1) + (H + 1) W), every crack in both directions."""
+        return 32 * (H + 1) * (W + 1), 2 * (H * (W + 1) + (H + 1) * W)
+
+    def polygon_trace(self, ids_plane, obj_ids, stream, table, status, scratch, *, connectivity=8, edge_capacity, path=0):
+        """PROB_TO_ID flags == 8192 (ABI 11, form added; include/cutie_hip.h): ids_plane uint8 [H, W] (contiguous, any alignment, read
+        only) -> the outlines of the objects of ``obj_ids`` (a sequence of ints, or an int32 tensor of them on the device, which is not
+        inspected; at most 255) as rings of lattice corners.  ``stream`` (uint8 or int32, contiguous, 16-byte aligned, a multiple of 4
+        bytes) receives rings int32 [R, 4] (object row | first vertex | vertices | unit edges) and directly behind them vertices uint32
+        [V] (x | y << 16); ``table`` int32 [n, 4]: first ring | rings | first vertex | vertices per entry of the list; ``status`` int32
+        [4]: stream bytes 16 R + 4 V | error bits (1: the stream does not fit, nothing is written to it; 2: more boundary edges than
+        ``edge_capacity``, nothing is traced) | R | E.  ``scratch``: int32, 16-byte aligned, at least ``polygon_scratch_words(H, W, n,
+        edge_capacity)`` words.  ``connectivity`` 8 joins diagonal pixels into one ring, 4 keeps them apart.  ``path`` 1 forces the
+        general launch chain; the results are the same."""
+        _need_form(_lib.has_polygons, 'no polygon trace, PROB_TO_ID flags == 8192')
+        H, W = _u8_plane('polygon_trace', 'ids_plane', ids_plane)
+        if H > 65535 or W > 65535:
+            raise ValueError(f'polygon_trace: a plane of {H} x {W}: a vertex packs x and y into 16 bits each, H, W <= 65535')
+        if (H + 1) * (W + 1) >= 1 << 29:
+            raise ValueError(f'polygon_trace: a plane of {H} x {W} has 2^29 lattice vertices or more')
+        n, objs, listed = _object_ids('polygon_trace', 'obj_ids', obj_ids)
+        if not 0 <= n <= self.POLY_MAX_OBJECTS:
+            raise ValueError(f'polygon_trace: {n} objects, 0 .. {self.POLY_MAX_OBJECTS}')
+        connectivity, edge_capacity, path = int(connectivity), int(edge_capacity), int(path)
+        if connectivity not in (4, 8):
+            raise ValueError(f'polygon_trace: connectivity {connectivity}, 4 or 8')
+        if path not in (0, 1):
+            raise ValueError(f'polygon_trace: path {path}, 0 (the launcher chooses) or 1 (the general path)')
+        if not 1 <= edge_capacity < 1 << 31:
+            raise ValueError(f'polygon_trace: edge_capacity {edge_capacity}, 1 .. 2^31 - 1')
+        if stream.dtype not in (torch.uint8, torch.int32) or not stream.is_contiguous():
+            raise ValueError(f'polygon_trace: stream is a contiguous uint8 or int32 buffer, not {stream.dtype}')
+        cap = int(stream.numel()) * stream.element_size()
+        if cap % 4 or cap >= 1 << 31:
+            raise ValueError(f'polygon_trace: a stream of {cap} bytes: a multiple of 4 below 2^31')
+        if table.dtype != torch.int32 or table.numel() != n * 4 or not table.is_contiguous():
+            raise ValueError(f'polygon_trace: table is a contiguous int32 [{n}, 4]')
+        if status.dtype != torch.int32 or status.numel() != 4 or not status.is_contiguous():
+            raise ValueError('polygon_trace: status is a contiguous int32 [4]')
+        need = self.polygon_scratch_words(H, W, n, edge_capacity)
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < need:
+            raise ValueError(f'polygon_trace: scratch is a contiguous int32 of at least {need} words')
+        for name, t in (('stream', stream), ('scratch', scratch)) + ((('table', table),) if n else ()):
+            if t.data_ptr() % 16:
+                raise ValueError(f'polygon_trace: {name} is 16-byte aligned')
+        for name, t in (('stream', stream), ('table', table), ('status', status), ('scratch', scratch)):
+            if t.device != ids_plane.device:
+                raise ValueError(f'polygon_trace: {name} is on {t.device}, ids_plane on {ids_plane.device}')
+        if objs is None and n:
+            objs = torch.tensor(listed, dtype=torch.int32).to(ids_plane.device)
+            self.keep.append(objs)
+        words = int(scratch.numel())
+        return self.add(PROB_TO_ID, 8192, [0, H, W, edge_capacity, cap, connectivity, path, words >> 31, words & 0x7fffffff, n], [],
+                        [None, None, ids_plane, stream, status, scratch, objs if n else None, table if n else None])
+
     JPEG_ENC_BLOCK_WORDS = 52     # JPG_BLOCK_WORDS (csrc/jpeg_enc.hip): a coded block is at most 22 + 63 * 26 = 1660 bits
 
     @staticmethod

@@ -56,6 +56,7 @@ from .inference.data.prefetch import ReadAhead, Window
 from .inference.data.video_reader import INGEST_MODES
 from .inference.inference_core import InferenceCore
 from .inference.utils.results_utils import EGRESS_MODES, VIS_MODES, ResultSaver
+from .inference.utils.polygons import PolygonReport
 from .inference.utils.track_report import TrackReport
 
 IMAGE_EXT = ('.jpg', '.jpeg', '.png', '.bmp')
@@ -160,7 +161,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
-                  region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0) -> Dict:
+                  region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0, polygons: bool = False) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
@@ -171,7 +172,9 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     small enclosed holes filled, on the device, before the mask is written, composed, tracked or scored; 'regions' (the totals) joins the
     result.  The model never sees the filtered plane.
     trimap = (r_in, r_out) / trimap_objects / dilate_mask = r: ResultSaver's -- output_dir/trimap/*.png (0 | 128 | 255) of the target objects
-    (default all), one per object in trimap_objects/<id>/, and the target objects dilated by the disk of r pixels in dilated/*.png."""
+    (default all), one per object in trimap_objects/<id>/, and the target objects dilated by the disk of r pixels in dilated/*.png.
+    polygons: every object's outline on every frame as exact rings of lattice corners, traced on the device (inference/utils/polygons.py):
+    output_dir/polygons/polygons.json, and 'polygons' (the json's content) in the result."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
@@ -258,7 +261,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             alpha_matte=alpha_matte, target_objects=target_objects, layer=layer,
                             tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None,
                             min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity,
-                            trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask)
+                            trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
+                            polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None)
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -283,6 +287,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         out['scores'] = saver.scores
     if tracks:
         out['tracks'] = saver.tracks.as_dict()
+    if polygons:
+        out['polygons'] = saver.polygons.as_dict()
     if saver.regions is not None:
         out['regions'] = saver.regions
     if vis_modes or soft_masks or alpha_matte:
@@ -317,6 +323,8 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--gt', help='ground-truth masks named like the outputs: prints the DAVIS J&F of the video (every frame that has one is scored)')
     ap.add_argument('--tracks', action='store_true',
                     help='OUT/tracks/tracks.json and tracks_mot.txt: area, box, centroid and confidence of every object on every frame, counted on the GPU')
+    ap.add_argument('--polygons', action='store_true',
+                    help='OUT/polygons/polygons.json: every object of every frame as exact rings of lattice corners (outer rings and holes), traced on the GPU')
     ap.add_argument('--min-region', type=int, default=0, metavar='N',
                     help='drop object components of fewer than N pixels from every mask, on the GPU, before it is written, composed, tracked or scored (0, 1: off)')
     ap.add_argument('--fill-holes', type=int, default=0, metavar='N',
@@ -351,7 +359,8 @@ def main():
                       mem_cleanup_ratio=args.mem_cleanup_ratio, ingest=args.ingest, egress=args.egress, gt_dir=args.gt, gt_decode=args.gt_decode,
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
                       decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
-                      region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask)
+                      region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask,
+                      polygons=args.polygons)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

@@ -565,7 +565,58 @@ enum {
      *    depend on the plane, the sets and i3 .. i6 alone.
      *    The launcher refuses, each with its own message and before any launch: H, W < 1, H * W >= 2^31, S outside 1 ..
      *    CUTIE_EDT_MAX_SETS, a negative inner or outer, a limit outside max(inner, outer) + 1 .. CUTIE_EDT_MAX_LIMIT, mid outside 0 ..
-     *    255, a null p2, p6 or p5, p3 and p7 both null, p5 or p7 not 4-byte aligned, fewer scratch words than needed. */
+     *    255, a null p2, p6 or p5, p3 and p7 both null, p5 or p7 not 4-byte aligned, fewer scratch words than needed.
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 7, value 128, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- the outlines of the objects of an id plane as exact polygons (not in the
+     *    reference; ResultSaver polygons=, eval_vos / process_video --polygons):
+     *  flags == 8192, a stage ON ITS OWN (8192 combined with any other flag stays the "unknown flags" error): every listed object of an
+     *    existing uint8 id plane p2 = [i1, i2] = [H, W] (row-major and contiguous, any alignment, READ ONLY) is traced into RINGS of
+     *    lattice corners (kernels in polygons.hip; the model: tests/polygon_ref.py).  i0, p0, p1 and the floats are unused.
+     *    SET AND LATTICE.  For a listed object with id v, F = {(x, y): plane[y][x] == v}.  Pixel (x, y) is the unit square [x, x + 1] x
+     *    [y, y + 1]; lattice vertices are the pixel corners (x, y), 0 <= x <= W, 0 <= y <= H.  Everything outside the frame is "not F":
+     *    an object cut by the border is closed along the border (unlike flags == 4096, where nothing exists outside: a polygon closes).
+     *    DIRECTED BOUNDARY EDGES.  A boundary edge is a unit edge between a pixel of F and one that is not, directed so that F lies on the
+     *    RIGHT of the direction of travel (x right, y down).  For a pixel of F at (x, y), where the neighbour across is not F:
+     *      top    E, d = 0: (x, y) -> (x + 1, y)            right  S, d = 1: (x + 1, y) -> (x + 1, y + 1)
+     *      bottom W, d = 2: (x + 1, y + 1) -> (x, y + 1)    left   N, d = 3: (x, y + 1) -> (x, y)
+     *    An edge is named by its tail vertex and direction: e = (y (W + 1) + x) * 4 + d.
+     *    SUCCESSOR.  The next edge starts at the head vertex: the first existing edge of the object there in the order left, straight,
+     *    right for connectivity 8 and right, straight, left for connectivity 4.  The two differ only at a SADDLE (the two pixels of one
+     *    diagonal in F, the other two not): 8 turns left and crosses to the diagonal pixel -- an 8-connected component is one ring that
+     *    touches itself at the vertex --, 4 turns right and stays on its pixel.  The successor is a permutation of the object's boundary
+     *    edges; its cycles are the rings.
+     *    RING.  A ring's first edge is its edge of smallest e (the smallest (y, x, d) of its tails).  Its vertices are the tails of the
+     *    edges whose predecessor has another direction (the corners; collinear lattice points are dropped), in the order of travel from
+     *    the first edge's tail, which is a corner.  Consecutive vertices differ in one coordinate, horizontal and vertical steps
+     *    alternate, a ring has an even number >= 4 of vertices.  The shoelace sum 1/2 sum(x_i y_{i+1} - x_{i+1} y_i) is positive for an
+     *    outer ring and negative for a hole; a ring is a hole iff its first edge is vertical (d = 1; an outer ring's has d = 0); the
+     *    signed areas of an object's rings add up to its pixel count.  The rings of an object are ordered by first edge, the objects as
+     *    listed.
+     *    p6 = object ids int32 [i9], 0 <= n <= 255.  Ids of the plane that are not listed belong to no object; an entry outside 1 .. 255
+     *    or equal to an earlier entry is an absent object without rings (the convention of flags == 32).
+     *    i5 = connectivity, 4 or 8.  i6 = path: 0 lets the launcher's chain choose (up to 4096 boundary edges are traced by one workgroup
+     *    in LDS), 1 forces the general chain; the results are the same words.  i3 = edge capacity E_cap >= 1.
+     *    p5 = scratch int32, 16-byte aligned, of i8 + 2^31 * i7 words (i7, i8 >= 0): at least OpList.polygon_scratch_words(H, W, n,
+     *    E_cap) = 64 + up4(ceil(NV / 1024)) + up4(NV) + 14 up4(E_cap) + 512 ceil(E_cap / 256) + 512 with NV = (H + 1)(W + 1) and up4 =
+     *    rounded up to a multiple of 4.  Its content before and after the launch means nothing.
+     *    p3 = stream, 16-byte aligned, i4 = its capacity in bytes, a multiple of 4 (a stream of 0 bytes may be null): rings int32 [R][4]
+     *    = object row k in p6 | index of the first vertex in the vertex array | vertices | unit edges L (the perimeter), followed
+     *    directly by vertices uint32 [V] = x | y << 16.
+     *    p7 = object table int32 [n][4], 16-byte aligned, written whatever it held: first ring | rings | first vertex | vertices; an
+     *    absent or empty object gets (r, 0, v, 0) with r and v the running offsets.
+     *    p4 = status int32 [4]: the stream's bytes 16 R + 4 V | error bits | R | E = the boundary edges of all listed objects (always
+     *    valid).  With n == 0 only the status is written (all zero; p6 and p7 may be null).
+     *    Error bit 1: the stream does not fit i4 -- NOTHING is written to p3 and the table's offsets are 0; the counts, R, E and the byte
+     *    total stay valid.  Error bit 2: E > E_cap -- nothing is traced, words 0 and 2 are 0 and the table is all zero; word 3 says
+     *    what was needed.
+     *    Bounds: V <= 4 (H + 1)(W + 1), E <= 2 (H (W + 1) + (H + 1) W), R <= V / 4 (OpList.polygon_capacity).
+     *    Determinism: integers only; every offset comes from a scan in a fixed order or from sums and minima whose result does not depend
+     *    on the order of arrival: stream, table and status depend on the plane, the list and i5 alone -- not on i6, the launch shape or
+     *    timing.
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1, H or W above 65535, (H + 1)(W + 1) >= 2^29 (the
+     *    edge index has 31 bits), n outside 0 .. 255, a connectivity other than 4 or 8, i6 outside 0 .. 1, E_cap < 1, a negative capacity
+     *    or one that is no multiple of 4, a null p2, p4, p5, p3 (with i4 > 0), p6 or p7 (with n > 0), p3, p5 or p7 not 16-byte aligned,
+     *    p4 or p6 not 4-byte aligned, fewer scratch words than needed. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -704,7 +755,8 @@ int cutie_op_struct_size(void);
  * bit 1 (value 2): RESIZE flags 64 / 128, the PNG decode stages, are present.  bit 2 (value 4): RESIZE flags 256, the batch forms of the
  * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present.
  * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
- * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present. */
+ * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present.  bit 7 (value 128):
+ * PROB_TO_ID flags == 8192, the polygon trace, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

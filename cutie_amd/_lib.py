@@ -107,6 +107,13 @@ def has_polygons():
     return bool(load().cutie_hip_build_flags() & 128)
 
 
+def has_png_photo():
+    """Does the loaded library know PROB_TO_ID flags == 16384, the PNG stream with scanline filters and dynamic Huffman codes?  Added
+    without a new ABI number; a library from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is
+    missing (OpList.png_photo; ResultSaver cutout= / png_codes='dynamic')."""
+    return bool(load().cutie_hip_build_flags() & 256)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

@@ -34,3 +34,18 @@ def assemble(stream: bytes, H: int, W: int, palette: Optional[Union[bytes, Seque
         parts.append(_chunk(b'PLTE', plte_bytes(palette)))
     parts += [_chunk(b'IDAT', bytes(stream)), _chunk(b'IEND', b'')]
     return b''.join(parts)
+
+
+COLOR_TYPES = {1: 0, 2: 4, 3: 2, 4: 6}      # bytes per pixel -> PNG colour type at 8 bits: L, LA, RGB, RGBA
+
+
+def assemble_image(stream: bytes, H: int, W: int, channels: int) -> bytes:
+    """File bytes of an 8-bit PNG of H x W pixels of ``channels`` = 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA) bytes whose IDAT data is
+    ``stream``: the complete zlib stream of the filtered rows, any filter per row (csrc/png_photo.hip: filters chosen per row,
+    dynamic Huffman codes).  ``Image.open`` gives the mode and the exact pixels."""
+    if H < 1 or W < 1:
+        raise ValueError('assemble_image: empty image')
+    if channels not in COLOR_TYPES:
+        raise ValueError(f'assemble_image: {channels} channels, one of {tuple(COLOR_TYPES)}')
+    ihdr = struct.pack('>IIBBBBB', W, H, 8, COLOR_TYPES[channels], 0, 0, 0)
+    return b''.join([SIGNATURE, _chunk(b'IHDR', ihdr), _chunk(b'IDAT', bytes(stream)), _chunk(b'IEND', b'')])

@@ -110,6 +110,7 @@ davis_palette = davis_palette_np.tobytes()
 
 
 EGRESS_MODES = ('host', 'device')
+PNG_CODES = ('fixed', 'dynamic')   # the encoder of the soft masks and the alpha matte: the id planes' (csrc/png.hip) | filters + dynamic Huffman (csrc/png_photo.hip)
 EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
 OVERLAY_MODES = ('host', 'device')
 JPEG_SLAB = 256 * 1024      # overlay='device': bytes of the first device-to-host copy of a frame's JPEG: status + the head of the stream (a 480p overlay is 30-120 KB)
@@ -168,7 +169,7 @@ class ResultSaver:
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
                  target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8,
-                 trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None):
+                 trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None, cutout=False, png_codes='fixed'):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -207,7 +208,18 @@ class ResultSaver:
         is traced on the device into exact rings of lattice corners (PROB_TO_ID flags == 8192), on the plane the PNG is written from --
         behind the region filter, connected under ``region_connectivity`` -- and reported to it; ``end`` writes
         ``polygons_output_root``/<video>/polygons.json (default root: <output_root>/polygons).  A frame beyond the stage's bounded
-        capacities is traced on the host (one warning).  Needs ``processor``; long ids have no uint8 plane."""
+        capacities is traced on the host (one warning).  Needs ``processor``; long ids have no uint8 plane.
+        ``cutout`` (the 'rgba' output of the reference's interactive tool, gui/interactive_utils.py:218-229): per
+        saved frame <output_root>/<video>/cutout/<frame>.png, an RGBA PNG whose RGB is the frame (``image_u8`` or ``path_to_image`` of
+        ``process``) and whose A is the alpha matte of ``target_objects`` -- the plane ``alpha_matte`` writes --, filtered and
+        entropy-coded on the device (PROB_TO_ID flags == 16384).  A frame too wide for the stage's row limit is written through PIL
+        (one warning).  Needs ``processor``; a ``use_long_id`` saver and ``process_merged`` refuse it.
+        ``png_codes``: 'fixed' (default: the soft masks and the alpha matte go through the id planes' encoder, as before) | 'dynamic'
+        (they are encoded by the filtered, dynamic-Huffman stage with one byte per pixel: the same pixels in fewer bytes).  The id
+        masks, trimaps and dilated masks never change encoder."""
+        if png_codes not in PNG_CODES:
+            raise ValueError(f'png_codes must be one of {PNG_CODES}, not {png_codes!r}')
+        self.cutout, self.png_codes = bool(cutout), png_codes
         if polygons is not None and use_long_id:
             raise ValueError('polygons: outlines are traced on uint8 id planes; a use_long_id saver (RGB masks) cannot report them')
         if polygons is not None and processor is None:
@@ -266,12 +278,12 @@ class ResultSaver:
         if unknown or len(set(vis_modes)) != len(vis_modes):
             raise ValueError(f'vis_modes is a subset of {VIS_MODES}, not {vis_modes}')
         self.vis_modes, self.soft_masks, self.alpha_matte = vis_modes, bool(soft_masks), bool(alpha_matte)
-        self._matte_on = bool(vis_modes or soft_masks or alpha_matte)
+        self._matte_on = bool(vis_modes or soft_masks or alpha_matte or self.cutout)
         if self._matte_on and use_long_id:
-            raise ValueError('vis_modes / soft_masks / alpha_matte are composed from uint8 id planes and object planes on the device: '
+            raise ValueError('vis_modes / soft_masks / alpha_matte / cutout are composed from uint8 id planes and object planes on the device: '
                              'a use_long_id saver (RGB masks) cannot write them')
         if self._matte_on and processor is None:
-            raise ValueError('vis_modes / soft_masks / alpha_matte need the processor (its device)')
+            raise ValueError('vis_modes / soft_masks / alpha_matte / cutout need the processor (its device)')
         if 'layer' in vis_modes and layer is None:
             raise ValueError("vis mode 'layer' needs layer (an RGBA image)")
         self.target_objects = None if target_objects is None else [int(v) for v in target_objects]
@@ -301,7 +313,7 @@ class ResultSaver:
             self.video_json = {k: v for k, v in init_json.items() if k != 'segmentations'}
             self.video_json['segmentations'] = self.segmentations
             self.json_style = 'burst'
-        self._rle_warned = self._jpeg_warned = self._polygons_warned = False
+        self._rle_warned = self._jpeg_warned = self._polygons_warned = self._cutout_warned = False
         self.use_long_id, self.palette, self.object_manager = use_long_id, palette, object_manager
         self.save_mask, self.visualize, self.visualize_output_root = save_mask, visualize, visualize_output_root
         self.processor = processor
@@ -321,7 +333,7 @@ class ResultSaver:
         self._pools = dict(
             egress=Pool(limit, lambda H, W, png: EgressBuffers(H, W, dev(), self._slab, rle=self.json_style == 'burst' and png, png=png,
                                                                jpeg=self.overlay == 'device')),
-            matte=Pool(limit, lambda H, W, K: MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev(), self._slab)),
+            matte=Pool(limit, lambda H, W, K: MatteBuffers(H, W, K, self.vis_modes, self.alpha_matte, dev(), self._slab, **self._matte_forms(W))),
             tracks=Pool(limit, lambda: TrackBuffers(dev())),
             regions=Pool(limit, lambda: RegionBuffers(dev())),
             polygons=Pool(limit, lambda H, W: PolygonBuffers(H, W, dev(), self._slab)),
@@ -336,6 +348,10 @@ class ResultSaver:
         dev = self.processor.network.device
         if kind == 'png':
             return Slab(O.OpList.png_capacity(H, W), EGRESS_SLAB, dev, self._copies)
+        if kind == 'png dynamic':                # a grey plane through the filtered, dynamic-Huffman stage
+            return Slab(O.OpList.png_photo_capacity(H, W, 1), EGRESS_SLAB, dev, self._copies)
+        if kind == 'cutout':                     # RGBA; the pinned head holds half the raw size, a photograph takes about a third
+            return Slab(O.OpList.png_photo_capacity(H, W, 4), 16 + 2 * H * W, dev, self._copies, what='cut-out PNG')
         if kind == 'polygons':
             def beyond(length, capacity):
                 if not self._polygons_warned:
@@ -409,7 +425,7 @@ class ResultSaver:
         if self.save_scores:
             raise ValueError('process_merged writes no scores: save_scores and the merge exclude each other')
         if self._matte_on:
-            raise ValueError('process_merged has no probability planes of its own: vis_modes / soft_masks / alpha_matte need process')
+            raise ValueError('process_merged has no probability planes of its own: vis_modes / soft_masks / alpha_matte / cutout need process')
         if self.processor is None:
             raise ValueError('process_merged needs the processor (its device; the merge has no host implementation)')
         own = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items()}
@@ -693,6 +709,19 @@ class ResultSaver:
             return torch.from_numpy(jpeg_writer.color_table(pal, all_ids)).to(dev)
         return self._tables.get('matte colors', tuple(all_ids), make)
 
+    def _matte_forms(self, W) -> dict:
+        """Which encoders a matte buffer set of width W is made for: ``cutout`` None | 'device' | 'host' (a row beyond the stage's
+        limit: PIL, one warning), ``dynamic``: the grey planes through the filtered stage."""
+        from ... import ops as O
+        cutout = None
+        if self.cutout:
+            cutout = 'device' if O.OpList.png_photo_fits(W, 4) else 'host'
+            if cutout == 'host' and not self._cutout_warned:
+                self._cutout_warned = True
+                log.warning(f'cut-outs: a row of {W} RGBA pixels is beyond the device PNG stage\'s limit of {O.OpList.PNG_PHOTO_ROW_LIMIT} bytes; '
+                            f'the cut-outs of {self.video_name} are written through PIL')
+        return dict(cutout=cutout, dynamic=self.png_codes == 'dynamic' and O.OpList.png_photo_fits(W, 1))
+
     def _queue_matte(self, prob, out_hw, ids, all_ids, path_to_image, image_u8) -> dict:
         """Queue the composite launches of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
         device), each followed by the JPEG stage on the composed frame, the soft-mask launch and the PNG stage per plane, the pinned
@@ -710,29 +739,38 @@ class ResultSaver:
         obj_to_tmp = {o: t for t, o in tmp_to_obj.items()}
         targets = [obj_to_tmp[o] for o in wanted if o in obj_to_tmp]
         ol = O.OpList()
+        need_matte = self.alpha_matte or self.cutout                 # the cut-out's fourth channel is the plane alpha_matte writes
+        frame = self._frame_u8(H, W, dev, path_to_image, image_u8) if (self.vis_modes or self.cutout) else None
         if self.vis_modes:
-            frame = self._frame_u8(H, W, dev, path_to_image, image_u8)
             qtables, scratch = self._jpeg_setup(H, W, dev)
             colors = self._matte_colors(all_ids, dev) if any(m in ('davis', 'light', 'fade') for m in self.vis_modes) else None
             for k, mode in enumerate(self.vis_modes):
                 soft = mode in ('popup', 'layer')
-                with_matte = self.alpha_matte and soft and not any(m in ('popup', 'layer') for m in self.vis_modes[:k])
+                with_matte = need_matte and soft and not any(m in ('popup', 'layer') for m in self.vis_modes[:k])
                 ol.matte_composite(mode, b.frames[k], out_hw=(H, W), frame=frame, planes=prob if soft else None, targets=targets,
                                    ids=None if soft else ids, colors=None if soft else colors,
                                    layer=self._layer(H, W, dev) if mode == 'layer' else None, matte=b.matte if with_matte else None)
                 ol.jpeg_encode(b.frames[k], None, None, qtables, b.jpeg[k].stream, b.jpeg[k].status, scratch, H=H, W=W)
-        if self.alpha_matte and not any(m in ('popup', 'layer') for m in self.vis_modes):
+        if need_matte and not any(m in ('popup', 'layer') for m in self.vis_modes):
             ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=targets, matte=b.matte)
         if K > 0:
             ol.matte_soft(prob, b.planes[:K], out_hw=(H, W))
-        scratch = self._scratch.get('matte png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
-        for k, slab in enumerate(b.png):
-            ol.png_deflate(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch, H=H, W=W)
+        if b.dynamic:
+            scratch = self._scratch.get('matte png dynamic', (H, W), lambda: torch.empty(O.OpList.png_photo_scratch_words(H, W, 1), dtype=torch.int32, device=dev))
+            for k, slab in enumerate(b.png):
+                ol.png_photo(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch)
+        else:
+            scratch = self._scratch.get('matte png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
+            for k, slab in enumerate(b.png):
+                ol.png_deflate(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch, H=H, W=W)
+        if b.cutout is not None:                 # frame + matte -> RGBA, interleaved inside the stage: no RGBA buffer exists
+            scratch = self._scratch.get('cutout', (H, W), lambda: torch.empty(O.OpList.png_photo_scratch_words(H, W, 4), dtype=torch.int32, device=dev))
+            ol.png_photo(frame, b.cutout.stream, b.cutout.status, scratch, last=b.matte)
         ol.run()
-        for slab in b.jpeg + b.png:
+        for slab in b.jpeg + b.png + ([b.cutout] if b.cutout is not None else []):
             slab.copy()
         b.event.record()
-        return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep))
+        return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep, frame))
 
     def end(self):
         self.queue.put(None)
@@ -844,6 +882,14 @@ class ResultSaver:
                 self._put(self.output_root, 'alpha', stem + '.png', data)
             elif job.matte_objects[k] is not None:
                 self._put(self.output_root, path.join('soft_masks', str(job.matte_objects[k])), stem + '.png', data)
+        if b.cutout is not None:
+            self._put(self.output_root, 'cutout', stem + '.png', png_container.assemble_image(b.cutout.fetch(b.event), b.H, b.W, 4))
+        elif b.cutout_mode == 'host':                # a row beyond the device stage's limit: frame and matte through PIL
+            b.event.synchronize()
+            rgba = np.dstack([self._copies.to_host(job.matte_keep[2]), self._copies.to_host(b.matte)])
+            folder = path.join(self.output_root, self.video_name, 'cutout')
+            os.makedirs(folder, exist_ok=True)
+            Image.fromarray(rgba, 'RGBA').save(path.join(folder, stem + '.png'), compress_level=1)
 
     def _write_tracks(self, job):
         """The frame's rows to the track report: its table has landed behind its event (no table: a frame without objects)."""

@@ -122,15 +122,20 @@ class MatteBuffers(_Buffers):
     """What one frame in flight owns of the vis_modes / soft_masks / alpha_matte outputs: per mode the composed frame and the slab of its
     JPEG segment, the quantised planes (K soft masks, then the matte) and per plane the slab of its zlib stream; one event behind all copies."""
 
-    def __init__(self, H, W, K, modes, alpha, device, slab):
+    def __init__(self, H, W, K, modes, alpha, device, slab, *, cutout=None, dynamic=False):
+        """``cutout``: None | 'device' (the slab of the RGBA cut-out's zlib stream) | 'host' (the frame is beyond the device stage's row
+        limit: the writer thread encodes it with PIL from the frame and the matte).  ``dynamic``: the planes' streams come from the
+        filtered, dynamic-Huffman stage (ResultSaver png_codes='dynamic')."""
         super().__init__(device)
         self.H, self.W, self.K, self.modes, self.alpha = H, W, K, tuple(modes), alpha
+        self.cutout_mode, self.dynamic = cutout, bool(dynamic)
         # (one tensor per mode: the composite's dword stores need a 16-byte aligned frame, and H * W * 3 is rarely a multiple of 16)
         self.frames = [torch.empty((H, W, 3), dtype=torch.uint8, device=device) for _ in self.modes]
         self.jpeg = [slab('jpeg', H, W) for _ in self.modes]
         self.planes = torch.empty((K, H, W), dtype=torch.uint8, device=device)               # the soft masks
-        self.matte = torch.empty((H, W), dtype=torch.uint8, device=device) if alpha else None # (a tensor of its own: 16-byte aligned)
-        self.png = [slab('png', H, W) for _ in range(K + (1 if alpha else 0))]
+        self.matte = torch.empty((H, W), dtype=torch.uint8, device=device) if (alpha or cutout) else None   # (a tensor of its own: 16-byte aligned)
+        self.png = [slab('png dynamic' if dynamic else 'png', H, W) for _ in range(K + (1 if alpha else 0))]
+        self.cutout = slab('cutout', H, W) if cutout == 'device' else None
 
 
 class TrackBuffers(_Buffers):

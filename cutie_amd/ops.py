@@ -992,6 +992,68 @@ class OpList:
         was written, 0).  scratch int32 [>= png_scratch_words(H, W)], 16-byte aligned.  cutie_amd/inference/utils/png.py wraps the stream."""
         return self.add(PROB_TO_ID, 8, [0, H, W, 0, 0, 0, 0, stream.numel(), scratch.numel()], [], [None, None, ids, stream, status, scratch])
 
+    PNG_PHOTO_ROW_LIMIT = 16384   # L = W * B + 1 (csrc/png_photo.hip PPH_ROW_LIMIT): every match distance inside DEFLATE's window
+    PNG_PHOTO_BAND = 32           # rows per DEFLATE block (PPH_R)
+
+    @classmethod
+    def png_photo_fits(cls, W, B):
+        """Does a row of W pixels of B bytes fit the row limit of png_photo?"""
+        return W * B + 1 <= cls.PNG_PHOTO_ROW_LIMIT
+
+    @classmethod
+    def png_photo_capacity(cls, H, W, B):
+        """Bytes that hold the zlib stream of ANY image of H x W pixels of B bytes: a block is never longer than its fixed-code form, in
+        which a filtered byte costs at most 9 bits; 10 bits of header and end-of-block per block of 32 rows; 2 bytes header, 4 bytes
+        Adler-32; rounded up to a multiple of 4."""
+        nb = -(-H // cls.PNG_PHOTO_BAND)
+        return -(-(-(-(9 * H * (W * B + 1) + 10 * nb) // 8) + 6) // 4) * 4
+
+    @classmethod
+    def png_photo_scratch_words(cls, H, W, B):
+        """int32 words of the scratch of png_photo (csrc/png_photo.hip pph_layout): 4 per row, 1024 per block of 32 rows (counts, codes,
+        header), the filtered bytes [H, L] and a 16-bit record per filtered byte, each rounded up to 4 words."""
+        L, nb = W * B + 1, -(-H // cls.PNG_PHOTO_BAND)
+        up4 = lambda v: (v + 3) & ~3
+        return 4 * H + 1024 * nb + up4(-(-H * L // 4)) + up4(-(-H * L // 2))
+
+    def png_photo(self, src, stream, status, scratch, *, last=None, ldrow=None):
+        """PROB_TO_ID flags == 16384 (ABI 11, form added; include/cutie_hip.h): the complete zlib stream of a PNG with scanline filters
+        and dynamic Huffman codes.  ``src`` uint8 [H, W] (a plane) or [H, W, 3] (packed pixels, row stride ``ldrow`` bytes, default the
+        tensor's), ``last`` an optional uint8 [H, W] plane that becomes the last channel: B = 1 (L), 2 (LA), 3 (RGB) or 4 (RGBA) bytes per
+        pixel, interleaved inside the launch.  ``stream`` uint8 [capacity] (4-byte aligned; png_photo_capacity holds any image);
+        ``status`` int32 [4] = (stream bytes, Adler-32, error bits: 1 = the capacity is too small and nothing was written, 0);
+        ``scratch`` int32 [>= png_photo_scratch_words(H, W, B)], 16-byte aligned.  W * B + 1 <= PNG_PHOTO_ROW_LIMIT.
+        cutie_amd/inference/utils/png.py wraps the stream (assemble_image)."""
+        _need_form(_lib.has_png_photo, 'no filtered PNG stream, PROB_TO_ID flags == 16384')
+        if src.dtype != torch.uint8 or src.dim() not in (2, 3) or (src.dim() == 3 and (src.shape[2] != 3 or src.stride(1) != 3)) or src.stride(-1) != 1:
+            raise ValueError(f'png_photo: src is uint8 [H, W] or [H, W, 3] with packed pixels, not {src.dtype} {tuple(src.shape)} strides {src.stride()}')
+        H, W, c0 = int(src.shape[0]), int(src.shape[1]), 3 if src.dim() == 3 else 1
+        if H < 1 or W < 1:
+            raise ValueError(f'png_photo: an image of {H} x {W}')
+        ld0 = int(src.stride(0) if ldrow is None else ldrow)
+        if ld0 < W * c0:
+            raise ValueError(f'png_photo: a row stride of {ld0} bytes below the row\'s {W * c0}')
+        B = c0 + (1 if last is not None else 0)
+        if last is not None and (last.dtype != torch.uint8 or tuple(last.shape) != (H, W) or last.stride(1) != 1 or last.stride(0) < W):
+            raise ValueError(f'png_photo: last is a uint8 [{H}, {W}] plane with contiguous rows')
+        if not self.png_photo_fits(W, B):
+            raise ValueError(f'png_photo: a row of {W} pixels of {B} bytes: W * B + 1 <= {self.PNG_PHOTO_ROW_LIMIT}')
+        if 9 * H * (W * B + 1) + 10 * -(-H // self.PNG_PHOTO_BAND) + 64 >= 1 << 31:
+            raise ValueError(f'png_photo: {H} x {W} x {B} exceeds 2^31 stream bits')
+        if stream.dtype != torch.uint8 or not stream.is_contiguous() or stream.data_ptr() % 4:
+            raise ValueError('png_photo: stream is a contiguous uint8 buffer, 4-byte aligned')
+        if status.dtype != torch.int32 or status.numel() != 4 or not status.is_contiguous():
+            raise ValueError('png_photo: status is a contiguous int32 [4]')
+        need = self.png_photo_scratch_words(H, W, B)
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < need or scratch.data_ptr() % 16:
+            raise ValueError(f'png_photo: scratch is a contiguous int32 of at least {need} words, 16-byte aligned')
+        for name, t in (('last', last), ('stream', stream), ('status', status), ('scratch', scratch)):
+            if t is not None and t.device != src.device:
+                raise ValueError(f'png_photo: {name} is on {t.device}, src on {src.device}')
+        return self.add(PROB_TO_ID, 16384, [0, H, W, c0, ld0, int(last.stride(0)) if last is not None else 0, 0, stream.numel(),
+                                            min(scratch.numel(), (1 << 31) - 1)], [],
+                        [None, None, src, stream, status, scratch, last])
+
     RLE_MAX_OBJECTS = 255
 
     @staticmethod

@@ -17,7 +17,7 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
         [--vis MODE [MODE ...]] [--soft-masks] [--alpha] [--target-objects ID [ID ...]] [--layer FILE]
-        [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
+        [--cutout] [--png-codes fixed|dynamic] [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
         [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
                             has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
 
@@ -27,6 +27,11 @@ the GPU (ResultSaver vis_modes / soft_masks / alpha_matte) into OUT/visualizatio
 OUT/alpha/*.png.  ``--target-objects``: the objects that popup, layer and the matte keep (default all); ``--layer``: the RGBA image of
 mode layer.  The uint8 frame the modes read is the one device ingest uploaded or decoded; with ``--ingest host`` it is made from the
 float frame on the device, once per frame.
+
+``--cutout``: the 'rgba' output of that tool (gui/interactive_utils.py:218-229) -- OUT/cutout/*.png, the frame as an RGBA PNG whose alpha is
+the matte of the ``--target-objects``: the objects cut out, ready to composite.  Frame and matte are interleaved, filtered and coded with
+dynamic Huffman codes on the GPU (csrc/png_photo.hip).  ``--png-codes dynamic`` sends the soft masks and the alpha matte through the same
+encoder (the same pixels in fewer bytes); the default ``fixed`` keeps their bytes as they were.  The id masks never change encoder.
 
 ``--trimap R_IN R_OUT``, ``--trimap-objects``, ``--dilate-mask R``: what matting and inpainting models take next to the frame, as 8-bit
 grey PNGs: OUT/trimap/*.png (255 sure foreground, 0 sure background, 128 the band of R_IN pixels inside and R_OUT pixels outside the edge
@@ -161,7 +166,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                   mem_cleanup_ratio: float = -1, mem_get_info=None, lookahead: bool = True, ingest: str = 'host', egress: str = 'host',
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
-                  region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0, polygons: bool = False) -> Dict:
+                  region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0, polygons: bool = False,
+                  cutout: bool = False, png_codes: str = 'fixed') -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
@@ -174,12 +180,15 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     trimap = (r_in, r_out) / trimap_objects / dilate_mask = r: ResultSaver's -- output_dir/trimap/*.png (0 | 128 | 255) of the target objects
     (default all), one per object in trimap_objects/<id>/, and the target objects dilated by the disk of r pixels in dilated/*.png.
     polygons: every object's outline on every frame as exact rings of lattice corners, traced on the device (inference/utils/polygons.py):
-    output_dir/polygons/polygons.json, and 'polygons' (the json's content) in the result."""
+    output_dir/polygons/polygons.json, and 'polygons' (the json's content) in the result.
+    cutout: per frame output_dir/cutout/*.png, the frame as RGBA with the alpha matte of the target objects as its fourth channel (the
+    'rgba' output of the reference's interactive tool), filtered and entropy-coded on the device.  png_codes = 'fixed' | 'dynamic':
+    ResultSaver's -- 'dynamic' writes the soft masks and the alpha matte through that encoder too (the same pixels, fewer bytes)."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
     vis_modes = tuple(vis_modes)
-    want_u8 = bool(vis_modes)                                   # the modes read the uint8 frame; soft masks and the matte do not
+    want_u8 = bool(vis_modes) or bool(cutout)                   # the modes and the cut-out read the uint8 frame; soft masks and the matte do not
     src = FrameSource(video, u8=(ingest == 'device'), packets=(ingest == 'device-decode'))
 
     def upload(f):
@@ -262,7 +271,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None,
                             min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity,
                             trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
-                            polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None)
+                            polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None, cutout=cutout, png_codes=png_codes)
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -291,9 +300,9 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         out['polygons'] = saver.polygons.as_dict()
     if saver.regions is not None:
         out['regions'] = saver.regions
-    if vis_modes or soft_masks or alpha_matte:
+    if vis_modes or soft_masks or alpha_matte or cutout:
         out['folders'] = ([path.join(output_dir, 'visualization', m) for m in vis_modes] + ([path.join(output_dir, 'soft_masks')] if soft_masks else []) +
-                          ([path.join(output_dir, 'alpha')] if alpha_matte else []))
+                          ([path.join(output_dir, 'alpha')] if alpha_matte else []) + ([path.join(output_dir, 'cutout')] if cutout else []))
     return out
 
 
@@ -316,7 +325,10 @@ def arg_parser() -> ArgumentParser:
                     help=f'visualisations written as OUT/visualization/MODE/*.jpg, composed and encoded on the GPU: {", ".join(VIS_MODES)}')
     ap.add_argument('--soft-masks', action='store_true', help='one 8-bit grey PNG per object and frame: OUT/soft_masks/<object id>/*.png')
     ap.add_argument('--alpha', action='store_true', help='the alpha matte of the target objects: OUT/alpha/*.png')
-    ap.add_argument('--target-objects', nargs='+', type=int, metavar='ID', help='the objects popup, layer and the matte keep (default: all)')
+    ap.add_argument('--target-objects', nargs='+', type=int, metavar='ID', help='the objects popup, layer, the matte and the cut-out keep (default: all)')
+    ap.add_argument('--cutout', action='store_true', help='the frame with the alpha matte of the target objects as its fourth channel: OUT/cutout/*.png (RGBA), encoded on the GPU')
+    ap.add_argument('--png-codes', choices=('fixed', 'dynamic'), default='fixed',
+                    help='the PNG encoder of the soft masks and the alpha matte: the id masks\' (fixed Huffman codes, default) or scanline filters + dynamic codes')
     ap.add_argument('--layer', metavar='FILE', help='the RGBA image of --vis layer (resized to the frames)')
     ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
                     help='--gt: device = the ground-truth PNGs are decoded on the GPU (default host: PIL)')
@@ -360,7 +372,7 @@ def main():
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
                       decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
                       region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask,
-                      polygons=args.polygons)
+                      polygons=args.polygons, cutout=args.cutout, png_codes=args.png_codes)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

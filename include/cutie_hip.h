@@ -28,6 +28,7 @@ extern "C" {
 #define CUTIE_OP_NF 6
 #define CUTIE_OP_NP 16
 #define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
+#define CUTIE_PNG_PHOTO_ROW_LIMIT 16384   /* PROB_TO_ID flags == 16384 (ABI 11, form added): filtered bytes per row, W * B + 1 */
 #define CUTIE_EDT_MAX_LIMIT 65536   /* PROB_TO_ID flags == 4096 (ABI 11, form added): distances are exact below it; radii up to 255 (255^2 = 65025) */
 #define CUTIE_EDT_MAX_SETS 16       /* ... sets of ids per op; the host splits more over several ops */
 #define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
@@ -616,7 +617,54 @@ enum {
      *    The launcher refuses, each with its own message and before any launch: H, W < 1, H or W above 65535, (H + 1)(W + 1) >= 2^29 (the
      *    edge index has 31 bits), n outside 0 .. 255, a connectivity other than 4 or 8, i6 outside 0 .. 1, E_cap < 1, a negative capacity
      *    or one that is no multiple of 4, a null p2, p4, p5, p3 (with i4 > 0), p6 or p7 (with n > 0), p3, p5 or p7 not 16-byte aligned,
-     *    p4 or p6 not 4-byte aligned, fewer scratch words than needed. */
+     *    p4 or p6 not 4-byte aligned, fewer scratch words than needed.
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 8, value 256, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- the reference tool's 'rgba' output (gui/interactive_utils.py:218-229, saved by
+     *    gui/resource_manager.py:158-161: the frame with the matte of the chosen objects as its alpha) and smooth grey planes as PNG;
+     *    ResultSaver cutout= / png_codes='dynamic', process_video --cutout / --png-codes; DESIGN.md section 24:
+     *  flags == 16384, a stage ON ITS OWN (16384 combined with any other flag stays the "unknown flags" error): the complete zlib stream of
+     *    a PNG's IDAT chunk with scanline filters chosen per row and dynamic Huffman codes (kernels in png_photo.hip; the model:
+     *    tests/png_photo_ref.py; the bytes are equal).  flags&8 is untouched: filter 0 and one fixed block, which suits id planes.
+     *    p2 = first source uint8, i3 = its channels c0: 1 = a plane [H, W], 3 = packed pixels [H, W, 3]; i4 = its row stride in bytes
+     *    (>= W c0).  p6 = optional uint8 plane [H, W] with row stride i5 >= W: the LAST channel.  i1 = H, i2 = W.  B = c0 + (p6 != 0) bytes
+     *    per pixel = PNG colour type 0 (L), 4 (LA), 2 (RGB), 6 (RGBA) at 8 bits; the channels are interleaved while the rows are filtered.
+     *    L = W B + 1 <= 16384 (CUTIE_PNG_PHOTO_ROW_LIMIT): every match distance lies inside DEFLATE's window and inside what RESIZE flags
+     *    64 | 128 decode; LDS sets no lower limit.  i0, p0, p1, i6, i9 and the floats are unused.  The sources are READ ONLY.
+     *    THE RULE (deterministic, independent of the launch shape):
+     *    1 FILTER.  Raw byte j of a row: x; a = the byte B to the left (0 for j < B); b = the byte above (0 in the first row); c = the byte
+     *      above a.  Residuals mod 256 of the filters 0 .. 4: x | x - a | x - b | x - ((a + b) >> 1) | x - paeth(a, b, c), paeth with
+     *      p = a + b - c: a if |p - a| <= |p - b| and |p - a| <= |p - c|, else b if |p - b| <= |p - c|, else c.  The cost of a filter is
+     *      the sum over the row of |residual read as int8| (0x80 counts 128); the lowest cost wins, ties go to the lower number.  The
+     *      filtered row is the filter number followed by its W B residuals.
+     *    2 TOKENS, on the filtered bytes f of a row, filter byte included; a token never crosses a row.  At byte i:
+     *        n1 = the bytes from i on that equal their left neighbour in the row (0 at i = 0)        distance 1
+     *        nB = the bytes from i on that equal the byte B before them in the row (0 for i < B; only B > 1)     distance B
+     *        nL = the bytes from i on that equal the filtered byte one row up (0 in the first row)   distance L
+     *      each counted up to 261 and no further.  n = max(n1, nB, nL); ties go to distance 1, then B, then L.  n < MINMATCH = 12: a
+     *      literal, one byte.  Else a match of take(n) bytes at that distance, take(n) = n (n <= 258) | n - 3 (259, 260) | 258 (261),
+     *      as flags&8.  (A distance-L match in a block's first row reaches into the block before: the window is continuous.)
+     *    3 BLOCKS.  Rows r with r / 32 equal are one DEFLATE block (R = 32); the last block carries BFINAL.
+     *    4 CODES, per block.  Counts of the literal/length symbols, end-of-block once, and of the distance symbols.  Code lengths of an
+     *      alphabet: the symbols with a count sorted by (count, symbol) ascending; Huffman depths by the in-place two-queue merge over
+     *      that list (Moffat & Katajainen; where a leaf and an inner node weigh the same the leaf is taken); depths above the limit (15;
+     *      7 for the code-length code) are counted at the limit and, while the Kraft sum exceeds 1, one code leaves the limit and the
+     *      longest shorter length that has a code gives one up to make two one level down; then the lengths, shortest first, go to the
+     *      symbols from the END of the sorted list.  One symbol with a count: length 1 (inflate accepts the incomplete distance code);
+     *      none: all zero, HDIST = 1 with one length 0.  Codes are canonical (RFC 1951 3.2.2).  HLIT, HDIST, HCLEN are the smallest legal
+     *      values.  The HLIT + HDIST lengths form one sequence; at position i with value v and r equal values from i on: v == 0 and
+     *      r >= 11: symbol 18 for min(r, 138) | v == 0 and r >= 3: symbol 17 for r | v != 0, i > 0, the value before is v and r >= 3:
+     *      symbol 16 for min(r, 6) | else v itself.  The block is written with the FIXED codes (BTYPE 01) whenever that takes no more
+     *      bits than the dynamic form, header and end-of-block included: so no block exceeds 9 bits per filtered byte + 10.
+     *    5 zlib header 78 01, the blocks, the Adler-32 of the filtered bytes big-endian.
+     *    p3 = stream uint8, 4-byte aligned, i7 = its capacity in bytes (rounded down to a multiple of 4).  ceil((9 H L + 10 ceil(H / 32))
+     *    / 8) + 6 bytes hold any image (OpList.png_photo_capacity).  p4 = status int32 [4], written by the launch: 0 stream bytes, 1
+     *    Adler-32, 2 error bits (1: the stream does not fit the capacity; NOTHING is written to p3 then -- with i7 < 4 it may be null --,
+     *    [0] still says what it needs), 3 zero.  p5 = int32 scratch of i8 words, 16-byte aligned, i8 >= 4 H + 1024 ceil(H / 32) +
+     *    up4(ceil(H L / 4)) + up4(ceil(H L / 2)) (OpList.png_photo_scratch_words); its content before and after means nothing.
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1, c0 other than 1 or 3, L above the row limit, a
+     *    row stride below a row's bytes, 9 H L + 10 ceil(H / 32) + 64 >= 2^31 stream bits, a negative capacity, a null p2, p4, p5 or p3
+     *    (with i7 >= 4), p3 or p4 not 4-byte aligned, p5 not 16-byte aligned, fewer scratch words than needed.
+     *    cutie_amd/inference/utils/png.py assemble_image wraps the stream into a file (signature, IHDR, one IDAT, IEND). */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -756,7 +804,8 @@ int cutie_op_struct_size(void);
  * JPEG decode stages, are present (both came without a new ABI number).  bit 3 (value 8): the mixed forms of the lock-step ops are present.
  * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
  * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present.  bit 7 (value 128):
- * PROB_TO_ID flags == 8192, the polygon trace, is present. */
+ * PROB_TO_ID flags == 8192, the polygon trace, is present.  bit 8 (value 256): PROB_TO_ID flags == 16384, the PNG stream with scanline
+ * filters and dynamic Huffman codes, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

@@ -219,23 +219,9 @@ __global__ void area_down3_kernel(Area3 a) {
     }
 }
 
-// masks f32 [K,H,W] -> m16 f32 [K,h,w]: one wave per output pixel (r*r = 256 inputs, 4 per lane, row-coalesced)
-__global__ void mask_down_mean_kernel(const float* __restrict__ m, float* __restrict__ m16, int K, int H, int W, int r) {
-    int h = H / r, w = W / r;
-    long idx = (long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    if (idx >= (long)K * h * w) return;
-    int ox = idx % w; long t = idx / w; int oy = t % h; int k = t / h;
-    float acc = 0.f;
-    for (int e = lane; e < r * r; e += 64) {
-        int dy = e / r, dx = e - dy * r;
-        acc += m[((long)k * H + oy * r + dy) * W + ox * r + dx];
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) m16[idx] = acc / (float)(r * r);
-}
-// Both steps in one launch: one wave per output pixel walks the K objects (means in object order, then the pairs from the means it
-// has just written).  Same sums in the same order as the two kernels below.
+// masks f32 [K,H,W] -> m16 f32 [K,h,w] (the r x r means) and pair bf16 [K,h,w,ld] = (mask, others, 0...) in one launch: one wave per output
+// pixel walks the K objects (r*r = 256 inputs of an object, 4 per lane, row-coalesced; means in object order, then the pairs from the means
+// it has just written).
 __global__ void mask_down_pair_kernel(const float* __restrict__ m, float* __restrict__ m16, uint4* __restrict__ y, int K, int H, int W, int r,
                                       int ld8) {          // ld8: 16-B units per pixel of y (1 = 8 channels; 8 = 64, channels 8.. stay as they are)
     const int h = H / r, w = W / r, hw = h * w;
@@ -270,24 +256,15 @@ __global__ void mask_down_pair_kernel(const float* __restrict__ m, float* __rest
             y[((long)k * hw + px) * ld8] = make_uint4(pack_bf2(mk, others), 0u, 0u, 0u);
         }
 }
-// m16 f32 [K,hw] -> pair bf16 [K,hw,8] = (mask, others, 0...)
-__global__ void mask_pair_kernel(const float* __restrict__ m16, uint4* __restrict__ y, int K, int hw) {
-    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (long)K * hw) return;
-    int k = idx / hw; int p = idx - (long)k * hw;
-    float sum = 0.f;
-    for (int j = 0; j < K; ++j) sum += m16[(long)j * hw + p];
-    float mk = m16[idx];
-    float others = fminf(fmaxf(sum - mk, 0.f), 1.f);
-    y[idx] = make_uint4(pack_bf2(mk, others), 0u, 0u, 0u);
-}
-
 // ---------------------------------------------------------------------------------------------
 // GAP, two deterministic stages (no float atomics: results are bit-reproducible run to run):
 //  1. grid (ceil(HW/64), B): block 256 = row groups x channel octets over a 64-pixel chunk -> part[b][chunk][c]
 //  2. grid (B): sums the chunks in order and scales by 1/HW
 __global__ __launch_bounds__(256) void gap_partial_kernel(const bf16_t* __restrict__ x, float* __restrict__ part, int HW, int C) {
-    __shared__ float red[2048 + 32];                      // [row group][C + 1]
+    // [row group][C + 1]: nrg = 256 / (C / 8) row groups of C + 1 floats = 2048 + 2048 / C, most at the smallest C the launch check accepts
+    constexpr int GAP_CMIN = 8, GAP_RED = 2048 + 2048 / GAP_CMIN;
+    static_assert((256 / (GAP_CMIN / 8)) * (GAP_CMIN + 1) == GAP_RED, "red holds every row group at C = 8");
+    __shared__ float red[GAP_RED];
     const int b = blockIdx.y, p0 = blockIdx.x * 64;
     const int C8 = C >> 3;
     const int c8 = threadIdx.x % C8, rg = threadIdx.x / C8, nrg = 256 / C8;       // C=256: 32 octets x 8 row groups

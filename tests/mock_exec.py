@@ -168,7 +168,11 @@ class MockExecutor:
     def _op_4(self, flags, i, f, p):
         B, h, w, C = i[:4]
         g = view(p[0], BF16, (B, h, w, C)).float().permute(0, 3, 1, 2)
-        if len(i) > 4 and i[4] > 0:                                     # clips in lock step: one skip map per group of i4 objects, i5 pixels apart
+        if len(i) > 6 and i[6]:                                         # mixed form: i6 = the clips' object counts, clip c adds the map c * i5 pixels on
+            counts = [(i[6] >> (3 * c)) & 7 for c in range(8) if (i[6] >> (3 * c)) & 7]
+            maps = view(p[1], BF16, (len(counts), 2 * h, 2 * w, C), (i[5] * C, 2 * w * C, C, 1)).float()
+            skip = torch.cat([maps[c:c + 1].expand(k, -1, -1, -1) for c, k in enumerate(counts)])
+        elif len(i) > 4 and i[4] > 0:                                     # clips in lock step: one skip map per group of i4 objects, i5 pixels apart
             skip = view(p[1], BF16, (B // i[4], 2 * h, 2 * w, C), (i[5] * C, 2 * w * C, C, 1)).float().repeat_interleave(i[4], 0)
         else:
             skip = view(p[1], BF16, (1, 2 * h, 2 * w, C)).float()
@@ -218,7 +222,7 @@ class MockExecutor:
         B, HW, C = i[:3]
         x = view(p[0], BF16, (B, HW, C)).float()
         nchunk = -(-HW // 64)
-        gap = view(p[1], F32, (B, C))
+        gap = view(p[1], F32, (B, C)) if p[1] else torch.zeros((B, C))     # (gap_out is optional)
         if flags & 1:                                                   # fixed-point sums from the producing conv
             gap.copy_((view(p[5], I64, (B, C)).double() / 16777216.0).float() / HW)
         else:
@@ -253,6 +257,18 @@ class MockExecutor:
 
     def _op_11(self, flags, i, f, p):
         P, h, w = i[:3]
+        if len(i) > 5 and i[5]:                                         # mixed form: clip c has K_c objects, its planes behind those of the clips in front
+            st, ncell = 0, (h // 4) * (w // 4)
+            for c in range(i[4]):
+                k = (i[5] >> (3 * c)) & 7
+                pc = list(p)
+                pc[0], pc[1] = p[0] + 4 * st * h * w, p[1] + 4 * (st + c) * 16 * h * w
+                pc[2] = p[2] + 4 * (st + c) * 16 * h * w if p[2] else 0
+                if flags & 4:
+                    pc[3], pc[4] = p[3] + 4 * st * ncell, p[4] + 2 * st * ncell * i[3]
+                self._op_11(flags, [k + 1, h, w, i[3], 1, 0] + i[6:], f, pc)
+                st += k
+            return
         if len(i) > 4 and i[4] > 1:                                     # clips in lock step: clip by clip with the pointers advanced
             K, ncell = P - 1, (h // 4) * (w // 4)
             for c in range(i[4]):
@@ -278,9 +294,10 @@ class MockExecutor:
             m16 = F.avg_pool2d(prob[1:].unsqueeze(0), 16)[0]
             view(p[3], F32, (K, H // 16, W // 16)).copy_(m16)
             ld = i[3]
-            out = view(p[4], BF16, (K, H // 16, W // 16, 2), ((H // 16) * (W // 16) * ld, (W // 16) * ld, ld, 1))
+            out = view(p[4], BF16, (K, H // 16, W // 16, 8), ((H // 16) * (W // 16) * ld, (W // 16) * ld, ld, 1))
             out[..., 0] = m16
             out[..., 1] = (m16.sum(0, keepdim=True) - m16).clamp(0, 1)
+            out[..., 2:] = 0                                             # (the kernel stores all 8 channels of the pair, like MASK_DOWN)
 
     # ---- MASK_MERGE / AGG_SOFTMAX ----------------------------------------------------------------
     def _op_12(self, flags, i, f, p):

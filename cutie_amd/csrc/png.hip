@@ -21,77 +21,33 @@
 //                         and the last word of a row are shared with its neighbours and are OR-ed in with a vector atomic.
 // The same plane gives the same bytes whatever the launch shape: nothing depends on the order in which rows arrive.
 #include "common.h"
-
-#define PNG_ADLER 65521u
+#include "deflate_enc.h"            // bit writer, symbols, fixed codes, run lengths, the scan body and the shift-out, shared with png_photo.hip
 
 static __host__ __device__ inline int png_row_words(int L) { return (9 * L + 31) / 32 + 2; }      // fixed codes: at most 9 bits per byte
 
-struct PngBits {                        // LSB-first bit writer into 32-bit words (one lane)
-    uint32_t* out;
-    uint64_t acc;
-    int nacc, nwords;
-    __device__ __forceinline__ void put(uint32_t v, int n) {          // n <= 32, nacc < 32
-        acc |= (uint64_t)v << nacc;
-        nacc += n;
-        if (nacc >= 32) {
-            out[nwords++] = (uint32_t)acc;
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-};
-
-__device__ __forceinline__ uint32_t png_rev(uint32_t code, int n) { return __brev(code) >> (32 - n); }   // Huffman codes go MSB first
-
-__device__ __forceinline__ void png_literal(PngBits& b, uint32_t v) {
-    if (v < 144) b.put(png_rev(0x30 + v, 8), 8);
-    else b.put(png_rev(0x190 + (v - 144), 9), 9);
+__device__ __forceinline__ void png_literal(DeBits& b, uint32_t v) {
+    const uint32_t e = de_fixed_lit(v);
+    b.put(e & 0xffffu, (int)(e >> 16));
 }
 
-// length 3..258 (RFC 1951 3.2.5), then the distance code prepared by the caller
-__device__ __forceinline__ void png_match(PngBits& b, int len, uint32_t dbits, int dn) {
-    int sym, eb = 0;
-    uint32_t extra = 0;
-    const int l = len - 3;
-    if (len == 258) sym = 285;
-    else if (l < 8) sym = 257 + l;
-    else {
-        eb = (31 - __clz(l)) - 2;
-        sym = 261 + 4 * eb + ((l >> eb) & 3);
-        extra = l & ((1 << eb) - 1);
-    }
-    const uint32_t code = sym < 280 ? png_rev(sym - 256, 7) : png_rev(0xC0 + (sym - 280), 8);
-    const int cn = sym < 280 ? 7 : 8;
-    b.put(code | (extra << cn), cn + eb);          // <= 13 bits
-    b.put(dbits, dn);                              // <= 18 bits
+// length 3..258 under the fixed codes, then the distance code prepared by the caller
+__device__ __forceinline__ void png_match(DeBits& b, int len, uint32_t dbits, int dn) {
+    int sym, eb;
+    uint32_t extra;
+    de_len_sym(len, sym, eb, extra);
+    const uint32_t e = de_fixed_len(sym);
+    const int cn = (int)(e >> 16);
+    b.put((e & 0xffffu) | (extra << cn), cn + eb);  // <= 13 bits
+    b.put(dbits, dn);                               // <= 18 bits
 }
 
-// distance code + extra bits as one LSB-first field
+// distance symbol under the fixed 5-bit code + extra bits as one LSB-first field
 __device__ __forceinline__ void png_dist(int dist, uint32_t& bits, int& n) {
-    const int d = dist - 1;
-    int code, eb = 0;
-    uint32_t extra = 0;
-    if (d < 4) code = d;
-    else {
-        eb = (31 - __clz(d)) - 1;
-        code = 2 * eb + 2 + ((d >> eb) & 1);
-        extra = d & ((1 << eb) - 1);
-    }
-    bits = png_rev(code, 5) | (extra << 5);
+    int sym, eb;
+    uint32_t extra;
+    de_dist_sym(dist, sym, eb, extra);
+    bits = de_rev((uint32_t)sym, 5) | (extra << 5);
     n = 5 + eb;
-}
-
-// number of set bits of `mask` from bit i on (the masks are zero from bit L on, so a run ends inside the row)
-__device__ __forceinline__ int png_run(const uint64_t* mask, int i, int nmask) {
-    int k = i >> 6;
-    uint64_t z = ~mask[k] >> (i & 63);
-    if (z) return __builtin_ctzll(z);              // (the shifted-in zeros of ~mask are ones of mask only beyond bit 63: handled below)
-    int pos = (k + 1) << 6;
-    for (++k; k < nmask; ++k, pos += 64) {
-        z = ~mask[k];
-        if (z) return pos + __builtin_ctzll(z) - i;
-    }
-    return pos - i;
 }
 
 // A: grid = H rows, block = one wave.  info[r] = {bits, sum of bytes mod 65521, sum of (L - j) * byte_j mod 65521, -}
@@ -99,7 +55,7 @@ extern "C" __global__ __launch_bounds__(64) void png_rows_kernel(const uint8_t* 
                                                                   uint32_t* __restrict__ scratch, int stride) {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int r = blockIdx.x, lane = threadIdx.x;
-    const int L = W + 1, nmask = (L + 63) >> 6;    // (a shift by i & 63 of the last mask word never needs a word behind it)
+    const int L = W + 1, nmask = (L + 63) >> 6;
     uint64_t* mu = (uint64_t*)lds;                 // equal to the byte one row up
     uint64_t* me = mu + nmask + 1;                 // equal to the byte on the left
     uint8_t* cur = (uint8_t*)(me + nmask + 1);     // the filtered row
@@ -128,10 +84,10 @@ extern "C" __global__ __launch_bounds__(64) void png_rows_kernel(const uint8_t* 
     int dn1, dnL;
     png_dist(1, dbits1, dn1);
     png_dist(L, dbitsL, dnL);
-    PngBits b{scratch + (long)r * stride, 0ull, 0, 0};
+    DeBits b{scratch + (long)r * stride, 0ull, 0, 0};
     int i = 0;
     while (i < L) {
-        const int u = png_run(mu, i, nmask), e = i > 0 ? png_run(me, i, nmask) : 0;
+        const int u = de_run<0>(mu, i, nmask), e = i > 0 ? de_run<0>(me, i, nmask) : 0;
         const int n = u >= e ? u : e;
         if (n < 3) {
             const uint32_t v = cur[i];
@@ -139,78 +95,19 @@ extern "C" __global__ __launch_bounds__(64) void png_rows_kernel(const uint8_t* 
             i += 1;
             continue;
         }
-        const int take = n <= 258 ? n : (n - 258 < 3 ? n - 3 : 258);
+        const int take = de_take(n);
         if (u >= e) png_match(b, take, dbitsL, dnL);
         else png_match(b, take, dbits1, dn1);
         i += take;
     }
-    if (b.nacc > 0) b.out[b.nwords] = (uint32_t)b.acc;
-    info[r] = make_int4(b.nwords * 32 + b.nacc, (int)(S % PNG_ADLER), (int)(T % PNG_ADLER), 0);
+    info[r] = make_int4(b.finish(), (int)(S % DE_ADLER), (int)(T % DE_ADLER), 0);
 }
 
-// B: one block.  status = {stream bytes, Adler-32, error bits (1: the stream does not fit the capacity; nothing is written then), 0}
+// B: one block (de_scan): 2 header bytes, 3 bits block header, the rows, 7 bits end-of-block (code 0: the cleared buffer holds it already).
+// Word 0: the zlib header (32K window, no dictionary), then BFINAL = 1, BTYPE = 01
 extern "C" __global__ __launch_bounds__(1024) void png_scan_kernel(int4* __restrict__ info, int H, int W, uint8_t* __restrict__ out, int cap,
                                                                     int* __restrict__ status) {
-    __shared__ uint32_t part[1024];
-    __shared__ uint64_t red[2][16];
-    __shared__ uint32_t carry_s, len_s;
-    const int t = threadIdx.x, L = W + 1;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    uint64_t a = 0, bsum = 0;
-    for (int base = 0; base < H; base += 1024) {
-        const int r = base + t;
-        const int4 v = r < H ? info[r] : make_int4(0, 0, 0, 0);
-        part[t] = (uint32_t)v.x;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {                     // inclusive scan of the 1024 bit counts
-            const uint32_t add = t >= o ? part[t - o] : 0u;
-            __syncthreads();
-            part[t] += add;
-            __syncthreads();
-        }
-        const uint32_t carry = carry_s;
-        if (r < H) {
-            info[r].w = (int)(carry + part[t] - (uint32_t)v.x);  // exclusive bit offset of the row behind the block header
-            a += (uint32_t)v.y;
-            bsum += ((uint64_t)(H - 1 - r) * L % PNG_ADLER) * (uint32_t)v.y % PNG_ADLER + (uint32_t)v.z;
-        }
-        __syncthreads();
-        if (t == 1023) carry_s = carry + part[1023];
-        __syncthreads();
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor((unsigned long long)a, o, 64);
-        bsum += __shfl_xor((unsigned long long)bsum, o, 64);
-    }
-    if ((t & 63) == 0) { red[0][t >> 6] = a; red[1][t >> 6] = bsum; }
-    __syncthreads();
-    if (t == 0) {
-        uint64_t A = 1, B = (uint64_t)H * L % PNG_ADLER;
-        for (int k = 0; k < 16; ++k) { A += red[0][k] % PNG_ADLER; B += red[1][k] % PNG_ADLER; }
-        const uint32_t adler = (uint32_t)(B % PNG_ADLER) << 16 | (uint32_t)(A % PNG_ADLER);
-        // 2 header bytes, 3 bits block header, the rows, 7 bits end-of-block (code 0: the cleared buffer holds it already), 4 bytes Adler-32
-        const uint32_t body = (16u + 3u + carry_s + 7u + 7u) >> 3, len = body + 4u;
-        const bool fits = len <= (uint32_t)cap;
-        status[0] = (int)len;
-        status[1] = (int)adler;
-        status[2] = fits ? 0 : 1;
-        status[3] = 0;
-        len_s = fits ? len : 0u;
-        red[0][0] = adler;
-    }
-    __syncthreads();
-    const uint32_t len = len_s;
-    if (len == 0) return;
-    uint32_t* w = (uint32_t*)out;
-    const uint32_t nw = (len + 3) >> 2;                           // cap is a multiple of 4 (launch check): within the buffer
-    for (uint32_t k = t; k < nw; k += 1024) w[k] = 0u;
-    __syncthreads();
-    if (t == 0) {
-        w[0] = 0x78u | (0x01u << 8) | (3u << 16);                 // zlib header (32K window, no dictionary), then BFINAL = 1, BTYPE = 01
-        const uint32_t adler = (uint32_t)red[0][0];
-        for (int k = 0; k < 4; ++k) out[len - 4 + k] = (uint8_t)(adler >> (24 - 8 * k));
-    }
+    de_scan(info, H, W + 1, 16u + 3u, 7u, 0x78u | (0x01u << 8) | (3u << 16), out, cap, status);
 }
 
 // C: grid = H rows, block = one wave
@@ -221,14 +118,7 @@ extern "C" __global__ __launch_bounds__(64) void png_emit_kernel(const int4* __r
     const int4 v = info[r];
     const uint32_t nbits = (uint32_t)v.x, off = 19u + (uint32_t)v.w;
     if (nbits == 0) return;
-    const uint32_t w0 = off >> 5, w1 = (off + nbits - 1) >> 5, sh = off & 31u, nsrc = (nbits + 31) >> 5;
-    const uint32_t* src = scratch + (long)r * stride;
-    for (uint32_t k = lane; k <= w1 - w0; k += 64) {
-        const uint32_t lo = k < nsrc ? src[k] : 0u, prev = (k > 0 && k - 1 < nsrc) ? src[k - 1] : 0u;
-        const uint32_t val = sh ? (lo << sh) | (prev >> (32 - sh)) : lo;
-        if (k == 0 || k == w1 - w0) atomicOr(out + w0 + k, val);
-        else out[w0 + k] = val;
-    }
+    de_shift_out(scratch + (long)r * stride, (nbits + 31) >> 5, nbits, off, out, lane);
 }
 
 // PROB_TO_ID flags&8.  p2 = ids u8 [H, W] (H, W: the plane as stored, i.e. the output geometry of the id stage), p3 = stream, i7 = capacity,

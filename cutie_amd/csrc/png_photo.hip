@@ -25,8 +25,8 @@
 //                         the shared first and last words are OR-ed in with a vector atomic, as png_emit_kernel does.
 // LDS does not lower the row limit: the emit kernel's image of a row at L = 16384 is 32 KB.
 #include "common.h"
+#include "deflate_enc.h"       // bit writer, symbols, code builder and dynamic header (deflate_enc_core.h), run lengths, scan body, shift-out
 
-#define PPH_ADLER 65521u
 #define PPH_MINMATCH 12        // tests/png_photo_ref.py MINMATCH; the table that chose it: DESIGN.md section 24
 #define PPH_R 32               // rows per DEFLATE block
 #define PPH_RUNCAP 261         // run lengths are counted this far: take() needs no more
@@ -57,39 +57,7 @@ static PphLayout pph_layout(long H, long L) {
     return o;
 }
 
-__device__ __forceinline__ uint32_t pph_rev(uint32_t code, int n) { return n ? __brev(code) >> (32 - n) : 0u; }
-__device__ __forceinline__ int pph_take(int n) { return n <= 258 ? n : (n - 258 < 3 ? n - 3 : 258); }
-
-// length 3 .. 258 -> symbol, extra bits, extra value (RFC 1951 3.2.5)
-__device__ __forceinline__ void pph_len_sym(int len, int& sym, int& eb, uint32_t& extra) {
-    const int l = len - 3;
-    eb = 0;
-    extra = 0;
-    if (len == 258) sym = 285;
-    else if (l < 8) sym = 257 + l;
-    else {
-        eb = (31 - __clz(l)) - 2;
-        sym = 261 + 4 * eb + ((l >> eb) & 3);
-        extra = l & ((1 << eb) - 1);
-    }
-}
-
-__host__ __device__ inline void pph_dist_sym(int dist, int& sym, int& eb, uint32_t& extra) {
-    const int d = dist - 1;
-    eb = 0;
-    extra = 0;
-    if (d < 4) sym = d;
-    else {
-        int hb = 0;
-        while ((d >> (hb + 1)) != 0) ++hb;
-        eb = hb - 1;
-        sym = 2 * eb + 2 + ((d >> eb) & 1);
-        extra = d & ((1 << eb) - 1);
-    }
-}
-
-__device__ __forceinline__ int pph_ll_extra(int s) { return (s < 265 || s == 285) ? 0 : (s - 261) >> 2; }
-__device__ __forceinline__ int pph_d_extra(int s) { return s < 4 ? 0 : (s - 2) >> 1; }
+static_assert(PPH_HDR_WORDS >= DE_HDR_WORDS, "the band's header slot holds any dynamic header");
 
 __device__ __forceinline__ int pph_abs8(uint32_t v) { const int s = (int)(int8_t)(uint8_t)v; return s < 0 ? -s : s; }
 
@@ -151,20 +119,7 @@ extern "C" __global__ __launch_bounds__(64) void pph_filter_kernel(PphSrc S, int
         Ssum += __shfl_xor((unsigned long long)Ssum, o, 64);
         T += __shfl_xor((unsigned long long)T, o, 64);
     }
-    if (lane == 0) info[r] = make_int4(0, (int)(Ssum % PPH_ADLER), (int)(T % PPH_ADLER), 0);
-}
-
-// set bits of `mask` from bit i on, counted up to PPH_RUNCAP (mask[nmask] is a zero word: a run ends inside the row)
-__device__ __forceinline__ int pph_run(const uint64_t* mask, int i, int nmask) {
-    int k = i >> 6;
-    uint64_t z = ~mask[k] >> (i & 63);
-    if (z) return min(__builtin_ctzll(z), PPH_RUNCAP);
-    int pos = (k + 1) << 6;
-    for (++k; k <= nmask && pos - i < PPH_RUNCAP; ++k, pos += 64) {
-        z = ~mask[k];
-        if (z) return min(pos + __builtin_ctzll(z) - i, PPH_RUNCAP);
-    }
-    return min(pos - i, PPH_RUNCAP);
+    if (lane == 0) info[r] = make_int4(0, (int)(Ssum % DE_ADLER), (int)(T % DE_ADLER), 0);
 }
 
 // B: grid = H rows, block = one wave.  tok[r][i]: 0 = no token starts here | 0x8000 literal | 0x8000 | kind << 9 | length (kind 0: distance
@@ -200,12 +155,12 @@ extern "C" __global__ __launch_bounds__(64) void pph_token_kernel(int H, int L, 
         const bool in = i < L;
         int n = 0, kind = 0;
         if (in) {
-            const int n1 = pph_run(m1, i, nmask), nB = pph_run(mB, i, nmask), nL = pph_run(mL, i, nmask);
+            const int n1 = de_run<PPH_RUNCAP>(m1, i, nmask), nB = de_run<PPH_RUNCAP>(mB, i, nmask), nL = de_run<PPH_RUNCAP>(mL, i, nmask);
             n = max(n1, max(nB, nL));
             kind = (n1 >= nB && n1 >= nL) ? 0 : (nB >= nL ? 1 : 2);
         }
         const bool match = in && n >= PPH_MINMATCH;
-        const int step = match ? pph_take(n) : 1;
+        const int step = match ? de_take(n) : 1;
         const uint64_t M = __ballot(match);
         uint64_t starts = 0;
         int cur = entry - base;                                  // >= 0
@@ -226,7 +181,7 @@ extern "C" __global__ __launch_bounds__(64) void pph_token_kernel(int H, int L, 
                 rec |= (uint32_t)kind << 9 | (uint32_t)step;
                 int sym, eb;
                 uint32_t extra;
-                pph_len_sym(step, sym, eb, extra);
+                de_len_sym(step, sym, eb, extra);
                 atomicAdd(&cnt[sym], 1u);
                 atomicAdd(&cnt[PPH_DIST + (kind == 0 ? dsym1 : kind == 1 ? dsymB : dsymL)], 1u);
             } else
@@ -240,83 +195,6 @@ extern "C" __global__ __launch_bounds__(64) void pph_token_kernel(int H, int L, 
         if (cnt[k]) atomicAdd(&g[k], cnt[k]);
 }
 
-struct PphBits {                        // LSB-first bit writer into 32-bit words (one lane); the words are zero before
-    uint32_t* out;
-    uint64_t acc;
-    int nacc, nwords;
-    __device__ __forceinline__ void put(uint32_t v, int n) {          // n <= 16, nacc < 32
-        acc |= (uint64_t)v << nacc;
-        nacc += n;
-        if (nacc >= 32) {
-            out[nwords++] = (uint32_t)acc;
-            acc >>= 32;
-            nacc -= 32;
-        }
-    }
-};
-
-// Code lengths of the n symbols order[0 .. n) whose counts A[0 .. n) ascend (ties by symbol): the in-place two-queue Huffman merge, depths
-// above `limit` folded into it and the Kraft sum repaired, lengths handed out from the end of the list.  num[1 .. limit] = codes per length.
-// One lane.  (The method of Moffat and Katajainen, "In-place calculation of minimum-redundancy codes", 1995.)
-__device__ void pph_lengths(int* A, const int* order, int n, int limit, int* len, int* num) {
-    for (int k = 0; k <= 15; ++k) num[k] = 0;
-    if (n == 0) return;
-    if (n == 1) { len[order[0]] = 1; num[1] = 1; return; }
-    A[0] += A[1];
-    int root = 0, leaf = 2;
-    for (int next = 1; next < n - 1; ++next) {
-        if (leaf >= n || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = next; }
-        else A[next] = A[leaf++];
-        if (leaf >= n || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = next; }
-        else A[next] += A[leaf++];
-    }
-    A[n - 2] = 0;
-    for (int next = n - 3; next >= 0; --next) A[next] = A[A[next]] + 1;
-    int avbl = 1, used = 0, dpth = 0, next = n - 1;
-    root = n - 2;
-    while (avbl > 0) {
-        while (root >= 0 && A[root] == dpth) { ++used; --root; }
-        while (avbl > used) { A[next--] = dpth; --avbl; }
-        avbl = 2 * used;
-        ++dpth;
-        used = 0;
-    }
-    for (int k = 0; k < n; ++k) num[min(A[k], limit)] += 1;
-    uint32_t total = 0;
-    for (int k = 1; k <= limit; ++k) total += (uint32_t)num[k] << (limit - k);
-    while (total > (1u << limit)) {                                 // (a Huffman code is complete: the sum is never below)
-        num[limit] -= 1;
-        for (int k = limit - 1; k > 0; --k)
-            if (num[k]) { num[k] -= 1; num[k + 1] += 2; break; }
-        total -= 1;
-    }
-    int j = n;
-    for (int k = 1; k <= limit; ++k)
-        for (int c = num[k]; c > 0; --c) len[order[--j]] = k;
-}
-
-// the symbols of cnt[0 .. nsym) with a count, sorted by (count, symbol) ascending, by insertion: for the small alphabets.  One lane.
-__device__ int pph_sort_small(const int* cnt, int nsym, int* A, int* order) {
-    int n = 0;
-    for (int s = 0; s < nsym; ++s) {
-        const int c = cnt[s];
-        if (c <= 0) continue;
-        int k = n;
-        while (k > 0 && A[k - 1] > c) { A[k] = A[k - 1]; order[k] = order[k - 1]; --k; }
-        A[k] = c;
-        order[k] = s;
-        ++n;
-    }
-    return n;
-}
-
-__device__ __forceinline__ uint32_t pph_fixed_ll(int s) {       // code | bits << 16, the code already reversed
-    if (s < 144) return pph_rev(0x30 + s, 8) | 8u << 16;
-    if (s < 256) return pph_rev(0x190 + (s - 144), 9) | 9u << 16;
-    if (s < 280) return pph_rev(s - 256, 7) | 7u << 16;
-    return pph_rev(0xC0 + (s - 280), 8) | 8u << 16;
-}
-
 // bits of the token whose record is `rec` at a byte of value `byte`, under the table `tab`
 __device__ __forceinline__ int pph_token_bits(const uint32_t* tab, uint32_t rec, uint32_t byte, int dsym0, int dsym1, int dsym2) {
     if (!(rec & 0x8000u)) return 0;
@@ -325,19 +203,19 @@ __device__ __forceinline__ int pph_token_bits(const uint32_t* tab, uint32_t rec,
     const int kind = (rec >> 9) & 3u;
     int sym, eb;
     uint32_t extra;
-    pph_len_sym(len, sym, eb, extra);
+    de_len_sym(len, sym, eb, extra);
     const int ds = kind == 0 ? dsym0 : kind == 1 ? dsym1 : dsym2;
-    return (int)(tab[sym] >> 16) + eb + (int)(tab[PPH_DIST + ds] >> 16) + pph_d_extra(ds);
+    return (int)(tab[sym] >> 16) + eb + (int)(tab[PPH_DIST + ds] >> 16) + de_d_extra(ds);
 }
 
 // C: grid = bands, block = 256
 extern "C" __global__ __launch_bounds__(256) void pph_codes_kernel(int H, int L, int4* __restrict__ info, uint32_t* __restrict__ band,
                                                                     const uint8_t* __restrict__ filt, const uint16_t* __restrict__ tok,
                                                                     int dsym1, int dsymB, int dsymL) {
-    __shared__ int cnt[PPH_TAB], len[PPH_TAB], A[288], order[288], num[16], dnum[16], clnum[16];
+    __shared__ int cnt[PPH_TAB], len[PPH_TAB], A[DE_NSORT], order[DE_NSORT], num[16], dnum[16], clnum[16];
     __shared__ int clcnt[19], cllen[19], clcode[19], nextc[16], dnext[16];
     __shared__ uint32_t tab[PPH_TAB];
-    __shared__ uint16_t rle[320];                                // symbol | extra value << 5
+    __shared__ uint16_t rle[DE_NRLE];
     __shared__ int n_s, sums[2], rowbits[PPH_R], form_s, hdrbits_s;
     __shared__ uint32_t hdr[PPH_HDR_WORDS];
     const int b = blockIdx.x, t = threadIdx.x;
@@ -365,17 +243,11 @@ extern "C" __global__ __launch_bounds__(256) void pph_codes_kernel(int H, int L,
     }
     __syncthreads();
     if (t == 0) {
-        pph_lengths(A, order, n_s, 15, len, num);
-        const int nd = pph_sort_small(cnt + PPH_DIST, 30, A, order);
-        pph_lengths(A, order, nd, 15, len + PPH_DIST, dnum);
-        nextc[0] = dnext[0] = 0;
-        int code = 0, dcode = 0;
-        for (int k = 1; k <= 15; ++k) {
-            code = (code + num[k - 1]) << 1;
-            dcode = (dcode + dnum[k - 1]) << 1;
-            nextc[k] = code;
-            dnext[k] = dcode;
-        }
+        de_lengths(A, order, n_s, 15, len, num);
+        const int nd = de_sort_small(cnt + PPH_DIST, 30, A, order);
+        de_lengths(A, order, nd, 15, len + PPH_DIST, dnum);
+        de_first_codes(num, 15, nextc);
+        de_first_codes(dnum, 15, dnext);
     }
     __syncthreads();
     // canonical codes: the first code of the length plus the symbols of that length in front
@@ -386,70 +258,22 @@ extern "C" __global__ __launch_bounds__(256) void pph_codes_kernel(int H, int L,
         if (l) {
             int before = 0;
             for (int u = dist ? PPH_DIST : 0; u < s; ++u) before += len[u] == l ? 1 : 0;
-            e = pph_rev((uint32_t)((dist ? dnext[l] : nextc[l]) + before), l) | (uint32_t)l << 16;
+            e = de_rev((uint32_t)((dist ? dnext[l] : nextc[l]) + before), l) | (uint32_t)l << 16;
         }
         tab[s] = e;
         // the two forms' bits of the block's tokens
         const int c = cnt[s];
         if (c > 0 && (s < 286 || dist)) {
-            const int ext = dist ? pph_d_extra(s - PPH_DIST) : pph_ll_extra(s);
-            const int fl = dist ? 5 : (int)(pph_fixed_ll(s) >> 16);
+            const int ext = dist ? de_d_extra(s - PPH_DIST) : de_ll_extra(s);
+            const int fl = dist ? 5 : (int)(de_fixed_ll(s) >> 16);
             atomicAdd(&sums[0], c * (l + ext));
             atomicAdd(&sums[1], c * (fl + ext));
         }
     }
     __syncthreads();
     if (t == 0) {
-        // the HLIT + HDIST lengths as one sequence, in code-length symbols
-        int hlit = 257, hdist = 1;
-        for (int s = 257; s < 286; ++s) if (len[s]) hlit = s + 1;
-        for (int s = 0; s < 30; ++s) if (len[PPH_DIST + s]) hdist = s + 1;
-        const int nseq = hlit + hdist;
-        for (int k = 0; k < 19; ++k) { clcnt[k] = 0; cllen[k] = 0; }
-        int nrle = 0, i = 0, prev = -1;
-        while (i < nseq) {
-            const int v = len[i < hlit ? i : PPH_DIST + (i - hlit)];
-            int run = 1;
-            while (i + run < nseq && run < 138) {
-                const int k = i + run;
-                if (len[k < hlit ? k : PPH_DIST + (k - hlit)] != v) break;
-                ++run;
-            }
-            int tk, sym, extra;
-            if (v == 0 && run >= 11) { tk = run; sym = 18; extra = tk - 11; }
-            else if (v == 0 && run >= 3) { tk = run; sym = 17; extra = tk - 3; }
-            else if (v != 0 && prev == v && run >= 3) { tk = min(run, 6); sym = 16; extra = tk - 3; }
-            else { tk = 1; sym = v; extra = 0; }
-            rle[nrle++] = (uint16_t)(sym | extra << 5);
-            clcnt[sym] += 1;
-            prev = v;
-            i += tk;
-        }
-        const int ncl = pph_sort_small(clcnt, 19, A, order);
-        pph_lengths(A, order, ncl, 7, cllen, clnum);
-        int code = 0, nx[8];
-        nx[0] = 0;
-        for (int k = 1; k <= 7; ++k) { code = (code + clnum[k - 1]) << 1; nx[k] = code; }
-        for (int s = 0; s < 19; ++s) { const int l = cllen[s]; clcode[s] = l ? (int)pph_rev((uint32_t)nx[l]++, l) : 0; }
-        const int ord[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-        int hclen = 4;
-        for (int k = 0; k < 19; ++k) if (cllen[ord[k]]) hclen = max(hclen, k + 1);
         const uint32_t final = r1 == H ? 1u : 0u;
-        PphBits w{hdr, 0ull, 0, 0};
-        w.put(final | 2u << 1, 3);
-        w.put((uint32_t)(hlit - 257), 5);
-        w.put((uint32_t)(hdist - 1), 5);
-        w.put((uint32_t)(hclen - 4), 4);
-        for (int k = 0; k < hclen; ++k) w.put((uint32_t)cllen[ord[k]], 3);
-        for (int k = 0; k < nrle; ++k) {
-            const int sym = rle[k] & 31, extra = rle[k] >> 5;
-            w.put((uint32_t)clcode[sym], cllen[sym]);
-            if (sym == 16) w.put((uint32_t)extra, 2);
-            else if (sym == 17) w.put((uint32_t)extra, 3);
-            else if (sym == 18) w.put((uint32_t)extra, 7);
-        }
-        if (w.nacc > 0) hdr[w.nwords] = (uint32_t)w.acc;
-        const int hbits = w.nwords * 32 + w.nacc;
+        const int hbits = de_dynamic_header(len, len + PPH_DIST, final, A, order, clcnt, cllen, clcode, clnum, rle, hdr).bits;
         const int dyn = hbits + sums[0], fix = 3 + sums[1];
         const bool fixed = fix <= dyn;
         form_s = 2 - (int)((uint32_t)~(dyn - fix) >> 31);          // 1 fixed, 2 dynamic; arithmetic on the sign of dyn - fix (both far below 2^31)
@@ -462,7 +286,7 @@ extern "C" __global__ __launch_bounds__(256) void pph_codes_kernel(int H, int L,
     __syncthreads();
     if (form_s == 1)
         for (int s = t; s < PPH_TAB; s += 256)
-            tab[s] = s < 286 ? pph_fixed_ll(s) : (s >= PPH_DIST && s < PPH_DIST + 30) ? (pph_rev((uint32_t)(s - PPH_DIST), 5) | 5u << 16) : 0u;
+            tab[s] = s < 286 ? de_fixed_ll(s) : (s >= PPH_DIST && s < PPH_DIST + 30) ? (de_rev((uint32_t)(s - PPH_DIST), 5) | 5u << 16) : 0u;
     __syncthreads();
     for (int k = t; k < PPH_TAB; k += 256) g[PPH_TAB + k] = tab[k];
     const int hw = (hdrbits_s + 31) >> 5;
@@ -485,68 +309,11 @@ extern "C" __global__ __launch_bounds__(256) void pph_codes_kernel(int H, int L,
     }
 }
 
-// D: one block.  status = {stream bytes, Adler-32, error bits (1: the stream does not fit the capacity; nothing is written then), 0}
+// D: one block (de_scan): 2 header bytes and the blocks -- their headers and end-of-block codes are counted in the rows' bits.  Word 0: the
+// zlib header (32K window, no dictionary)
 extern "C" __global__ __launch_bounds__(1024) void pph_scan_kernel(int4* __restrict__ info, int H, int L, uint8_t* __restrict__ out, int cap,
                                                                     int* __restrict__ status) {
-    __shared__ uint32_t part[1024];
-    __shared__ uint64_t red[2][16];
-    __shared__ uint32_t carry_s, len_s;
-    const int t = threadIdx.x;
-    if (t == 0) carry_s = 0;
-    __syncthreads();
-    uint64_t a = 0, bsum = 0;
-    for (int base = 0; base < H; base += 1024) {
-        const int r = base + t;
-        const int4 v = r < H ? info[r] : make_int4(0, 0, 0, 0);
-        part[t] = (uint32_t)v.x;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {                     // inclusive scan of the 1024 bit counts
-            const uint32_t add = t >= o ? part[t - o] : 0u;
-            __syncthreads();
-            part[t] += add;
-            __syncthreads();
-        }
-        const uint32_t carry = carry_s;
-        if (r < H) {
-            info[r].w = (int)(carry + part[t] - (uint32_t)v.x);  // exclusive bit offset of the row behind the zlib header
-            a += (uint32_t)v.y;
-            bsum += ((uint64_t)(H - 1 - r) * L % PPH_ADLER) * (uint32_t)v.y % PPH_ADLER + (uint32_t)v.z;
-        }
-        __syncthreads();
-        if (t == 1023) carry_s = carry + part[1023];
-        __syncthreads();
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor((unsigned long long)a, o, 64);
-        bsum += __shfl_xor((unsigned long long)bsum, o, 64);
-    }
-    if ((t & 63) == 0) { red[0][t >> 6] = a; red[1][t >> 6] = bsum; }
-    __syncthreads();
-    if (t == 0) {
-        uint64_t A = 1, B = (uint64_t)H * L % PPH_ADLER;
-        for (int k = 0; k < 16; ++k) { A += red[0][k] % PPH_ADLER; B += red[1][k] % PPH_ADLER; }
-        const uint32_t adler = (uint32_t)(B % PPH_ADLER) << 16 | (uint32_t)(A % PPH_ADLER);
-        const uint32_t body = (16u + carry_s + 7u) >> 3, len = body + 4u;      // 2 header bytes and the blocks, then 4 bytes Adler-32
-        const bool fits = len <= (uint32_t)cap;
-        status[0] = (int)len;
-        status[1] = (int)adler;
-        status[2] = fits ? 0 : 1;
-        status[3] = 0;
-        len_s = fits ? len : 0u;
-        red[0][0] = adler;
-    }
-    __syncthreads();
-    const uint32_t len = len_s;
-    if (len == 0) return;
-    uint32_t* w = (uint32_t*)out;
-    const uint32_t nw = (len + 3) >> 2;                           // cap is a multiple of 4 (launch check): within the buffer
-    for (uint32_t k = t; k < nw; k += 1024) w[k] = 0u;
-    __syncthreads();
-    if (t == 0) {
-        w[0] = 0x78u | (0x01u << 8);                              // zlib header: 32K window, no dictionary
-        const uint32_t adler = (uint32_t)red[0][0];
-        for (int k = 0; k < 4; ++k) out[len - 4 + k] = (uint8_t)(adler >> (24 - 8 * k));
-    }
+    de_scan(info, H, L, 16u, 0u, 0x78u | (0x01u << 8), out, cap, status);
 }
 
 // E: grid = H rows, block = one wave.  LDS: the band's table, then the row's image
@@ -591,7 +358,7 @@ extern "C" __global__ __launch_bounds__(64) void pph_emit_kernel(const int4* __r
                 const int kind = (rec >> 9) & 3u;
                 int sym, eb;
                 uint32_t extra;
-                pph_len_sym(len, sym, eb, extra);
+                de_len_sym(len, sym, eb, extra);
                 const uint32_t e1 = tab[sym];
                 val = e1 & 0xffffu;
                 nb = (int)(e1 >> 16);
@@ -602,7 +369,7 @@ extern "C" __global__ __launch_bounds__(64) void pph_emit_kernel(const int4* __r
                 val |= (uint64_t)(e2 & 0xffffu) << nb;
                 nb += (int)(e2 >> 16);
                 val |= (uint64_t)(kind == 0 ? dex1 : kind == 1 ? dexB : dexL) << nb;
-                nb += pph_d_extra(ds);                            // <= 15 + 5 + 15 + 13 = 48 bits
+                nb += de_d_extra(ds);                            // <= 15 + 5 + 15 + 13 = 48 bits
             }
         }
         int incl = nb;
@@ -627,13 +394,7 @@ extern "C" __global__ __launch_bounds__(64) void pph_emit_kernel(const int4* __r
     }
     __syncthreads();
     if (nbits == 0) return;
-    const uint32_t w0 = off >> 5, w1 = (off + nbits - 1) >> 5, sh = off & 31u;
-    for (uint32_t k = lane; k <= w1 - w0; k += 64) {
-        const uint32_t lo = k < nsrc ? img[k] : 0u, prev = (k > 0 && k - 1 < nsrc) ? img[k - 1] : 0u;
-        const uint32_t val = sh ? (lo << sh) | (prev >> (32 - sh)) : lo;
-        if (k == 0 || k == w1 - w0) atomicOr(out + w0 + k, val);
-        else out[w0 + k] = val;
-    }
+    de_shift_out(img, nsrc, nbits, off, out, lane);
 }
 
 // PROB_TO_ID flags == 16384 (slots: include/cutie_hip.h).  p2 = first source u8 ([H, W] or [H, W, 3], i3 = its channels, i4 = its row stride
@@ -666,9 +427,9 @@ int launch_png_photo(const cutie_op* op, hipStream_t s) {
     PphSrc S{(const uint8_t*)p[2], (const uint8_t*)p[6], c0, B, ld0, ld1};
     int ds[3], deb[3];
     uint32_t dex[3];
-    pph_dist_sym(1, ds[0], deb[0], dex[0]);
-    pph_dist_sym(B, ds[1], deb[1], dex[1]);
-    pph_dist_sym((int)L, ds[2], deb[2], dex[2]);
+    de_dist_sym(1, ds[0], deb[0], dex[0]);
+    de_dist_sym(B, ds[1], deb[1], dex[1]);
+    de_dist_sym((int)L, ds[2], deb[2], dex[2]);
     const int nmask = (int)((L + 63) >> 6);
     const size_t lds_tok = (size_t)(3 * (nmask + 1)) * 8 + PPH_TAB * 4;
     const int imgwords = (int)((15 * L + 15 + 31) / 32) + PPH_HDR_WORDS + 4;     // a token costs at most 15 bits per byte it covers

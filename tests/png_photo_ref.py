@@ -298,6 +298,27 @@ def _pack(vals, lens) -> bytes:
     return np.packbits(bits[keep], bitorder='little').tobytes()
 
 
+def _band_counts(filt, toks, dsyms, rows):
+    """Counts of the literal/length symbols (end-of-block once) and of the distance symbols over the rows of one block."""
+    ll = np.zeros(286, np.int64)
+    dd = np.zeros(30, np.int64)
+    for r in rows:
+        st, kd, ln = toks[r]
+        lit = kd < 0
+        ll[:256] += np.bincount(filt[r][st[lit]], minlength=256)
+        ll[257:] += np.bincount(_LEN_SYM[ln[~lit]], minlength=29)
+        for k in range(3):
+            dd[dsyms[k][0]] += int((kd == k).sum())
+    ll[256] = 1
+    return ll, dd
+
+
+def band_counts(e, band: int = R):
+    """[(ll, dd, final)] per block of an encode() result: the counts its codes were built from."""
+    H, dsyms = e['H'], [dist_code(d) for d in (1, e['B'], e['L'])]
+    return [_band_counts(e['filtered'], e['tokens'], dsyms, range(b0, min(b0 + band, H))) + (min(b0 + band, H) == H,) for b0 in range(0, H, band)]
+
+
 def encode(src0, src1=None, *, minmatch: int = MINMATCH, band: int = R, want_bytes: bool = True):
     """-> dict: stream (bytes, exactly the device's), adler, filtered [H, L], filters [H], forms (per block: 'fixed' | 'dynamic'), bits (per
     block), tokens (per row).  ``minmatch`` / ``band`` other than the constants and want_bytes=False are for the size tables only."""
@@ -310,16 +331,7 @@ def encode(src0, src1=None, *, minmatch: int = MINMATCH, band: int = R, want_byt
     for b0 in range(0, H, band):
         rows = range(b0, min(b0 + band, H))
         final = rows[-1] == H - 1
-        ll = np.zeros(286, np.int64)
-        dd = np.zeros(30, np.int64)
-        for r in rows:
-            st, kd, ln = toks[r]
-            lit = kd < 0
-            ll[:256] += np.bincount(filt[r][st[lit]], minlength=256)
-            ll[257:] += np.bincount(_LEN_SYM[ln[~lit]], minlength=29)
-            for k in range(3):
-                dd[dsyms[k][0]] += int((kd == k).sum())
-        ll[256] = 1
+        ll, dd = _band_counts(filt, toks, dsyms, rows)
         ll_len, d_len = code_lengths(ll, 15), code_lengths(dd, 15)
         hdr, _ = dynamic_header(ll_len, d_len, final)
         ll_ext = np.zeros(286, np.int64)

@@ -5,6 +5,8 @@ the parser through the descriptor interpreter (tests/mock_exec_png_photo.py)."""
 import io
 import glob
 import os
+import shutil
+import subprocess
 import zlib
 
 import numpy as np
@@ -182,10 +184,134 @@ def test_degenerate_alphabets():
 
 def test_code_length_code_limit_search():
     """No seeded plane of 64 x 256 or below was found whose code-length code passes 7 bits before limiting (C.CL_SEED is None; DESIGN.md
-    section 24): the function-level check above covers the limiter.  Should a seed be committed, its plane must need the limit."""
+    section 24): the function-level check above covers the model's limiter, and test_encoder_core_under_sanitizers below executes the
+    shipped one (csrc/deflate_enc_core.h) at limit 7 on the host, from count vectors.  Should a seed be committed, its plane must need
+    the limit."""
     if C.CL_SEED is not None:
         e = P.encode(C.cl_candidate(C.CL_SEED))
         assert zlib.decompress(e['stream']) == e['filtered'].tobytes()
+
+
+# ---- the shipped code builder on the host ---------------------------------------------------------------------------------------------
+CL_DEEP_SEEDS = (0, 2, 3)          # _split_counts(seed): literal/length counts whose code-length code is 8 deep before limiting
+
+
+def _host_compiler():
+    for cc in (os.environ.get('CXX'), 'c++', 'g++', 'clang++'):
+        if cc and shutil.which(cc):
+            return shutil.which(cc)
+    return None
+
+
+def _split_counts(seed):
+    """A complete prefix code grown by splitting leaves (a random one or the deepest, by a coin), every symbol counted 2^(15 - length) so
+    that Huffman gives those lengths back: many lengths with skewed frequencies of their own, which is what deepens the code-length code."""
+    rng = np.random.default_rng(seed)
+    leaves, n = [0], int(rng.integers(20, 287))
+    while len(leaves) < n:
+        ok = [k for k, d in enumerate(leaves) if d < 15]
+        k = ok[int(rng.integers(len(ok)))] if rng.random() < 0.5 else max(ok, key=lambda k: leaves[k])
+        d = leaves.pop(k)
+        leaves += [d + 1, d + 1]
+    ll = np.zeros(286, np.int64)
+    ll[rng.permutation(286)[:n]] = [1 << (15 - d) for d in leaves]
+    return ll
+
+
+def _cl_counts(ll_len, d_len):
+    _, (hlit, hdist, _, _) = P.dynamic_header(ll_len, d_len, True)
+    cl_cnt = np.zeros(19, np.int64)
+    for s, _, _ in P.rle_lengths(list(ll_len[:hlit]) + list(d_len[:hdist])):
+        cl_cnt[s] += 1
+    return cl_cnt
+
+
+def _random_counts(rng, kind, n):
+    if kind == 'uniform':
+        return rng.integers(0, 50, n)
+    if kind == 'sparse':
+        return rng.integers(0, 3, n) // 2 * rng.integers(1, 100000, n)
+    if kind == 'fibonacci':                                                      # a + b of the two before, jittered, in a random order
+        v = [1, 1]
+        while len(v) < min(n, 40):
+            v.append(v[-1] + v[-2] + int(rng.integers(0, 2)))
+        out = np.zeros(n, np.int64)
+        out[rng.permutation(n)[:len(v)]] = v
+        return out
+    return rng.permutation((1 << np.minimum(np.arange(n), 20) // int(rng.integers(1, 4))).astype(np.int64))    # geometric
+
+
+def test_encoder_core_under_sanitizers(tmp_path):
+    """png_enc_host.cpp = the encoders' scalar core (csrc/deflate_enc_core.h) with its own main, built with -fsanitize=address,undefined,
+    every work array a heap block of the kernel's size: the counts of every block of the corpus, the degenerate alphabets, count vectors
+    that need the limiter at 15 and at 7 (the code-length code's: seeded vectors, asserted to need it) and every length and distance go
+    through it on the CPU; its lengths, codes and header bytes equal the model's."""
+    cc = _host_compiler()
+    if cc is None:
+        pytest.skip('no host C++ compiler')
+    exe = str(tmp_path / 'png_enc_host')
+    subprocess.run([cc, '-O1', '-g', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
+                    os.path.join(HERE, '..', 'cutie_amd', 'csrc', 'png_enc_host.cpp'), '-o', exe], check=True)
+    fib = [1, 1]
+    while len(fib) < 30:
+        fib.append(fib[-1] + fib[-2])
+    none = np.zeros(30, np.int64)
+    eob = np.zeros(286, np.int64)
+    eob[256] = 1
+    two = eob.copy()
+    two[65] = 9
+    blocks = [(name, ll, dd, final) for name in C.corpus() for ll, dd, final in P.band_counts(C.encoded(name))]
+    assert len(blocks) >= len(C.corpus()) and any(not dd.any() for _, _, dd, _ in blocks)                 # a block without any distance symbol
+    blocks += [('one symbol', eob, none, True), ('two symbols', two, none, False)]
+    blocks.append(('no distance symbol', np.bincount(C.corpus()['noise'][0].ravel(), minlength=286) + eob, none, True))
+    for seed in CL_DEEP_SEEDS:
+        ll = _split_counts(seed)
+        assert P.code_lengths(_cl_counts(P.code_lengths(ll, 15), none), 40).max() > 7, seed            # the case keeps covering the limiter
+        blocks.append((f'deep code-length code {seed}', ll, none, True))
+    deep = sum(P.code_lengths(_cl_counts(P.code_lengths(ll, 15), P.code_lengths(dd, 15)), 40).max() > 7 for _, ll, dd, _ in blocks)
+    assert deep >= len(CL_DEEP_SEEDS)                                                                     # (ramp_avg's block is one more)
+    vectors = [(7, fib[:19]), (15, fib[:30]), (7, [0, 4, 0]), (15, [0, 4, 0]), (7, [3, 0, 4]), (15, [3, 0, 4]), (15, [0] * 30)]
+    assert P.code_lengths(fib[:19], 40).max() == 18 and P.code_lengths(fib[:30], 40).max() == 29
+    rng = np.random.default_rng(11)
+    limited = {7: 0, 15: 0}
+    for kind in ('uniform', 'sparse', 'fibonacci', 'geometric'):
+        for n, limit in ((19, 7), (30, 7), (19, 15), (30, 15), (286, 15)):
+            for _ in range(20):
+                counts = [int(v) for v in _random_counts(rng, kind, n)]
+                vectors.append((limit, counts))
+                limited[limit] += int(P.code_lengths(counts, 40).max() > limit)
+    assert len(vectors) >= 400 and limited[7] > 0 and limited[15] > 0, limited
+    records = tmp_path / 'records.txt'
+    with open(records, 'w') as f:
+        for _, ll, dd, final in blocks:
+            f.write('H %d %s %s\n' % (final, ' '.join(map(str, ll.tolist())), ' '.join(map(str, dd.tolist()))))
+        for limit, counts in vectors:
+            f.write('L %d %d %s\n' % (limit, len(counts), ' '.join(map(str, counts))))
+        f.write('S\n')
+    run = subprocess.run([exe, str(records)], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and run.stderr == '', run.stderr[-2000:]
+    lines = [ln.split() for ln in run.stdout.splitlines()]
+    assert len(lines) == 7 * len(blocks) + len(vectors) + 7
+    ints = lambda ln, tag: [int(v) for v in ln[1:]] if ln[0] == tag else pytest.fail(f'{ln[0]} where {tag} was expected')   # noqa: E731
+    for k, (name, ll, dd, final) in enumerate(blocks):
+        got = lines[7 * k:7 * k + 7]
+        ll_len, d_len = P.code_lengths(ll, 15), P.code_lengths(dd, 15)
+        assert ints(got[0], 'll') == ll_len.tolist() and ints(got[1], 'dd') == d_len.tolist(), name
+        assert ints(got[2], 'llcode') == P.canonical(ll_len).tolist() and ints(got[3], 'dcode') == P.canonical(d_len).tolist(), name
+        hdr, (hlit, hdist, hclen, cl_len) = P.dynamic_header(ll_len, d_len, final)
+        assert got[4][0] == 'hdr' and int(got[4][1]) == sum(n for _, n in hdr), name
+        assert got[4][2] == P._pack([v for v, _ in hdr], [n for _, n in hdr]).hex(), name
+        assert ints(got[5], 'h') == [hlit, hdist, hclen] and ints(got[6], 'cl') == cl_len.tolist(), name
+    for (limit, counts), ln in zip(vectors, lines[7 * len(blocks):]):
+        assert ints(ln, 'len') == P.code_lengths(counts, limit).tolist(), (limit, counts)
+    sym = dict((ln[0], [int(v) for v in ln[1:]]) for ln in lines[-7:])
+    assert sym['lensym'] == [v for n in range(3, 259) for v in (257 + int(P._LEN_SYM[n]), int(P._LEN_EB[n]), int(P._LEN_EX[n]))]
+    assert sym['distsym'] == [v for d in range(1, 32769) for v in P.dist_code(d)]
+    assert sym['take'] == [P.take(n) for n in range(601)]
+    d_ext = dict(P.dist_code(d)[:2] for d in range(1, 32769))
+    assert sym['llextra'] == [0] * 257 + P.LEXT and sym['dextra'] == [d_ext[s] for s in range(30)]
+    fixed = P.canonical(list(P.FIXED_LL) + [8, 8])[:286]
+    assert sym['fixed'] == [int(v) for s in range(286) for v in (fixed[s], P.FIXED_LL[s])] and sym['rev0'] == [0]
 
 
 # ---- sizes ------------------------------------------------------------------------------------------------------------------------------

@@ -271,6 +271,8 @@ int launch_bank(const cutie_op* op, hipStream_t s) {
     switch (op->kind) {
         case CUTIE_OP_RANK_SELECT: {
             if (!p[3]) { cutie_set_error("rank_select: needs its partial-rank scratch (p3, %d x n ints)", RS_SPLIT); return -2; }
+            // (k > n would leave order[n .. k) and the gathered rows behind them as they were: torch.topk raises there)
+            if (i[0] < 1 || i[1] > i[0]) { cutie_set_error("rank_select: k=%d of n=%d elements (needs 1 <= n and k <= n)", i[1], i[0]); return -2; }
             RankSide sd = {{(const uint32_t*)p[4], (const uint32_t*)p[6]}, {(uint32_t*)p[5], (uint32_t*)p[7]}, {i[2], i[3]}, (uint32_t*)p[8], i[4]};
             if ((p[4] && (i[2] & 3)) || (p[6] && (i[3] & 3))) { cutie_set_error("rank_select: gathered rows must be whole 16-B words"); return -2; }
             const int nb = (i[0] + 255) / 256;

@@ -1246,7 +1246,8 @@ __global__ void axpy_kernel(const float* __restrict__ x, float* __restrict__ y, 
 }
 // life counters of up to two token ranges advance by one; optionally use[i] += delta[i] (the usage a look-ahead read-out parked
 // in a side buffer, applied when -- and only when -- that read-out is consumed)
-// dfx & 1: delta holds unsigned 64-bit fixed-point sums (2^-40, AFF_READOUT flags&1): converted with one rounding; dfx & 2: and is cleared behind it
+// dfx & 1: delta holds unsigned 64-bit fixed-point sums (2^-40, AFF_READOUT flags&1): converted with one rounding -- u64 -> f32 rounds once
+// for every d, the power of two behind it is exact (a detour through double rounds a second time from d = 2^53); dfx & 2: and is cleared behind it
 __global__ void tick_kernel(float* lifeA, long nA, float* lifeB, long nB, float* use, float* delta, long nU, int dfx) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (lifeA && i < nA) lifeA[i] += 1.f;
@@ -1254,7 +1255,7 @@ __global__ void tick_kernel(float* lifeA, long nA, float* lifeB, long nB, float*
     if (use && i < nU) {
         if (dfx & 1) {
             unsigned long long* d = reinterpret_cast<unsigned long long*>(delta);
-            use[i] += (float)((double)d[i] * 9.094947017729282e-13);
+            use[i] += (float)d[i] * 0x1p-40f;
             if (dfx & 2) d[i] = 0ull;
         } else use[i] += delta[i];
     }

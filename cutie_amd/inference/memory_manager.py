@@ -777,6 +777,11 @@ class MemoryManager:
         n = b.n_work - self.min_work_tokens            # candidates: the oldest working tokens
         if n <= 0:
             return
+        if n < P:
+            # the reference raises at this point (torch.topk, memory_manager.py:339); ranking k > n would leave the rest of the order, and the
+            # prototypes built from it, to whatever an earlier consolidation left in the buffers
+            raise RuntimeError(f'long-term consolidation: selected index k out of range: n={n} candidate tokens for num_prototypes={P} '
+                               f'({HW} tokens per memory frame)')
         if b.n_long + P > b.L:
             self._fit_bucket(b)
         assert b.n_long + P <= b.L, ('long-term region overrun', b.n_long, P, b.L)

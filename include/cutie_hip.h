@@ -303,7 +303,8 @@ enum {
     /* USAGE_TICK: life[i] += 1 for i in [0,n)   kv_memory_store.py:161  p0=life  i: 0 n
      * optional (0 = none): p1=life2 f32 [i1]: += 1;  p2=use f32 [i2], p3=delta f32 [i2]: use += delta (the usage of a
      * look-ahead read-out, accumulated into a side buffer by AFF_READOUT and applied when the read-out is consumed)
-     * ABI 4: flags&1 = p3 holds unsigned 64-bit fixed-point sums (2^-40, AFF_READOUT flags&1), converted with one rounding; flags&2 = and is
+     * ABI 4: flags&1 = p3 holds unsigned 64-bit fixed-point sums (2^-40, AFF_READOUT flags&1), converted with one rounding for every 64-bit
+     *      value (the correctly rounded fp32 of d / 2^40: u64 -> f32, then an exact power of two); flags&2 = and is
      *      cleared behind the addition (the side counters of a read-out that is always consumed) */
     CUTIE_OP_USAGE_TICK = 30,
     /* RANK_SELECT: order[r] = index of the r-th largest of use/life (ties -> lower index), r < k
@@ -312,7 +313,8 @@ enum {
      * optional side jobs of the scattering launch: p4/p5, p6/p7 = src/dst of up to two row gathers dst[r,:] = src[order[r],:]
      * (rows of i2 / i3 32-bit words, multiples of 4: the prototype keys / selections of memory_manager.py:341-345);
      * p8 = u32 buffer of i4 words cleared (the column maxima of CONSOL_AFF)
-     * i: 0 n 1 k 2 row words of gather 1 3 row words of gather 2 4 words to clear */
+     * i: 0 n 1 k 2 row words of gather 1 3 row words of gather 2 4 words to clear
+     * refused: n < 1 and k > n (order[n .. k) would keep what an earlier call left there; torch.topk raises) */
     CUTIE_OP_RANK_SELECT = 31,
     /* GATHER_ROWS: dst[r,:] = src[order[r],:]   p0=src p1=order i32 p2=dst  i: 0 k 1 rowbytes 2 src_stride 3 dst_stride */
     CUTIE_OP_GATHER_ROWS = 32,

@@ -44,6 +44,17 @@ def view(ptr, dtype, shape, strides=None):
     return t.as_strided(shape, strides)
 
 
+def fx40_to_f32(d):
+    """The correctly rounded fp32 of d / 2^40 for unsigned 64-bit counters (an int64 tensor holding their bits), in integer arithmetic:
+    below 2^53 the double is exact and its conversion the one rounding; from there the low 11 bits are folded into a sticky bit first, which lies
+    far below fp32's rounding position, so the double is again exact and decides the same way as the full integer."""
+    u = d.contiguous().numpy().view(np.uint64)
+    big = u >= np.uint64(1 << 53)
+    t = np.where(big, (u >> np.uint64(11)) | ((u & np.uint64(0x7ff)) != 0).astype(np.uint64), u)
+    f = t.astype(np.float64).astype(np.float32) * np.where(big, np.float32(2048.0), np.float32(1.0))
+    return torch.from_numpy(f * np.float32(2.0 ** -40))
+
+
 def _act(v, code):
     if code == O.ACT_RELU:
         return F.relu(v)
@@ -692,7 +703,7 @@ class MockExecutor:
         if p[1] and i[1] > 0:
             view(p[1], F32, (i[1],)).add_(1.0)
         if p[2] and p[3] and i[2] > 0 and (flags & 1):                   # delta: unsigned 64-bit fixed point (2^-40), one rounding
-            view(p[2], F32, (i[2],)).add_((view(p[3], U64, (i[2],)).double() * 2.0 ** -40).float())
+            view(p[2], F32, (i[2],)).add_(fx40_to_f32(view(p[3], U64, (i[2],))))
             if flags & 2:
                 view(p[3], U64, (i[2],)).zero_()
         elif p[2] and p[3] and i[2] > 0:
@@ -700,6 +711,8 @@ class MockExecutor:
 
     def _op_31(self, flags, i, f, p):
         n, k = i[:2]
+        if n < 1 or k > n:
+            raise RuntimeError(f'rank_select: k={k} of n={n} elements (needs 1 <= n and k <= n)')
         u = view(p[0], F32, (n,)) / view(p[1], F32, (n,))
         order = sorted(range(n), key=lambda t: (-float(u[t]), t))[:k]
         order_t = torch.tensor(order, dtype=torch.int32)
@@ -719,8 +732,8 @@ class MockExecutor:
         view(p[2], U8, (k, rb), (ds, 1)).copy_(src[order])
 
     def _op_33(self, flags, i, f, p):
-        """CONSOL_AFF: S[p, i] = similarity of candidate i and prototype p, -inf in the padding up to ldS (the column maxima p5 are an
-        internal hand-over to CONSOL_READ: the interpreter's CONSOL_READ takes its maxima from S)."""
+        """CONSOL_AFF: S[p, i] = similarity of candidate i and prototype p, -inf in the padding up to ldS; the column maxima p5 as
+        order-preserving keys, raised over what the buffer holds (the interpreter's CONSOL_READ takes its maxima from S)."""
         n, P, ldS = i[:3]
         ck, cs = view(p[0], F32, (n, 64)), view(p[1], F32, (n,))
         pk, pe = view(p[2], F32, (P, 64)), view(p[3], F32, (P, 64))
@@ -731,6 +744,10 @@ class MockExecutor:
         S = view(p[4], F32, (P, ldS))
         S.fill_(float('-inf'))
         S[:, :n] = sim.t()
+        if p[5]:
+            cm = view(p[5], I32, (P,)).numpy().view(np.uint32)
+            b = S[:, :n].max(1).values.contiguous().numpy().view(np.uint32)
+            np.maximum(cm, np.where(b >> 31, ~b, b | np.uint32(0x80000000)), out=cm)
 
     def _op_34(self, flags, i, f, p):
         """CONSOL_READ: softmax over the candidates, applied to every object's values and to the shrinkage."""

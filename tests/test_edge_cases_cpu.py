@@ -47,6 +47,31 @@ def test_product_reproduces_reference_outcome(name, product_net):
     assert got == want, (name, got, want)
 
 
+@pytest.mark.filterwarnings('ignore:Leaking:UserWarning')           # (the step that raises leaves its frame in the feature store, as above)
+def test_consolidation_with_fewer_candidates_than_prototypes_raises(product_net):
+    """An 80 x 112 clip has 35 stride-16 cells; with 3 / 2 memory frames a consolidation has 35 candidates for 64 prototypes.  The reference
+    raises there (torch.topk, "selected index k out of range", memory_manager.py:339; oracle/inference.py:362 likewise); RANK_SELECT with
+    k > n would leave the rest of the order, and the prototypes built from it, to whatever an earlier call left in the buffers.  With 8
+    prototypes the same clip consolidates."""
+    import torch
+    from cutie_amd.inference.inference_core import InferenceCore
+    from cutie_amd.utils.synth import SyntheticClip
+    from oracle.scenarios import LT_SMALL
+
+    def run(P):
+        lt = dict(LT_SMALL, max_mem_frames=3, min_mem_frames=2, num_prototypes=P, max_num_tokens=400, buffer_tokens=100)
+        p, c = InferenceCore(product_net, cfg=default_config(mem_every=1, use_long_term=True, long_term=lt)), SyntheticClip(80, 112, 3, 6, seed=7)
+        with torch.inference_mode():
+            p.step(c.frame(0), c.first_mask(), objects=[1, 2, 3])
+            for t in range(1, 6):
+                p.step(c.frame(t))
+        return p
+
+    with pytest.raises(RuntimeError, match=r'n=35 .*num_prototypes=64'):
+        run(64)
+    assert max(b.n_long for b in run(8).memory.buckets.values()) >= 8
+
+
 @pytest.mark.parametrize('name', sorted(CASES))
 def test_oracle_reproduces_reference_outcome(name, oracle_net):
     got = run_case(name, lambda over: OracleProcessor(oracle_net, dict(DEFAULT_CFG, **over)))

@@ -114,6 +114,13 @@ def has_png_photo():
     return bool(load().cutie_hip_build_flags() & 256)
 
 
+def has_guided_filter():
+    """Does the loaded library know PROB_TO_ID flags == 32768, the colour guided filter of uint8 planes under the frame?  Added without a
+    new ABI number; a library from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing
+    (OpList.guided_filter; ResultSaver matte_refine=)."""
+    return bool(load().cutie_hip_build_flags() & 512)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

@@ -136,8 +136,9 @@ int cutie_hip_build_flags(void) {
     // bit 1: RESIZE flags 64 / 128, the PNG decode stages; bit 2: RESIZE flags 256, the batch forms of the JPEG decode (ABI 11, forms added);
     // bit 3: the mixed forms of the lock-step ops (clips with different object counts); bit 4: PROB_TO_ID flags == 1024, the track statistics;
     // bit 5: PROB_TO_ID flags == 2048, the region filter; bit 6: PROB_TO_ID flags == 4096, the distance transform and its bands;
-    // bit 7: PROB_TO_ID flags == 8192, the polygon trace; bit 8: PROB_TO_ID flags == 16384, the filtered PNG stream with dynamic codes
-    const int forms = 2 | 4 | 8 | 16 | 32 | 64 | 128 | 256;
+    // bit 7: PROB_TO_ID flags == 8192, the polygon trace; bit 8: PROB_TO_ID flags == 16384, the filtered PNG stream with dynamic codes;
+    // bit 9: PROB_TO_ID flags == 32768, the colour guided filter
+    const int forms = 2 | 4 | 8 | 16 | 32 | 64 | 128 | 256 | 512;
 #ifdef CUTIE_DIAG
     return forms | 1;
 #else

@@ -169,7 +169,8 @@ class ResultSaver:
                  save_scores=False, score_output_root=None, visualize_output_root=None, visualize=False, init_json=None,
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
                  target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8,
-                 trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None, cutout=False, png_codes='fixed'):
+                 trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None, cutout=False, png_codes='fixed',
+                 matte_refine=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -216,7 +217,36 @@ class ResultSaver:
         (one warning).  Needs ``processor``; a ``use_long_id`` saver and ``process_merged`` refuse it.
         ``png_codes``: 'fixed' (default: the soft masks and the alpha matte go through the id planes' encoder, as before) | 'dynamic'
         (they are encoded by the filtered, dynamic-Huffman stage with one byte per pixel: the same pixels in fewer bytes).  The id
-        masks, trimaps and dilated masks never change encoder."""
+        masks, trimaps and dilated masks never change encoder.
+        ``matte_refine``: None (default: no launch, the same bytes) | (r, eps) -- the matte plane (``alpha_matte``, the A channel of
+        ``cutout``) and, with ``soft_masks``, the K object planes go through the colour guided filter (PROB_TO_ID flags == 32768; DESIGN.md
+        section 25) with the uint8 frame as the guide before the PNG stages read them: radius r (1 .. 64 pixels of the output frame), eps
+        (1e-6 .. 1) in units of the frame scaled to [0, 1].  The planes of a frame share one launch, up to 16 of them.  The 'popup' and
+        'layer' JPEGs keep their bytes: they are composed from the float planes inside their own launch.  The id masks, trimaps and
+        dilated masks are untouched.  Needs one of ``alpha_matte`` / ``cutout`` / ``soft_masks`` and the ``processor``; a ``use_long_id``
+        saver and ``process_merged`` refuse it."""
+        if matte_refine is not None:
+            from ... import ops as O
+            try:
+                r, eps = matte_refine
+                ok = int(r) == r and not isinstance(r, bool)
+                r, eps = int(r), float(eps)
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise ValueError(f'matte_refine is None or (radius, eps), an int and a float, not {matte_refine!r}')
+            if not 1 <= r <= O.OpList.GUIDED_MAX_RADIUS:
+                raise ValueError(f'matte_refine: radius {r}, 1 .. {O.OpList.GUIDED_MAX_RADIUS}')
+            if not O.OpList.GUIDED_EPS_MIN <= eps <= O.OpList.GUIDED_EPS_MAX:
+                raise ValueError(f'matte_refine: eps {eps}, {O.OpList.GUIDED_EPS_MIN} .. {O.OpList.GUIDED_EPS_MAX}')
+            if not (alpha_matte or cutout or soft_masks):
+                raise ValueError('matte_refine refines the planes of alpha_matte, cutout and soft_masks: none of them is set')
+            if use_long_id:
+                raise ValueError('matte_refine: the matte outputs are composed from uint8 id planes; a use_long_id saver (RGB masks) cannot write them')
+            if processor is None:
+                raise ValueError('matte_refine needs the processor (its device)')
+            matte_refine = (r, eps)
+        self.matte_refine = matte_refine
         if png_codes not in PNG_CODES:
             raise ValueError(f'png_codes must be one of {PNG_CODES}, not {png_codes!r}')
         self.cutout, self.png_codes = bool(cutout), png_codes
@@ -720,7 +750,10 @@ class ResultSaver:
                 self._cutout_warned = True
                 log.warning(f'cut-outs: a row of {W} RGBA pixels is beyond the device PNG stage\'s limit of {O.OpList.PNG_PHOTO_ROW_LIMIT} bytes; '
                             f'the cut-outs of {self.video_name} are written through PIL')
-        return dict(cutout=cutout, dynamic=self.png_codes == 'dynamic' and O.OpList.png_photo_fits(W, 1))
+        forms = dict(cutout=cutout, dynamic=self.png_codes == 'dynamic' and O.OpList.png_photo_fits(W, 1))
+        if self.matte_refine is not None:            # (a saver without it builds its buffers with the arguments it always did)
+            forms['refine'] = True
+        return forms
 
     def _queue_matte(self, prob, out_hw, ids, all_ids, path_to_image, image_u8) -> dict:
         """Queue the composite launches of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the
@@ -740,7 +773,7 @@ class ResultSaver:
         targets = [obj_to_tmp[o] for o in wanted if o in obj_to_tmp]
         ol = O.OpList()
         need_matte = self.alpha_matte or self.cutout                 # the cut-out's fourth channel is the plane alpha_matte writes
-        frame = self._frame_u8(H, W, dev, path_to_image, image_u8) if (self.vis_modes or self.cutout) else None
+        frame = self._frame_u8(H, W, dev, path_to_image, image_u8) if (self.vis_modes or self.cutout or self.matte_refine is not None) else None
         if self.vis_modes:
             qtables, scratch = self._jpeg_setup(H, W, dev)
             colors = self._matte_colors(all_ids, dev) if any(m in ('davis', 'light', 'fade') for m in self.vis_modes) else None
@@ -755,17 +788,27 @@ class ResultSaver:
             ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=targets, matte=b.matte)
         if K > 0:
             ol.matte_soft(prob, b.planes[:K], out_hw=(H, W))
+        if b.refined is not None:                # the guided filter under the frame: K planes and the matte in one launch, 16 at a time
+            r, eps = self.matte_refine
+            n, cap = int(b.refined.shape[0]), O.OpList.GUIDED_MAX_PLANES
+            scratch = self._scratch.get('matte refine', (H, W, min(n, cap)),
+                                        lambda: torch.empty(O.OpList.guided_scratch_words(min(n, cap), H, W), dtype=torch.int32, device=dev))
+            for s0 in range(0, n, cap):
+                s1 = min(s0 + cap, n)
+                k1 = min(s1, K)
+                ol.guided_filter(frame, b.planes[s0:k1] if k1 > s0 else None, b.refined[s0:s1], scratch, radius=r, eps=eps,
+                                 last=b.matte if s1 > K else None)
         if b.dynamic:
             scratch = self._scratch.get('matte png dynamic', (H, W), lambda: torch.empty(O.OpList.png_photo_scratch_words(H, W, 1), dtype=torch.int32, device=dev))
             for k, slab in enumerate(b.png):
-                ol.png_photo(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch)
+                ol.png_photo(b.final_plane(k), slab.stream, slab.status, scratch)
         else:
             scratch = self._scratch.get('matte png', (H, W), lambda: torch.empty(O.OpList.png_scratch_words(H, W), dtype=torch.int32, device=dev))
             for k, slab in enumerate(b.png):
-                ol.png_deflate(b.planes[k] if k < K else b.matte, slab.stream, slab.status, scratch, H=H, W=W)
+                ol.png_deflate(b.final_plane(k), slab.stream, slab.status, scratch, H=H, W=W)
         if b.cutout is not None:                 # frame + matte -> RGBA, interleaved inside the stage: no RGBA buffer exists
             scratch = self._scratch.get('cutout', (H, W), lambda: torch.empty(O.OpList.png_photo_scratch_words(H, W, 4), dtype=torch.int32, device=dev))
-            ol.png_photo(frame, b.cutout.stream, b.cutout.status, scratch, last=b.matte)
+            ol.png_photo(frame, b.cutout.stream, b.cutout.status, scratch, last=b.final_plane(K))
         ol.run()
         for slab in b.jpeg + b.png + ([b.cutout] if b.cutout is not None else []):
             slab.copy()
@@ -886,7 +929,7 @@ class ResultSaver:
             self._put(self.output_root, 'cutout', stem + '.png', png_container.assemble_image(b.cutout.fetch(b.event), b.H, b.W, 4))
         elif b.cutout_mode == 'host':                # a row beyond the device stage's limit: frame and matte through PIL
             b.event.synchronize()
-            rgba = np.dstack([self._copies.to_host(job.matte_keep[2]), self._copies.to_host(b.matte)])
+            rgba = np.dstack([self._copies.to_host(job.matte_keep[2]), self._copies.to_host(b.final_plane(b.K))])     # (the refined plane under matte_refine)
             folder = path.join(self.output_root, self.video_name, 'cutout')
             os.makedirs(folder, exist_ok=True)
             Image.fromarray(rgba, 'RGBA').save(path.join(folder, stem + '.png'), compress_level=1)

@@ -122,10 +122,11 @@ class MatteBuffers(_Buffers):
     """What one frame in flight owns of the vis_modes / soft_masks / alpha_matte outputs: per mode the composed frame and the slab of its
     JPEG segment, the quantised planes (K soft masks, then the matte) and per plane the slab of its zlib stream; one event behind all copies."""
 
-    def __init__(self, H, W, K, modes, alpha, device, slab, *, cutout=None, dynamic=False):
+    def __init__(self, H, W, K, modes, alpha, device, slab, *, cutout=None, dynamic=False, refine=False):
         """``cutout``: None | 'device' (the slab of the RGBA cut-out's zlib stream) | 'host' (the frame is beyond the device stage's row
         limit: the writer thread encodes it with PIL from the frame and the matte).  ``dynamic``: the planes' streams come from the
-        filtered, dynamic-Huffman stage (ResultSaver png_codes='dynamic')."""
+        filtered, dynamic-Huffman stage (ResultSaver png_codes='dynamic').  ``refine``: the planes pass the guided filter
+        (ResultSaver matte_refine=) into ``refined`` -- the K soft masks, then the matte -- which the PNG stages read instead."""
         super().__init__(device)
         self.H, self.W, self.K, self.modes, self.alpha = H, W, K, tuple(modes), alpha
         self.cutout_mode, self.dynamic = cutout, bool(dynamic)
@@ -136,6 +137,14 @@ class MatteBuffers(_Buffers):
         self.matte = torch.empty((H, W), dtype=torch.uint8, device=device) if (alpha or cutout) else None   # (a tensor of its own: 16-byte aligned)
         self.png = [slab('png dynamic' if dynamic else 'png', H, W) for _ in range(K + (1 if alpha else 0))]
         self.cutout = slab('cutout', H, W) if cutout == 'device' else None
+        n = K + (1 if self.matte is not None else 0)
+        self.refined = torch.empty((n, H, W), dtype=torch.uint8, device=device) if (refine and n) else None
+
+    def final_plane(self, k):
+        """The plane the PNG stages encode: soft mask k < K, the matte at k == K; the refined one where the guided filter ran."""
+        if self.refined is not None:
+            return self.refined[k]
+        return self.planes[k] if k < self.K else self.matte
 
 
 class TrackBuffers(_Buffers):

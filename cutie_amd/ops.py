@@ -1054,6 +1054,81 @@ class OpList:
                                             min(scratch.numel(), (1 << 31) - 1)], [],
                         [None, None, src, stream, status, scratch, last])
 
+    GUIDED_MAX_RADIUS = 64    # csrc/guided.hip GF_RMAX
+    GUIDED_MAX_PLANES = 16    # GF_MAXS: planes per op; the host splits more over several ops
+    GUIDED_THREADS = 256      # GF_T: the columns a block holds, both halos of GUIDED_MAX_RADIUS included
+    GUIDED_TILE_X = 128       # GF_TX: output columns per block
+    GUIDED_TILE_Y = 64        # GF_TY: output rows per block (the column sums are rebuilt at every multiple of it)
+    GUIDED_EPS_MIN, GUIDED_EPS_MAX = 1e-6, 1.0
+
+    @staticmethod
+    def guided_scratch_words(S, H, W):
+        """int32 words of the scratch of guided_filter: the four fixed-point coefficients of every plane and pixel."""
+        return 4 * S * H * W
+
+    def guided_filter(self, guide, planes, out, scratch, *, radius, eps, last=None, ldrow=None):
+        """PROB_TO_ID flags == 32768 (ABI 11, form added; include/cutie_hip.h): the colour guided filter (He, Sun, Tang) of uint8 planes
+        under a uint8 guide -- every plane is fitted, per window of (2 radius + 1)^2 pixels clipped at the frame, as an affine function of
+        the guide's RGB, and the fits are averaged: the planes' edges move onto the guide's.  ``guide`` uint8 [H, W, 3] (packed pixels,
+        row stride ``ldrow`` bytes, default the tensor's, any alignment); ``planes`` uint8 [S0, H, W] (contiguous pixels, any row and
+        plane strides, any alignment) or None; ``last`` an optional uint8 [H, W] plane filtered as plane S0 (a matte that lives in a
+        tensor of its own); S = S0 + (last is not None), 1 <= S <= GUIDED_MAX_PLANES.  ``out`` uint8 [S, H, W] contiguous, overlapping no
+        input.  ``radius`` 1 .. GUIDED_MAX_RADIUS; ``eps`` GUIDED_EPS_MIN .. GUIDED_EPS_MAX in units of the guide scaled to [0, 1]
+        (carried as a float32).  ``scratch`` int32 [>= guided_scratch_words(S, H, W)].  Integer sums and a float64 solve in a fixed order:
+        the bytes are those of tests/guided_ref.py model, whatever the launch shape."""
+        _need_form(_lib.has_guided_filter, 'no guided filter, PROB_TO_ID flags == 32768')
+        who = 'guided_filter'
+        if guide.dtype != torch.uint8 or guide.dim() != 3 or guide.shape[2] != 3 or guide.stride(2) != 1 or guide.stride(1) != 3:
+            raise ValueError(f'{who}: guide is uint8 [H, W, 3] with packed pixels, not {guide.dtype} {tuple(guide.shape)} strides {guide.stride()}')
+        H, W = int(guide.shape[0]), int(guide.shape[1])
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f'{who}: a frame of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        ldg = int(guide.stride(0) if ldrow is None else ldrow)
+        if ldg < 3 * W:
+            raise ValueError(f"{who}: a guide row stride of {ldg} bytes below the row's {3 * W}")
+        S0 = 0
+        if planes is not None:
+            if planes.dtype != torch.uint8 or planes.dim() != 3 or tuple(planes.shape[1:]) != (H, W) or planes.stride(2) != 1:
+                raise ValueError(f'{who}: planes is uint8 [S, {H}, {W}] with contiguous pixels, not {planes.dtype} {tuple(planes.shape)} strides {planes.stride()}')
+            S0 = int(planes.shape[0])
+        if last is not None and (last.dtype != torch.uint8 or tuple(last.shape) != (H, W) or last.stride(1) != 1):
+            raise ValueError(f'{who}: last is a uint8 [{H}, {W}] plane with contiguous pixels')
+        S = S0 + (1 if last is not None else 0)
+        if not 1 <= S <= self.GUIDED_MAX_PLANES:
+            raise ValueError(f'{who}: {S} planes, 1 .. {self.GUIDED_MAX_PLANES} (split more over several ops)')
+        ldp, ps, ldl = 0, 0, int(last.stride(0)) if last is not None else 0
+        if S0:
+            ldp, ps = int(planes.stride(1)), int(planes.stride(0))
+            if ldp < W or (S0 > 1 and ps < (H - 1) * ldp + W) or ps >= 1 << 31:
+                raise ValueError(f'{who}: plane strides {planes.stride()}: rows of at least {W} bytes, planes that do not overlap, below 2^31')
+        if last is not None and ldl < W:
+            raise ValueError(f"{who}: a row stride of last of {ldl} bytes below the row's {W}")
+        radius = int(radius)
+        if not 1 <= radius <= self.GUIDED_MAX_RADIUS:
+            raise ValueError(f'{who}: radius {radius}, 1 .. {self.GUIDED_MAX_RADIUS}')
+        eps = float(eps)
+        if not np.float32(self.GUIDED_EPS_MIN) <= np.float32(eps) <= np.float32(self.GUIDED_EPS_MAX):     # as the launcher judges it (NaN fails both)
+            raise ValueError(f'{who}: eps {eps}, {self.GUIDED_EPS_MIN} .. {self.GUIDED_EPS_MAX}')
+        if out.dtype != torch.uint8 or tuple(out.shape) != (S, H, W) or not out.is_contiguous():
+            raise ValueError(f'{who}: out is a contiguous uint8 [{S}, {H}, {W}], not {out.dtype} {tuple(out.shape)}')
+        need = self.guided_scratch_words(S, H, W)
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < need:
+            raise ValueError(f'{who}: scratch is a contiguous int32 of at least {need} words')
+        for name, t in (('planes', planes), ('last', last), ('out', out), ('scratch', scratch)):
+            if t is not None and t.device != guide.device:
+                raise ValueError(f'{who}: {name} is on {t.device}, guide on {guide.device}')
+        spans = [('guide', guide.data_ptr(), (H - 1) * ldg + 3 * W)]
+        if S0:
+            spans.append(('planes', planes.data_ptr(), (S0 - 1) * ps + (H - 1) * ldp + W))
+        if last is not None:
+            spans.append(('last', last.data_ptr(), (H - 1) * ldl + W))
+        for name, at, n in spans:
+            if at < out.data_ptr() + S * H * W and out.data_ptr() < at + n:
+                raise ValueError(f'{who}: out overlaps {name}: the filter does not work in place')
+        words = int(scratch.numel())
+        return self.add(PROB_TO_ID, 32768, [0, H, W, radius, ldg, ldp, ps, words >> 31, words & 0x7fffffff, S0, ldl], [eps],
+                        [None, None, guide, out, None, scratch, planes, last])
+
     RLE_MAX_OBJECTS = 255
 
     @staticmethod

@@ -17,7 +17,7 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
     python -m cutie_amd.process_video -v FRAMES_DIR -m MASK_DIR -o OUT [--weights ckpt.pth] [--mem_every 10]
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
         [--vis MODE [MODE ...]] [--soft-masks] [--alpha] [--target-objects ID [ID ...]] [--layer FILE]
-        [--cutout] [--png-codes fixed|dynamic] [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
+        [--cutout] [--png-codes fixed|dynamic] [--refine-matte R [--refine-eps EPS]] [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
         [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
                             has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
 
@@ -32,6 +32,12 @@ float frame on the device, once per frame.
 the matte of the ``--target-objects``: the objects cut out, ready to composite.  Frame and matte are interleaved, filtered and coded with
 dynamic Huffman codes on the GPU (csrc/png_photo.hip).  ``--png-codes dynamic`` sends the soft masks and the alpha matte through the same
 encoder (the same pixels in fewer bytes); the default ``fixed`` keeps their bytes as they were.  The id masks never change encoder.
+
+``--refine-matte R`` (with ``--refine-eps EPS``, default 1e-4): the matte of ``--alpha``, the alpha of ``--cutout`` and the planes of
+``--soft-masks`` are probabilities computed at ``--max_internal_size`` and resampled to the frame: their edges are ramps on the coarse grid.
+The colour guided filter (He, Sun, Tang) fits every plane, per window of radius R pixels, as an affine function of the frame's RGB and
+averages the fits, which moves the planes' edges onto the frame's edges; it runs on the GPU between the planes and their PNG encoders
+(ResultSaver matte_refine, csrc/guided.hip).  The id masks and the --vis JPEGs keep their bytes.
 
 ``--trimap R_IN R_OUT``, ``--trimap-objects``, ``--dilate-mask R``: what matting and inpainting models take next to the frame, as 8-bit
 grey PNGs: OUT/trimap/*.png (255 sure foreground, 0 sure background, 128 the band of R_IN pixels inside and R_OUT pixels outside the edge
@@ -167,7 +173,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
                   region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0, polygons: bool = False,
-                  cutout: bool = False, png_codes: str = 'fixed') -> Dict:
+                  cutout: bool = False, png_codes: str = 'fixed', matte_refine=None) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
@@ -183,12 +189,14 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     output_dir/polygons/polygons.json, and 'polygons' (the json's content) in the result.
     cutout: per frame output_dir/cutout/*.png, the frame as RGBA with the alpha matte of the target objects as its fourth channel (the
     'rgba' output of the reference's interactive tool), filtered and entropy-coded on the device.  png_codes = 'fixed' | 'dynamic':
-    ResultSaver's -- 'dynamic' writes the soft masks and the alpha matte through that encoder too (the same pixels, fewer bytes)."""
+    ResultSaver's -- 'dynamic' writes the soft masks and the alpha matte through that encoder too (the same pixels, fewer bytes).
+    matte_refine = None | (r, eps): ResultSaver's -- the matte, the cut-out's alpha and the soft masks pass the colour guided filter with
+    the frame as the guide (radius r pixels, eps on the [0, 1] scale) before they are encoded; the id masks and the JPEGs keep their bytes."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
     vis_modes = tuple(vis_modes)
-    want_u8 = bool(vis_modes) or bool(cutout)                   # the modes and the cut-out read the uint8 frame; soft masks and the matte do not
+    want_u8 = bool(vis_modes) or bool(cutout) or matte_refine is not None   # the modes, the cut-out and the guided filter read the uint8 frame
     src = FrameSource(video, u8=(ingest == 'device'), packets=(ingest == 'device-decode'))
 
     def upload(f):
@@ -271,7 +279,8 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             tracks=TrackReport(path.basename(path.normpath(video))) if tracks else None,
                             min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity,
                             trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
-                            polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None, cutout=cutout, png_codes=png_codes)
+                            polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None, cutout=cutout, png_codes=png_codes,
+                            **({} if matte_refine is None else dict(matte_refine=matte_refine)))
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -329,6 +338,10 @@ def arg_parser() -> ArgumentParser:
     ap.add_argument('--cutout', action='store_true', help='the frame with the alpha matte of the target objects as its fourth channel: OUT/cutout/*.png (RGBA), encoded on the GPU')
     ap.add_argument('--png-codes', choices=('fixed', 'dynamic'), default='fixed',
                     help='the PNG encoder of the soft masks and the alpha matte: the id masks\' (fixed Huffman codes, default) or scanline filters + dynamic codes')
+    ap.add_argument('--refine-matte', type=int, metavar='R', default=None,
+                    help='refine the alpha matte, the cut-out\'s alpha and the soft masks with the colour guided filter under the frame: radius R, 1 .. 64 pixels')
+    ap.add_argument('--refine-eps', type=float, metavar='EPS', default=None,
+                    help='--refine-matte: the regulariser on the [0, 1] scale, 1e-6 .. 1 (default 1e-4); smaller follows the frame\'s edges more closely')
     ap.add_argument('--layer', metavar='FILE', help='the RGBA image of --vis layer (resized to the frames)')
     ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
                     help='--gt: device = the ground-truth PNGs are decoded on the GPU (default host: PIL)')
@@ -350,9 +363,26 @@ def arg_parser() -> ArgumentParser:
     return ap
 
 
+def refine_args(ap, args):
+    """--refine-matte / --refine-eps -> ResultSaver's matte_refine (None | (r, eps)); a bad combination is the parser's error."""
+    if args.refine_matte is None:
+        if args.refine_eps is not None:
+            ap.error('--refine-eps needs --refine-matte')
+        return None
+    eps = 1e-4 if args.refine_eps is None else args.refine_eps
+    if not 1 <= args.refine_matte <= 64:
+        ap.error(f'--refine-matte: a radius of {args.refine_matte}, 1 .. 64')
+    if not 1e-6 <= eps <= 1.0:
+        ap.error(f'--refine-eps: {eps}, 1e-6 .. 1')
+    if not (args.alpha or args.cutout or args.soft_masks):
+        ap.error('--refine-matte refines the planes of --alpha, --cutout and --soft-masks: none of them is set')
+    return (args.refine_matte, eps)
+
+
 def main():
     ap = arg_parser()
     args = ap.parse_args()
+    matte_refine = refine_args(ap, args)                        # (a bad combination ends here, before the model is loaded)
     if 'layer' in args.vis and not args.layer:
         ap.error('--vis layer needs --layer FILE')
     if args.decode_batch < 1:
@@ -372,7 +402,7 @@ def main():
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
                       decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
                       region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask,
-                      polygons=args.polygons, cutout=args.cutout, png_codes=args.png_codes)
+                      polygons=args.polygons, cutout=args.cutout, png_codes=args.png_codes, matte_refine=matte_refine)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

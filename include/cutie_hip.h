@@ -29,6 +29,8 @@ extern "C" {
 #define CUTIE_OP_NP 16
 #define CUTIE_MERGE_MAX_SOURCES 8   /* PROB_TO_ID flags&16 (ABI 8) */
 #define CUTIE_PNG_PHOTO_ROW_LIMIT 16384   /* PROB_TO_ID flags == 16384 (ABI 11, form added): filtered bytes per row, W * B + 1 */
+#define CUTIE_GUIDED_MAX_RADIUS 64  /* PROB_TO_ID flags == 32768 (ABI 11, form added): the largest window radius */
+#define CUTIE_GUIDED_MAX_PLANES 16  /* ... planes per op; the host splits more over several ops */
 #define CUTIE_EDT_MAX_LIMIT 65536   /* PROB_TO_ID flags == 4096 (ABI 11, form added): distances are exact below it; radii up to 255 (255^2 = 65025) */
 #define CUTIE_EDT_MAX_SETS 16       /* ... sets of ids per op; the host splits more over several ops */
 #define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
@@ -666,7 +668,55 @@ enum {
      *    The launcher refuses, each with its own message and before any launch: H, W < 1, c0 other than 1 or 3, L above the row limit, a
      *    row stride below a row's bytes, 9 H L + 10 ceil(H / 32) + 64 >= 2^31 stream bits, a negative capacity, a null p2, p4, p5 or p3
      *    (with i7 >= 4), p3 or p4 not 4-byte aligned, p5 not 16-byte aligned, fewer scratch words than needed.
-     *    cutie_amd/inference/utils/png.py assemble_image wraps the stream into a file (signature, IHDR, one IDAT, IEND). */
+     *    cutie_amd/inference/utils/png.py assemble_image wraps the stream into a file (signature, IHDR, one IDAT, IEND).
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 9, value 512, says the form is present -- a library from before
+     *    refuses such a descriptor as "unknown flags") -- edge-aware refinement of the matte planes (not in the reference; ResultSaver
+     *    matte_refine=, process_video --refine-matte / --refine-eps):
+     *  flags == 32768, a stage ON ITS OWN (32768 combined with any other flag stays the "unknown flags" error): the colour guided filter
+     *    (He, Sun, Tang, "Guided Image Filtering") of S uint8 planes under a uint8 RGB guide (kernels in guided.hip; the model:
+     *    tests/guided_ref.py; the bytes are equal).  Every plane is fitted, per window, as an affine function of the guide's RGB and the
+     *    fits of all windows that hold a pixel are averaged there: the planes' edges move onto the guide's.
+     *    p2 = guide uint8 [H, W, 3], pixels packed, i4 = its row stride in bytes (>= 3 W), any alignment.  i1 = H, i2 = W, H, W >= 1 and
+     *    H W < 2^31.  p6 = planes uint8 [S0, H, W], i9 = S0 >= 0, i5 = row stride (>= W), i6 = plane stride in bytes (>= (H - 1) i5 + W
+     *    when S0 > 1), any alignment; p7 = an optional further plane uint8 [H, W] with row stride i10 (>= W), filtered as plane S0 (a
+     *    matte in a buffer of its own).  S = S0 + (p7 != 0), 1 <= S <= CUTIE_GUIDED_MAX_PLANES.  The inputs are READ ONLY.
+     *    i3 = radius r, 1 <= r <= CUTIE_GUIDED_MAX_RADIUS.  f0 = eps, 1e-6 <= eps <= 1, in units of the guide scaled to [0, 1].
+     *    p3 = out uint8 [S, H, W] contiguous, any alignment; it overlaps neither an input nor the scratch.
+     *    p5 = scratch int32, 4-byte aligned, of i8 + 2^31 * i7 words (i7, i8 >= 0): at least 4 S H W (OpList.guided_scratch_words), the
+     *    coefficients.  Its content before and after the launch means nothing.  i0, p0, p1, p4 and the other floats are unused.
+     *    THE ARITHMETIC (binding; I_c = the guide's channel c = 0, 1, 2 as an integer 0 .. 255, p = a plane's byte):
+     *    WINDOW.  w(y, x) = the rows max(0, y - r) .. min(H - 1, y + r) and the columns max(0, x - r) .. min(W - 1, x + r): nothing exists
+     *      outside the frame.  N = its pixel count, <= 129^2 = 16641.
+     *    1 INTEGERS, exact, all sums over w(y, x).  Guide, once for all planes: S_c = sum I_c (3 values), S_cd = sum I_c I_d (6 values,
+     *      c <= d).  Per plane: T = sum p, T_c = sum I_c p.  In int64: C_cd = N S_cd - S_c S_d, g_c = N T_c - S_c T.  (N S_cd <= 16641^2
+     *      * 65025 ~ 1.8e13 < 2^53: every value converts to a double exactly, and no cancellation ever happens in floating point.)
+     *    2 FLOAT64 per pixel, IEEE 754 binary64, every operation rounded on its own (no fused multiply-add), in this order:
+     *        e = (((double)eps * 65025.0) * (double)N) * (double)N          (eps is the float of f0)
+     *        m00 = (double)C_00 + e   m11 = (double)C_11 + e   m22 = (double)C_22 + e   m01 = (double)C_01   m02 = (double)C_02   m12 = (double)C_12
+     *        a00 = m11 * m22 - m12 * m12      a01 = m02 * m12 - m01 * m22      a02 = m01 * m12 - m02 * m11
+     *        a11 = m00 * m22 - m02 * m02      a12 = m01 * m02 - m00 * m12      a22 = m00 * m11 - m01 * m01
+     *        det = (m00 * a00 + m01 * a01) + m02 * a02
+     *      (the symmetric adjugate of M = C + eps 65025 N^2 Id and its determinant: once per pixel, shared by the S planes), then per plane
+     *        a_0 = ((a00 * g_0 + a01 * g_1) + a02 * g_2) / det
+     *        a_1 = ((a01 * g_0 + a11 * g_1) + a12 * g_2) / det
+     *        a_2 = ((a02 * g_0 + a12 * g_1) + a22 * g_2) / det
+     *        b   = ((double)T - ((a_0 * (double)S_0 + a_1 * (double)S_1) + a_2 * (double)S_2)) / (double)N
+     *        A_c = sat_int32(rint(a_c * 1048576.0))     B = sat_int32(rint(b * 4096.0))       rint: round half to even
+     *      (a term "x * y - z * w" is two products and a difference.)  |a| <= sigma_p / (2 sqrt(eps)) <= 250 at eps = 1e-6, so |A| <=
+     *      2.7e8; |b| <= 255 (1 + 250 sqrt(3)), so |B| <= 4.6e8: both fit an int32, the saturation is a guard and not a path.  float64
+     *      because a grey guide (R = G = B) makes C rank 1: a float32 adjugate at eps = 1e-6 is wrong by tens of grey levels there.
+     *    3 INTEGERS, exact: sum A_c and sum B over w(y, x), in int64 (the coefficients of the windows centred in w(y, x)).
+     *    4 FLOAT64, as in 2:
+     *        q = (((((double)sum A_0 * (double)I_0 + (double)sum A_1 * (double)I_1) + (double)sum A_2 * (double)I_2) * 2^-20) + (double)sum B * 2^-12) / (double)N
+     *        out = (uint8)min(max(rint(q), 0), 255)        with I_c the guide at (y, x)
+     *    Consequences: a CONSTANT plane comes back unchanged, exactly (g_c = 0 as integers, so a = 0, b = the constant, B = 4096 times
+     *    it, q = it).  Every order-dependent sum is an integer sum and the float64 steps are per pixel: the bytes depend on the inputs, r
+     *    and eps alone -- not on the launch shape, the tiling, the summation order or timing; two runs give the same bytes.  (The
+     *    kernels slide integer sums along columns and take differences of prefix sums modulo 2^32: exact, a window sum is below 2^32.)
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1 or H W >= 2^31, a radius outside 1 ..
+     *    CUTIE_GUIDED_MAX_RADIUS, an eps outside 1e-6 .. 1 (NaN included), S outside 1 .. CUTIE_GUIDED_MAX_PLANES or a negative S0, a
+     *    null p2, p3, p5 or p6 (with S0 > 0), a guide row stride below 3 W, plane strides below a row's or a plane's bytes, p5 not 4-byte
+     *    aligned, a negative scratch size, fewer scratch words than 4 S H W, an output or a scratch that overlaps an input or each other. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -807,7 +857,7 @@ int cutie_op_struct_size(void);
  * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
  * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present.  bit 7 (value 128):
  * PROB_TO_ID flags == 8192, the polygon trace, is present.  bit 8 (value 256): PROB_TO_ID flags == 16384, the PNG stream with scanline
- * filters and dynamic Huffman codes, is present. */
+ * filters and dynamic Huffman codes, is present.  bit 9 (value 512): PROB_TO_ID flags == 32768, the colour guided filter, is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus

@@ -121,6 +121,13 @@ def has_guided_filter():
     return bool(load().cutie_hip_build_flags() & 512)
 
 
+def has_redact():
+    """Does the loaded library know PROB_TO_ID flags == 65536, the frame blurred, pixelated or filled under a weight plane?  Added without a
+    new ABI number; a library from before refuses such a descriptor as "unknown flags", so the callers ask first and say what is missing
+    (OpList.redact; ResultSaver redact=)."""
+    return bool(load().cutie_hip_build_flags() & 1024)
+
+
 class HipExecutor:
     """Runs op-descriptor arrays on the current torch HIP stream."""
     is_mock = False

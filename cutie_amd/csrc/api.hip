@@ -137,8 +137,8 @@ int cutie_hip_build_flags(void) {
     // bit 3: the mixed forms of the lock-step ops (clips with different object counts); bit 4: PROB_TO_ID flags == 1024, the track statistics;
     // bit 5: PROB_TO_ID flags == 2048, the region filter; bit 6: PROB_TO_ID flags == 4096, the distance transform and its bands;
     // bit 7: PROB_TO_ID flags == 8192, the polygon trace; bit 8: PROB_TO_ID flags == 16384, the filtered PNG stream with dynamic codes;
-    // bit 9: PROB_TO_ID flags == 32768, the colour guided filter
-    const int forms = 2 | 4 | 8 | 16 | 32 | 64 | 128 | 256 | 512;
+    // bit 9: PROB_TO_ID flags == 32768, the colour guided filter; bit 10: PROB_TO_ID flags == 65536, the redacted frame (blur, pixelate, fill)
+    const int forms = 2 | 4 | 8 | 16 | 32 | 64 | 128 | 256 | 512 | 1024;
 #ifdef CUTIE_DIAG
     return forms | 1;
 #else

@@ -134,4 +134,5 @@ int launch_edt_band(const cutie_op* op, hipStream_t s);                    // ed
 int launch_polygon_trace(const cutie_op* op, hipStream_t s);               // polygons.hip: PROB_TO_ID with flags == 8192 (ABI 11, form added)
 int launch_png_photo(const cutie_op* op, hipStream_t s);                   // png_photo.hip: PROB_TO_ID with flags == 16384 (ABI 11, form added)
 int launch_guided_filter(const cutie_op* op, hipStream_t s);               // guided.hip: PROB_TO_ID with flags == 32768 (ABI 11, form added)
+int launch_redact(const cutie_op* op, hipStream_t s);                      // redact.hip: PROB_TO_ID with flags == 65536 (ABI 11, form added)
 void cutie_set_error(const char* fmt, ...);

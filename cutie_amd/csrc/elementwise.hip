@@ -1724,6 +1724,7 @@ int launch_elementwise(const cutie_op* op, hipStream_t s) {
             if (op->flags == 8192) return launch_polygon_trace(op, s);                // the listed objects' outlines as rings of lattice corners (ABI 11, form added): a stage on its own
             if (op->flags == 16384) return launch_png_photo(op, s);                   // filtered, dynamic-Huffman PNG stream of a frame and / or a plane (ABI 11, form added): a stage on its own
             if (op->flags == 32768) return launch_guided_filter(op, s);               // colour guided filter of uint8 planes under the frame (ABI 11, form added): a stage on its own
+            if (op->flags == 65536) return launch_redact(op, s);                      // the frame blurred, pixelated or filled under a weight plane (ABI 11, form added): a stage on its own
             if (op->flags & ~31) { cutie_set_error("prob_to_id: unknown flags %d", op->flags); return -2; }
             const bool resample = op->flags & 4, deflate = op->flags & 8;
             if (op->flags & 16) {                                                     // S sources merged (ABI 8): every check before any launch

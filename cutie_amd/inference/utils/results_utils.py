@@ -66,7 +66,15 @@ background | 128 within r_out outside or r_in inside the edge | 255 sure foregro
 the frame, and the union dilated by the disk of radius ``dilate_mask`` (0 | 255).  Nothing exists outside the frame: an object cut by
 the frame's border is not eroded from there.  The planes go through the PNG stage and leave as 8-bit grey PNGs, like the soft masks:
 ``<output_root>/<video>/trimap/<frame>.png``, ``.../trimap_objects/<object id>/<frame>.png``, ``.../dilated/<frame>.png``.  The stage
-reads nothing but the plane, so it runs under both egress modes and in ``process_merged``.  Off: no launch, no file."""
+reads nothing but the plane, so it runs under both egress modes and in ``process_merged``.  Off: no launch, no file.
+
+``redact`` (not in the reference): the footage itself, edited with what the tracker knows -- the target objects
+blurred, pixelated or painted over in every frame, or with ``background`` everything but them.  Behind the id plane and the mattes one op
+list of its own: the weight plane (``edge='mask'``: the union of the targets on the plane of the file that is written, grown by the disk
+of ``grow`` pixels -- the ``dilate_mask`` call of the distance stage; ``edge='matte'``: the matte of the targets, the refined one under
+``matte_refine``), the effect and the blend (PROB_TO_ID flags == 65536, csrc/redact.hip: integers only, the bytes of tests/redact_ref.py)
+into an RGB buffer, and the JPEG stage of the vis modes on it.  ``<output_root>/<video>/redacted/<frame>.jpg``.  Off: no launch, no
+buffer, no file."""
 import logging
 import os
 import shutil
@@ -86,7 +94,7 @@ from . import coco_rle
 from . import jpeg_writer
 from . import png as png_container
 from .polygons import trace_rings
-from .saver_buffers import POLY_TABLE, RLE_TABLE, BandBuffers, EgressBuffers, KeyedCache, MatteBuffers, PolygonBuffers, Pool, RegionBuffers, Slab, TrackBuffers, WriterCopies
+from .saver_buffers import POLY_TABLE, RLE_TABLE, BandBuffers, EgressBuffers, KeyedCache, MatteBuffers, PolygonBuffers, Pool, RedactBuffers, RegionBuffers, Slab, TrackBuffers, WriterCopies
 
 log = logging.getLogger()
 
@@ -110,6 +118,58 @@ davis_palette = davis_palette_np.tobytes()
 
 
 EGRESS_MODES = ('host', 'device')
+REDACT_MODES = ('blur', 'pixelate', 'fill')
+REDACT_EDGES = ('mask', 'matte')
+REDACT_KEYS = ('mode', 'strength', 'color', 'grow', 'edge', 'background', 'targets')
+REDACT_DEFAULT_STRENGTH = {'blur': 12, 'pixelate': 16, 'fill': 0}     # a radius, a cell size, unused
+
+
+def redact_config(redact) -> dict:
+    """ResultSaver's ``redact`` with every key present and every value judged: ValueError names what is wrong."""
+    from ... import ops as O
+    if not isinstance(redact, dict):
+        raise ValueError(f'redact is None or a dict with the keys {REDACT_KEYS}, not {redact!r}')
+    unknown = sorted(set(redact) - set(REDACT_KEYS))
+    if unknown:
+        raise ValueError(f'redact: unknown keys {unknown}; the keys are {REDACT_KEYS}')
+    mode = redact.get('mode')
+    if mode not in REDACT_MODES:
+        raise ValueError(f'redact: mode is one of {REDACT_MODES}, not {mode!r}')
+    strength = redact.get('strength')
+    strength = REDACT_DEFAULT_STRENGTH[mode] if strength is None else strength
+    if isinstance(strength, bool) or not isinstance(strength, (int, np.integer)):
+        raise ValueError(f'redact: strength is an integer, not {strength!r}')
+    strength = int(strength)
+    if mode == 'blur' and not 1 <= strength <= O.OpList.REDACT_MAX_RADIUS:
+        raise ValueError(f'redact: blur radius {strength}, 1 .. {O.OpList.REDACT_MAX_RADIUS}')
+    if mode == 'pixelate' and not 2 <= strength <= O.OpList.REDACT_MAX_CELL:
+        raise ValueError(f'redact: pixelate cell {strength}, 2 .. {O.OpList.REDACT_MAX_CELL}')
+    color = redact.get('color', (0, 0, 0))
+    try:
+        rgb = tuple(int(v) for v in color)
+        ok = len(rgb) == 3 and all(0 <= v <= 255 for v in rgb) and all(int(v) == v for v in color)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'redact: color is three bytes (R, G, B), not {color!r}')
+    try:
+        grow = float(redact.get('grow', 0.0))
+    except (TypeError, ValueError):
+        grow = float('nan')
+    if not 0.0 <= grow <= 255.0:                                # (also refuses nan)
+        raise ValueError(f"redact: grow of {redact.get('grow')!r} pixels, 0 .. 255")
+    edge = redact.get('edge', 'mask')
+    if edge not in REDACT_EDGES:
+        raise ValueError(f'redact: edge is one of {REDACT_EDGES}, not {edge!r}')
+    if edge == 'matte' and grow != 0.0:
+        raise ValueError('redact: grow dilates the id mask; with edge=\'matte\' it must be 0')
+    targets = redact.get('targets')
+    if targets is not None:
+        try:
+            targets = [int(v) for v in targets]
+        except (TypeError, ValueError):
+            raise ValueError(f'redact: targets is None (all objects) or a list of object ids, not {targets!r}')
+    return dict(mode=mode, strength=strength, color=rgb, grow=grow, edge=edge, background=bool(redact.get('background', False)), targets=targets)
 PNG_CODES = ('fixed', 'dynamic')   # the encoder of the soft masks and the alpha matte: the id planes' (csrc/png.hip) | filters + dynamic Huffman (csrc/png_photo.hip)
 EGRESS_SLAB = 64 * 1024     # bytes of the first device-to-host copy of a frame: the status block + the head of the stream (a 480p mask is 5.5-7.9 KB)
 OVERLAY_MODES = ('host', 'device')
@@ -153,12 +213,14 @@ class _Job:
     polygons: Optional[PolygonBuffers] = None  # polygons: the frame's table, rings and vertices arrive in these (None with poly_meta: a frame without objects)
     poly_meta: Optional[Tuple] = None        # ... (frame index, object ids of the table's rows, H, W): the frame is reported
     bands: Optional[BandBuffers] = None      # trimap / trimap_objects / dilate_mask: the frame's band planes arrive in these
+    redact: Optional[RedactBuffers] = None   # redact: the JPEG segment of the redacted frame arrives in these
+    redact_keep: Tuple = ()                  # ... what the launches read (planes, frame, tables)
     band_planes: Tuple = ()                  # ... (folder, object id or None) of every plane, in plane order
 
     def held(self) -> list:
         """the pooled buffer sets of the frame, each once"""
         sets = []
-        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions, self.bands, self.polygons):
+        for b in (self.egress, self.overlay, self.matte, self.tracks, self.regions, self.bands, self.polygons, self.redact):
             if b is not None and not any(b is s for s in sets):
                 sets.append(b)
         return sets
@@ -170,7 +232,7 @@ class ResultSaver:
                  processor=None, egress='host', scorer=None, overlay='host', vis_modes=(), soft_masks=False, alpha_matte=False,
                  target_objects=None, layer=None, tracks=None, tracks_output_root=None, min_region=0, fill_holes=0, region_connectivity=8,
                  trimap=None, trimap_objects=False, dilate_mask=0.0, polygons=None, polygons_output_root=None, cutout=False, png_codes='fixed',
-                 matte_refine=None):
+                 matte_refine=None, redact=None):
         """``processor`` (optional, not in the reference): the InferenceCore whose fused PROB_TO_ID kernel does argmax+remap;
         without it a plain torch argmax + lookup is used (e.g. for probabilities that did not come from an InferenceCore).
         ``egress``: 'host' (default: the id plane is copied to the host and PIL encodes it) | 'device' (the GPU writes the PNG's zlib
@@ -224,7 +286,23 @@ class ResultSaver:
         (1e-6 .. 1) in units of the frame scaled to [0, 1].  The planes of a frame share one launch, up to 16 of them.  The 'popup' and
         'layer' JPEGs keep their bytes: they are composed from the float planes inside their own launch.  The id masks, trimaps and
         dilated masks are untouched.  Needs one of ``alpha_matte`` / ``cutout`` / ``soft_masks`` and the ``processor``; a ``use_long_id``
-        saver and ``process_merged`` refuse it."""
+        saver and ``process_merged`` refuse it.
+        ``redact``: None (default: no launch, no buffer, no file) | dict(mode='blur' | 'pixelate' | 'fill', strength=the blur radius 1 ..
+        64 (default 12) or the pixelate cell 2 .. 256 (default 16), color=(R, G, B) of 'fill', grow=pixels 0 .. 255 the targets' mask is
+        dilated by, edge='mask' (default: the id plane of the mask file, 0 | 255) | 'matte' (the soft matte of the targets, the refined
+        one under ``matte_refine``; grow must be 0), background=False | True (everything BUT the targets takes the effect: background
+        blur), targets=None (all objects) | object ids) -- per frame ``<video>/redacted/<frame>.jpg``, the frame with the effect
+        blended over it under that weight plane (PROB_TO_ID flags == 65536), through the JPEG stage and tables of
+        the vis modes.  Works under both egress modes; needs the ``processor`` and the frame (``image_u8`` or ``path_to_image``); a
+        ``use_long_id`` saver refuses it, and ``process_merged`` refuses edge='matte' (it has no probability planes of its own)."""
+        if redact is not None:
+            redact = redact_config(redact)
+            if use_long_id:
+                raise ValueError('redact: the weight plane is made from uint8 id planes; a use_long_id saver (RGB masks) cannot write redacted frames')
+            if processor is None:
+                raise ValueError('redact needs the processor (its device)')
+        self.redact = redact
+        self._redact_mask = redact is not None and redact['edge'] == 'mask'
         if matte_refine is not None:
             from ... import ops as O
             try:
@@ -367,7 +445,8 @@ class ResultSaver:
             tracks=Pool(limit, lambda: TrackBuffers(dev())),
             regions=Pool(limit, lambda: RegionBuffers(dev())),
             polygons=Pool(limit, lambda H, W: PolygonBuffers(H, W, dev(), self._slab)),
-            bands=Pool(limit, lambda H, W, S: BandBuffers(H, W, S, dev(), self._slab)))
+            bands=Pool(limit, lambda H, W, S: BandBuffers(H, W, S, dev(), self._slab)),
+            redact=Pool(limit, lambda H, W: RedactBuffers(H, W, dev(), self._slab, refine=self.matte_refine is not None)))
         self.thread = Thread(target=_writer, args=(self.queue,), daemon=True)
         self.thread.start()
 
@@ -456,6 +535,8 @@ class ResultSaver:
             raise ValueError('process_merged writes no scores: save_scores and the merge exclude each other')
         if self._matte_on:
             raise ValueError('process_merged has no probability planes of its own: vis_modes / soft_masks / alpha_matte / cutout need process')
+        if self.redact is not None and self.redact['edge'] == 'matte':
+            raise ValueError("process_merged has no probability planes of its own: redact with edge='matte' needs process")
         if self.processor is None:
             raise ValueError('process_merged needs the processor (its device; the merge has no host implementation)')
         own = {int(t): int(o.id) for t, o in self.object_manager.tmp_id_to_obj.items()}
@@ -508,7 +589,7 @@ class ResultSaver:
         elif id_stage is not None:
             ids = torch.empty((H, W), dtype=torch.int32 if self.use_long_id else torch.uint8, device=self.processor.network.device)
         else:
-            ids = mask.contiguous() if self._regions_on or self._bands_on or self.polygons is not None else mask
+            ids = mask.contiguous() if self._regions_on or self._bands_on or self.polygons is not None or self._redact_mask else mask
         fused = None if self._regions_on else png
         if id_stage is not None:
             id_stage(ol, ids, fused)
@@ -539,6 +620,8 @@ class ResultSaver:
             fields.update(self._queue_bands(ids, all_ids))
         if self.polygons is not None:
             fields.update(self._queue_polygons(ids, all_ids, frame_index))
+        if self.redact is not None:              # (behind the mattes: edge='matte' reads the plane they wrote)
+            fields.update(self._queue_redact(planes, out_hw, ids, all_ids, path_to_image, image_u8, fields.get('matte')))
         if on_device:
             b.png.copy()
             if rle:
@@ -815,6 +898,54 @@ class ResultSaver:
         b.event.record()
         return dict(matte=b, matte_objects=tuple(tmp_to_obj.get(q) for q in range(1, K + 1)), matte_keep=(prob, ol.keep, frame))
 
+    # ---- redact ---------------------------------------------------------------------------------------------------------------------
+    def _queue_redact(self, prob, out_hw, ids, all_ids, path_to_image, image_u8, matte) -> dict:
+        """Queue the redacted frame of one frame on the current stream, behind the stage that wrote ``ids`` (uint8 [H, W] on the device),
+        behind the region filter and behind the mattes (``matte``: the frame's MatteBuffers or None): the weight plane, the effect and
+        the blend, the JPEG stage, the pinned copy of its status and stream head, and one event.  -> the _Job fields.  Nothing waits."""
+        from ... import ops as O
+        dev = self.processor.network.device
+        H, W = int(out_hw[0]), int(out_hw[1])
+        rc = self.redact
+        frame = self._frame_u8(H, W, dev, path_to_image, image_u8)
+        b = self._pools['redact'].take(H, W)
+        ol = O.OpList()
+        if rc['edge'] == 'mask':                 # the dilate_mask call: the union of the targets, grown by the disk of `grow` pixels, 0 | 255
+            union = tuple(all_ids) if rc['targets'] is None else tuple(o for o in rc['targets'] if o in all_ids)
+
+            def table():
+                t = np.zeros((1, 256), dtype=np.uint8)
+                t[0, list(union)] = 1
+                return torch.from_numpy(t).to(dev)
+            sets = self._tables.get('redact', union, table)
+            scratch = self._scratch.get('redact band', (H, W), lambda: torch.empty(O.OpList.edt_scratch_words(1, H, W), dtype=torch.int32, device=dev))
+            ol.edt_band(ids, sets, scratch, band=b.weight, inner=0, outer=int(rc['grow'] * rc['grow']), mid=255)
+            weight = b.weight[0]
+        elif matte is not None and matte.matte is not None and rc['targets'] == self.target_objects:
+            weight = matte.final_plane(matte.K)  # the plane alpha_matte / cutout write, made by the launches queued before this list
+        else:                                    # no output of the frame holds the targets' matte: it is composed (and refined) here
+            if prob is None:
+                raise ValueError("redact with edge='matte' needs the probability planes")
+            prob = self._planes_f32(prob, dev)
+            obj_to_tmp = {int(o.id): int(t) for t, o in self.object_manager.tmp_id_to_obj.items() if int(t) < int(prob.shape[0])}
+            wanted = all_ids if rc['targets'] is None else rc['targets']
+            ol.matte_composite('alpha', None, out_hw=(H, W), planes=prob, targets=[obj_to_tmp[o] for o in wanted if o in obj_to_tmp], matte=b.weight[0])
+            weight = b.weight[0]
+            if b.refined is not None:
+                r, eps = self.matte_refine
+                scratch = self._scratch.get('redact refine', (H, W), lambda: torch.empty(O.OpList.guided_scratch_words(1, H, W), dtype=torch.int32, device=dev))
+                ol.guided_filter(frame, None, b.refined, scratch, radius=r, eps=eps, last=weight)
+                weight = b.refined[0]
+        key = (H, W, rc['mode'], rc['strength'])
+        scratch = self._scratch.get('redact', key, lambda: torch.empty(O.OpList.redact_scratch_words(rc['mode'], H, W, rc['strength']), dtype=torch.int32, device=dev))
+        ol.redact(frame, weight, b.out, scratch, mode=rc['mode'], strength=rc['strength'], color=rc['color'], invert=rc['background'])
+        qtables, scratch = self._jpeg_setup(H, W, dev)
+        ol.jpeg_encode(b.out, None, None, qtables, b.jpeg.stream, b.jpeg.status, scratch, H=H, W=W)
+        ol.run()
+        b.jpeg.copy()
+        b.event.record()
+        return dict(redact=b, redact_keep=(prob, ol.keep, frame, ids))
+
     def end(self):
         self.queue.put(None)
         self.queue.join()
@@ -980,6 +1111,20 @@ class ResultSaver:
             data = png_container.assemble(slab.fetch(b.event), b.H, b.W, None)
             self._put(self.output_root, folder if oid is None else path.join(folder, str(oid)), job.frame_name[:-4] + '.png', data)
 
+    def _write_redact(self, job):
+        """``redacted/<frame>.jpg``: the device's segment wrapped; a segment that did not fit the device stream: the buffer through PIL"""
+        b = job.redact
+        if b is None:
+            return
+        stem = job.frame_name[:-4]
+        segment = b.jpeg.fetch(b.event)
+        if segment is not None:
+            self._put(self.output_root, 'redacted', stem + '.jpg', jpeg_writer.wrap(segment, b.H, b.W, self._jpeg_tables[0]))
+        else:
+            folder = path.join(self.output_root, self.video_name, 'redacted')
+            os.makedirs(folder, exist_ok=True)
+            Image.fromarray(self._copies.to_host(b.out)).save(path.join(folder, stem + '.jpg'))
+
     def _write_overlay(self, job, rgb_mask):
         """``<frame>.jpg`` of ``visualize``: the device's segment wrapped (overlay='device'; no PIL), else the host's blend through PIL
         -- also for a frame whose segment did not fit the device stream."""
@@ -1034,6 +1179,7 @@ def _writer(queue: Queue):
             s._write_polygons(job)
             s._write_regions(job)
             s._write_bands(job)
+            s._write_redact(job)
             s._write_overlay(job, rgb_mask)
         except Exception as e:                                 # keep the queue draining; surface the problem
             log.error(f'result writer failed on {job.frame_name}: {e}')

@@ -188,6 +188,20 @@ class BandBuffers(_Buffers):
         self.png = [slab('png', H, W) for _ in range(S)]
 
 
+class RedactBuffers(_Buffers):
+    """What one frame in flight owns of the redacted frame (ResultSaver redact=): the weight plane (the dilated union of the targets, or
+    their matte when no other output of the frame holds it), the plane the guided filter refines it into (``refine``), the redacted RGB
+    frame, the slab of its JPEG segment and the event behind its copy."""
+
+    def __init__(self, H, W, device, slab, *, refine=False):
+        super().__init__(device)
+        self.H, self.W = H, W
+        self.weight = torch.empty((1, H, W), dtype=torch.uint8, device=device)
+        self.refined = torch.empty((1, H, W), dtype=torch.uint8, device=device) if refine else None
+        self.out = torch.empty((H, W, 3), dtype=torch.uint8, device=device)
+        self.jpeg = slab('jpeg', H, W)
+
+
 class Pool:
     """Buffer sets recycled between two threads: ``take(*key)`` gives a returned set of that key, a new ``make(*key)`` while fewer than
     ``limit`` sets are alive, else it blocks for the next set given back; a returned set of another key is dropped (and no longer counts).

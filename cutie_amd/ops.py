@@ -1129,6 +1129,87 @@ class OpList:
         return self.add(PROB_TO_ID, 32768, [0, H, W, radius, ldg, ldp, ps, words >> 31, words & 0x7fffffff, S0, ldl], [eps],
                         [None, None, guide, out, None, scratch, planes, last])
 
+    REDACT_MODES = {'blur': 0, 'pixelate': 1, 'fill': 2}     # i6 of PROB_TO_ID flags == 65536 (csrc/redact.hip)
+    REDACT_MAX_RADIUS = 64    # RD_RMAX, CUTIE_REDACT_MAX_RADIUS
+    REDACT_MAX_CELL = 256     # RD_CMAX, CUTIE_REDACT_MAX_CELL
+    REDACT_THREADS = 256      # RD_T: the pixel columns a block of a blur pass holds, both halos of the radius included (256 - 2 r of output)
+    REDACT_TILE_Y = (32, 64)  # RD_TY_SMALL, RD_TY_LARGE: output rows per block for r <= REDACT_SMALL_RADIUS and above it
+    REDACT_SMALL_RADIUS = 16  # RD_R_SMALL
+
+    @classmethod
+    def redact_scratch_words(cls, mode, H, W, strength=None):
+        """int32 words of the scratch of redact.  ``mode`` 'blur' | 'pixelate' | 'fill' (or its code): blur takes two uint8 RGB images,
+        each rounded up to a word; pixelate the column sums [ceil(H / c)][3 W] and the cells' bytes -- for the cell size ``strength``,
+        without it for c = 2, which holds every cell size; fill one word that is never touched (a tensor with a pointer)."""
+        code = cls.REDACT_MODES.get(mode, mode)
+        if code == 0:
+            return 2 * -(-3 * H * W // 4)
+        if code == 1:
+            c = 2 if strength is None else int(strength)
+            CY, CX = -(-H // c), -(-W // c)
+            return CY * 3 * W + -(-CY * CX * 3 // 4)
+        if code == 2:
+            return 1
+        raise ValueError(f'redact_scratch_words: mode is one of {tuple(cls.REDACT_MODES)}, not {mode!r}')
+
+    def redact(self, frame, weight, out, scratch, *, mode, strength=0, color=(0, 0, 0), invert=False, ldrow=None, ldw=None):
+        """PROB_TO_ID flags == 65536 (ABI 11, form added; include/cutie_hip.h): the frame with an effect blended over it under a weight
+        plane -- out = (w' e + (255 - w') f + 127) / 255 per byte, w' = ``weight`` (255 - weight with ``invert``), e the effect:
+        ``mode`` 'blur' (three box passes of radius ``strength``, 1 .. REDACT_MAX_RADIUS, every pass one 2-D window mean rounded once,
+        windows clipped at the frame), 'pixelate' (the rounded mean of the cell of ``strength`` x ``strength`` pixels, 2 ..
+        REDACT_MAX_CELL, anchored at the origin) or 'fill' (``color``, three bytes).  ``frame`` uint8 [H, W, 3] (packed pixels, row
+        stride ``ldrow`` bytes, default the tensor's, any alignment), ``weight`` uint8 [H, W] (contiguous pixels, row stride ``ldw``,
+        default the tensor's), both read only; ``out`` uint8 [H, W, 3] contiguous, overlapping neither; ``scratch`` int32 [>=
+        redact_scratch_words(mode, H, W, strength)].  Integers only: the bytes are those of tests/redact_ref.py, whatever the launch shape."""
+        _need_form(_lib.has_redact, 'no redacted frames, PROB_TO_ID flags == 65536')
+        who = 'redact'
+        if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[2] != 3 or frame.stride(2) != 1 or frame.stride(1) != 3:
+            raise ValueError(f'{who}: frame is uint8 [H, W, 3] with packed pixels, not {frame.dtype} {tuple(frame.shape)} strides {frame.stride()}')
+        H, W = int(frame.shape[0]), int(frame.shape[1])
+        if H < 1 or W < 1 or H * W >= 1 << 31:
+            raise ValueError(f'{who}: a frame of {H} x {W}: H, W >= 1 and H * W < 2^31')
+        code = self.REDACT_MODES.get(mode)
+        if code is None:
+            raise ValueError(f'{who}: mode is one of {tuple(self.REDACT_MODES)}, not {mode!r}')
+        if isinstance(strength, bool) or int(strength) != strength:
+            raise ValueError(f'{who}: strength is an integer, not {strength!r}')
+        strength = int(strength)
+        if code == 0 and not 1 <= strength <= self.REDACT_MAX_RADIUS:
+            raise ValueError(f'{who}: blur radius {strength}, 1 .. {self.REDACT_MAX_RADIUS}')
+        if code == 1 and not 2 <= strength <= self.REDACT_MAX_CELL:
+            raise ValueError(f'{who}: pixelate cell {strength}, 2 .. {self.REDACT_MAX_CELL}')
+        try:
+            rgb = [int(v) for v in color]
+        except (TypeError, ValueError):
+            rgb = []
+        if len(rgb) != 3 or any(not 0 <= v <= 255 for v in rgb):
+            raise ValueError(f'{who}: color is three bytes (R, G, B), not {color!r}')
+        ldf = int(frame.stride(0) if ldrow is None else ldrow)
+        if ldf < 3 * W:
+            raise ValueError(f"{who}: a frame row stride of {ldf} bytes below the row's {3 * W}")
+        if weight.dtype != torch.uint8 or tuple(weight.shape) != (H, W) or weight.stride(1) != 1:
+            raise ValueError(f'{who}: weight is a uint8 [{H}, {W}] plane with contiguous pixels, not {weight.dtype} {tuple(weight.shape)} strides {weight.stride()}')
+        ldw = int(weight.stride(0) if ldw is None else ldw)
+        if ldw < W:
+            raise ValueError(f"{who}: a weight row stride of {ldw} bytes below the row's {W}")
+        if out.dtype != torch.uint8 or tuple(out.shape) != (H, W, 3) or not out.is_contiguous():
+            raise ValueError(f'{who}: out is a contiguous uint8 [{H}, {W}, 3], not {out.dtype} {tuple(out.shape)}')
+        need = self.redact_scratch_words(code, H, W, strength)
+        if scratch.dtype != torch.int32 or not scratch.is_contiguous() or scratch.numel() < need:
+            raise ValueError(f'{who}: scratch is a contiguous int32 of at least {need} words')
+        for name, t in (('weight', weight), ('out', out), ('scratch', scratch)):
+            if t.device != frame.device:
+                raise ValueError(f'{who}: {name} is on {t.device}, frame on {frame.device}')
+        spans = [('frame', frame.data_ptr(), (H - 1) * ldf + 3 * W), ('weight', weight.data_ptr(), (H - 1) * ldw + W)]
+        for mine, at0, n0 in (('out', out.data_ptr(), 3 * H * W), ('scratch', scratch.data_ptr(), 4 * need)):
+            for name, at, n in spans:
+                if at < at0 + n0 and at0 < at + n:
+                    raise ValueError(f'{who}: {mine} overlaps {name}: the stage does not work in place')
+            spans = spans + [(mine, at0, n0)]
+        words = int(scratch.numel())
+        return self.add(PROB_TO_ID, 65536, [0, H, W, strength, ldf, ldw, code, words >> 31, words & 0x7fffffff, 1 if invert else 0,
+                                            rgb[0] | rgb[1] << 8 | rgb[2] << 16], [], [None, None, frame, out, None, scratch, weight])
+
     RLE_MAX_OBJECTS = 255
 
     @staticmethod

@@ -18,6 +18,7 @@ reference, on purpose: frames from a directory are RGB (the reference hands Open
         [--max_internal_size 480] [--mem_cleanup_ratio 0.9] [--num_objects N] [--model small] [--ingest device] [--egress device]
         [--vis MODE [MODE ...]] [--soft-masks] [--alpha] [--target-objects ID [ID ...]] [--layer FILE]
         [--cutout] [--png-codes fixed|dynamic] [--refine-matte R [--refine-eps EPS]] [--trimap R_IN R_OUT] [--trimap-objects] [--dilate-mask R]
+        [--redact blur|pixelate|fill [--redact-strength N] [--redact-color R G B] [--redact-grow R] [--redact-edge mask|matte] [--redact-background]]
         [--gt GT_DIR]      (prints the video's DAVIS J&F against GT_DIR/<frame number, 7 digits>.png, counted on the GPU: every frame that
                             has a ground-truth file is scored; cutie_amd/inference/utils/davis_metrics.py)
 
@@ -38,6 +39,13 @@ encoder (the same pixels in fewer bytes); the default ``fixed`` keeps their byte
 The colour guided filter (He, Sun, Tang) fits every plane, per window of radius R pixels, as an affine function of the frame's RGB and
 averages the fits, which moves the planes' edges onto the frame's edges; it runs on the GPU between the planes and their PNG encoders
 (ResultSaver matte_refine, csrc/guided.hip).  The id masks and the --vis JPEGs keep their bytes.
+
+``--redact blur|pixelate|fill``: the footage itself, edited on the GPU -- OUT/redacted/*.jpg, every frame with the ``--target-objects`` (all
+objects without it) blurred (three box passes of radius ``--redact-strength``, 1 .. 64, default 12), pixelated (cells of
+``--redact-strength`` pixels, 2 .. 256, default 16) or painted with ``--redact-color R G B`` (default black).  ``--redact-grow R`` dilates
+the objects' mask by the disk of R pixels first (0 .. 255: margins around faces and plates); ``--redact-edge matte`` blends under the soft
+matte of the objects instead of the hard mask (the refined one with ``--refine-matte``); ``--redact-background`` inverts the weight:
+everything but the objects takes the effect ("portrait mode").  ResultSaver redact, csrc/redact.hip, DESIGN.md section 26.
 
 ``--trimap R_IN R_OUT``, ``--trimap-objects``, ``--dilate-mask R``: what matting and inpainting models take next to the frame, as 8-bit
 grey PNGs: OUT/trimap/*.png (255 sure foreground, 0 sure background, 128 the band of R_IN pixels inside and R_OUT pixels outside the edge
@@ -173,7 +181,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                   gt_dir: Optional[str] = None, gt_decode: str = 'host', vis_modes=(), soft_masks: bool = False, alpha_matte: bool = False, target_objects=None,
                   layer=None, decode_batch: int = 1, tracks: bool = False, min_region: int = 0, fill_holes: int = 0,
                   region_connectivity: int = 8, trimap=None, trimap_objects: bool = False, dilate_mask: float = 0.0, polygons: bool = False,
-                  cutout: bool = False, png_codes: str = 'fixed', matte_refine=None) -> Dict:
+                  cutout: bool = False, png_codes: str = 'fixed', matte_refine=None, redact=None) -> Dict:
     """decode_batch = B > 1 (ingest='device-decode' only, ignored otherwise): B frames are decoded through one chain of launches
     (jpegs_to_device) and B frames wait on the device ahead of the step; the results are the same.
     gt_dir: ground-truth PNGs named like the outputs -- the video is scored on every frame that has one and 'scores' (SequenceScorer.finish)
@@ -191,12 +199,14 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
     'rgba' output of the reference's interactive tool), filtered and entropy-coded on the device.  png_codes = 'fixed' | 'dynamic':
     ResultSaver's -- 'dynamic' writes the soft masks and the alpha matte through that encoder too (the same pixels, fewer bytes).
     matte_refine = None | (r, eps): ResultSaver's -- the matte, the cut-out's alpha and the soft masks pass the colour guided filter with
-    the frame as the guide (radius r pixels, eps on the [0, 1] scale) before they are encoded; the id masks and the JPEGs keep their bytes."""
+    the frame as the guide (radius r pixels, eps on the [0, 1] scale) before they are encoded; the id masks and the JPEGs keep their bytes.
+    redact = None | dict: ResultSaver's -- per frame output_dir/redacted/*.jpg, the frame with the target objects (or, with background=True,
+    everything but them) blurred, pixelated or filled on the device."""
     if ingest not in INGEST_MODES:
         raise ValueError(f'ingest must be one of {INGEST_MODES}, not {ingest!r}')
     dev = network.device
     vis_modes = tuple(vis_modes)
-    want_u8 = bool(vis_modes) or bool(cutout) or matte_refine is not None   # the modes, the cut-out and the guided filter read the uint8 frame
+    want_u8 = bool(vis_modes) or bool(cutout) or matte_refine is not None or redact is not None   # the modes, the cut-out, the guided filter and the redaction read the uint8 frame
     src = FrameSource(video, u8=(ingest == 'device'), packets=(ingest == 'device-decode'))
 
     def upload(f):
@@ -280,7 +290,7 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
                             min_region=min_region, fill_holes=fill_holes, region_connectivity=region_connectivity,
                             trimap=trimap, trimap_objects=trimap_objects, dilate_mask=dilate_mask,
                             polygons=PolygonReport(path.basename(path.normpath(video))) if polygons else None, cutout=cutout, png_codes=png_codes,
-                            **({} if matte_refine is None else dict(matte_refine=matte_refine)))
+                            **({} if matte_refine is None else dict(matte_refine=matte_refine)), **({} if redact is None else dict(redact=redact)))
         total, n, cleanups = 0.0, 0, 0
         try:
             # the next frame is on the device while this one is stepped (decode_batch B: the next B frames, uploaded B at a time)
@@ -309,9 +319,10 @@ def process_video(network, cfg, video: str, mask_dir: str, output_dir: str, *, n
         out['polygons'] = saver.polygons.as_dict()
     if saver.regions is not None:
         out['regions'] = saver.regions
-    if vis_modes or soft_masks or alpha_matte or cutout:
+    if vis_modes or soft_masks or alpha_matte or cutout or redact is not None:
         out['folders'] = ([path.join(output_dir, 'visualization', m) for m in vis_modes] + ([path.join(output_dir, 'soft_masks')] if soft_masks else []) +
-                          ([path.join(output_dir, 'alpha')] if alpha_matte else []) + ([path.join(output_dir, 'cutout')] if cutout else []))
+                          ([path.join(output_dir, 'alpha')] if alpha_matte else []) + ([path.join(output_dir, 'cutout')] if cutout else []) +
+                          ([path.join(output_dir, 'redacted')] if redact is not None else []))
     return out
 
 
@@ -342,6 +353,14 @@ def arg_parser() -> ArgumentParser:
                     help='refine the alpha matte, the cut-out\'s alpha and the soft masks with the colour guided filter under the frame: radius R, 1 .. 64 pixels')
     ap.add_argument('--refine-eps', type=float, metavar='EPS', default=None,
                     help='--refine-matte: the regulariser on the [0, 1] scale, 1e-6 .. 1 (default 1e-4); smaller follows the frame\'s edges more closely')
+    ap.add_argument('--redact', choices=('blur', 'pixelate', 'fill'), default=None,
+                    help='OUT/redacted/*.jpg: every frame with the --target-objects (all objects without it) blurred, pixelated or painted over, on the GPU')
+    ap.add_argument('--redact-strength', type=int, metavar='N', default=None, help='--redact blur: the radius, 1 .. 64 (default 12); --redact pixelate: the cell size, 2 .. 256 (default 16)')
+    ap.add_argument('--redact-color', type=int, nargs=3, metavar=('R', 'G', 'B'), default=None, help='--redact fill: the colour, three bytes (default 0 0 0)')
+    ap.add_argument('--redact-grow', type=float, metavar='R', default=None, help='--redact: dilate the objects\' mask by the disk of R pixels first, 0 .. 255 (default 0)')
+    ap.add_argument('--redact-edge', choices=('mask', 'matte'), default=None,
+                    help='--redact: blend under the hard mask (default) or under the soft matte of the objects (the refined one with --refine-matte)')
+    ap.add_argument('--redact-background', action='store_true', help='--redact: everything BUT the objects takes the effect (background blur)')
     ap.add_argument('--layer', metavar='FILE', help='the RGBA image of --vis layer (resized to the frames)')
     ap.add_argument('--gt-decode', choices=('host', 'device'), default='host',
                     help='--gt: device = the ground-truth PNGs are decoded on the GPU (default host: PIL)')
@@ -379,10 +398,43 @@ def refine_args(ap, args):
     return (args.refine_matte, eps)
 
 
+def redact_args(ap, args):
+    """--redact and its companions -> ResultSaver's redact (None | dict); a bad combination is the parser's error."""
+    extras = [name for name, on in (('--redact-strength', args.redact_strength is not None), ('--redact-color', args.redact_color is not None),
+                                    ('--redact-grow', args.redact_grow is not None), ('--redact-edge', args.redact_edge is not None),
+                                    ('--redact-background', args.redact_background)) if on]
+    if args.redact is None:
+        if extras:
+            ap.error(f'{extras[0]} needs --redact')
+        return None
+    mode = args.redact
+    strength = {'blur': 12, 'pixelate': 16, 'fill': 0}[mode] if args.redact_strength is None else args.redact_strength
+    if mode == 'blur' and not 1 <= strength <= 64:
+        ap.error(f'--redact blur: a radius (--redact-strength) of {strength}, 1 .. 64')
+    if mode == 'pixelate' and not 2 <= strength <= 256:
+        ap.error(f'--redact pixelate: a cell (--redact-strength) of {strength}, 2 .. 256')
+    if mode == 'fill' and args.redact_strength is not None:
+        ap.error('--redact fill has no strength')
+    if args.redact_color is not None and mode != 'fill':
+        ap.error(f'--redact-color is the colour of --redact fill, not of {mode}')
+    color = tuple(args.redact_color) if args.redact_color is not None else (0, 0, 0)
+    if any(not 0 <= v <= 255 for v in color):
+        ap.error(f'--redact-color: three bytes, not {list(color)}')
+    grow = 0.0 if args.redact_grow is None else args.redact_grow
+    if not 0.0 <= grow <= 255.0:
+        ap.error(f'--redact-grow: {grow} pixels, 0 .. 255')
+    edge = args.redact_edge or 'mask'
+    if edge == 'matte' and grow != 0.0:
+        ap.error('--redact-grow dilates the id mask: with --redact-edge matte it must be 0')
+    return dict(mode=mode, strength=strength, color=color, grow=grow, edge=edge, background=bool(args.redact_background),
+                targets=None if args.target_objects is None else list(args.target_objects))
+
+
 def main():
     ap = arg_parser()
     args = ap.parse_args()
     matte_refine = refine_args(ap, args)                        # (a bad combination ends here, before the model is loaded)
+    redact = redact_args(ap, args)
     if 'layer' in args.vis and not args.layer:
         ap.error('--vis layer needs --layer FILE')
     if args.decode_batch < 1:
@@ -402,7 +454,7 @@ def main():
                       vis_modes=args.vis, soft_masks=args.soft_masks, alpha_matte=args.alpha, target_objects=args.target_objects, layer=args.layer,
                       decode_batch=args.decode_batch, tracks=args.tracks, min_region=args.min_region, fill_holes=args.fill_holes,
                       region_connectivity=args.region_connectivity, trimap=args.trimap, trimap_objects=args.trimap_objects, dilate_mask=args.dilate_mask,
-                      polygons=args.polygons, cutout=args.cutout, png_codes=args.png_codes, matte_refine=matte_refine)
+                      polygons=args.polygons, cutout=args.cutout, png_codes=args.png_codes, matte_refine=matte_refine, redact=redact)
     if args.gt is not None and r['scores'] is not None:
         from .inference.utils.davis_metrics import global_line, summarize
         print('J&F: ' + global_line(summarize({path.basename(path.normpath(args.video)): r['scores']})[0]))

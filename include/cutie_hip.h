@@ -31,6 +31,8 @@ extern "C" {
 #define CUTIE_PNG_PHOTO_ROW_LIMIT 16384   /* PROB_TO_ID flags == 16384 (ABI 11, form added): filtered bytes per row, W * B + 1 */
 #define CUTIE_GUIDED_MAX_RADIUS 64  /* PROB_TO_ID flags == 32768 (ABI 11, form added): the largest window radius */
 #define CUTIE_GUIDED_MAX_PLANES 16  /* ... planes per op; the host splits more over several ops */
+#define CUTIE_REDACT_MAX_RADIUS 64  /* PROB_TO_ID flags == 65536 (ABI 11, form added): the largest blur radius */
+#define CUTIE_REDACT_MAX_CELL 256   /* ... the largest pixelate cell */
 #define CUTIE_EDT_MAX_LIMIT 65536   /* PROB_TO_ID flags == 4096 (ABI 11, form added): distances are exact below it; radii up to 255 (255^2 = 65025) */
 #define CUTIE_EDT_MAX_SETS 16       /* ... sets of ids per op; the host splits more over several ops */
 #define CUTIE_JF_MAX_RADIUS 40      /* PROB_TO_ID flags == 64 (ABI 10): the largest match radius; 2160 x 3840 needs 36 */
@@ -716,7 +718,41 @@ enum {
      *    The launcher refuses, each with its own message and before any launch: H, W < 1 or H W >= 2^31, a radius outside 1 ..
      *    CUTIE_GUIDED_MAX_RADIUS, an eps outside 1e-6 .. 1 (NaN included), S outside 1 .. CUTIE_GUIDED_MAX_PLANES or a negative S0, a
      *    null p2, p3, p5 or p6 (with S0 > 0), a guide row stride below 3 W, plane strides below a row's or a plane's bytes, p5 not 4-byte
-     *    aligned, a negative scratch size, fewer scratch words than 4 S H W, an output or a scratch that overlaps an input or each other. */
+     *    aligned, a negative scratch size, fewer scratch words than 4 S H W, an output or a scratch that overlaps an input or each other.
+     * ABI 11, form added (the number stays 11; cutie_hip_build_flags() bit 10, value 1024, says the form is present -- a library from
+     *    before refuses such a descriptor as "unknown flags") -- redacted frames and background blur (not in the reference; ResultSaver
+     *    redact=, process_video --redact):
+     *  flags == 65536, a stage ON ITS OWN (65536 combined with any other flag stays the "unknown flags" error): the frame with an effect
+     *    -- blur, pixelate or a fill colour -- blended over it under a weight plane (kernels in redact.hip; the model: tests/redact_ref.py;
+     *    the bytes are equal).
+     *    p2 = frame uint8 [H, W, 3], pixels packed, i4 = its row stride in bytes (>= 3 W), any alignment.  p6 = weight plane w uint8
+     *    [H, W], i5 = its row stride (>= W), any alignment: 0 keeps the frame, 255 takes the effect, values between blend.  Both are READ
+     *    ONLY.  i1 = H, i2 = W, H, W >= 1 and H W < 2^31.  i6 = mode: 0 blur, 1 pixelate, 2 fill.  i3 = strength: the radius r of blur,
+     *    1 <= r <= CUTIE_REDACT_MAX_RADIUS; the cell size c of pixelate, 2 <= c <= CUTIE_REDACT_MAX_CELL; unused by fill.  i10 = the fill
+     *    colour, R | G << 8 | B << 16 (0 .. 2^24 - 1; read by fill only).  i9 = the invert bit, 0 or 1.
+     *    p3 = out uint8 [H, W, 3] contiguous, any alignment; it overlaps neither an input nor the scratch.
+     *    p5 = scratch int32, 4-byte aligned, of i8 + 2^31 * i7 words (i7, i8 >= 0), at least OpList.redact_scratch_words(mode, H, W):
+     *    blur 2 ceil(3 H W / 4) (two uint8 RGB images), pixelate ceil(H / c) 3 W + ceil(3 ceil(H / c) ceil(W / c) / 4) (column sums and
+     *    the cells' bytes), fill 1 (never touched; the pointer is not null).  Its content before and after the launch means nothing.
+     *    i0, p0, p1, p4, p7 and the floats are unused.
+     *    THE ARITHMETIC (binding; integers only; f = the frame's byte, every channel on its own, "/" = floor division of non-negative
+     *    integers):
+     *    BLUR.  Exactly three passes.  One pass maps a uint8 image a to a': with w(y, x) = the rows max(0, y - r) .. min(H - 1, y + r) and
+     *      the columns max(0, x - r) .. min(W - 1, x + r) -- nothing exists outside the frame --, N its pixel count (<= 129^2 = 16641)
+     *      and S the sum of a over it, a'(y, x) = (2 S + N) / (2 N): ONE 2-D window mean rounded once, not a rounded row mean followed by
+     *      a rounded column mean.  The effect e is the third pass's output (three boxes of radius r: a Gaussian of sigma about
+     *      sqrt(r (r + 1))).  S <= 255 * 16641 < 2^23: the kernels slide sums and take prefix differences modulo 2^32, exactly.
+     *    PIXELATE.  Cell (Y, X) holds the rows Y c .. min(H, (Y + 1) c) - 1 and the columns X c .. min(W, (X + 1) c) - 1: anchored at the
+     *      frame's origin, cut by its far edges.  With n the cell's pixel count and S its sum, e = (2 S + n) / (2 n) for every pixel of it.
+     *    FILL.  e = the colour's byte.
+     *    BLEND.  w' = w, or 255 - w with the invert bit; out = (w' e + (255 - w') f + 127) / 255.
+     *    Consequences: w' == 0 returns the frame's byte and w' == 255 returns e, both exactly; a CONSTANT frame comes back unchanged under
+     *    blur and pixelate for every w.  Every order-dependent sum is an integer sum: the bytes depend on the inputs, the mode and the
+     *    strength alone -- not on the launch shape, the tiling or timing; two runs give the same bytes.
+     *    The launcher refuses, each with its own message and before any launch: H, W < 1 or H W >= 2^31, an unknown mode, a radius outside
+     *    1 .. CUTIE_REDACT_MAX_RADIUS, a cell outside 2 .. CUTIE_REDACT_MAX_CELL, an invert word other than 0 or 1 or a colour beyond three
+     *    bytes, a null p2, p6, p3 or p5, a frame row stride below 3 W, a weight row stride below W, p5 not 4-byte aligned, a negative
+     *    scratch size, fewer scratch words than needed, an output or a scratch that overlaps an input or each other. */
     CUTIE_OP_PROB_TO_ID = 36,
     /* RESIZE: F.interpolate(x, size=(OH,OW)) -- the max_internal_size path of InferenceCore.step (inference_core.py:206-228,
      * 321-326): bilinear align_corners=False without antialias (flags&1 == 0) or nearest-exact (flags&1, index masks).
@@ -857,7 +893,8 @@ int cutie_op_struct_size(void);
  * bit 4 (value 16): PROB_TO_ID flags == 1024, the track statistics, is present.  bit 5 (value 32): PROB_TO_ID flags == 2048, the region
  * filter, is present.  bit 6 (value 64): PROB_TO_ID flags == 4096, the distance transform and its bands, is present.  bit 7 (value 128):
  * PROB_TO_ID flags == 8192, the polygon trace, is present.  bit 8 (value 256): PROB_TO_ID flags == 16384, the PNG stream with scanline
- * filters and dynamic Huffman codes, is present.  bit 9 (value 512): PROB_TO_ID flags == 32768, the colour guided filter, is present. */
+ * filters and dynamic Huffman codes, is present.  bit 9 (value 512): PROB_TO_ID flags == 32768, the colour guided filter, is present.
+ * bit 10 (value 1024): PROB_TO_ID flags == 65536, the redacted frame (blur, pixelate, fill under a weight plane), is present. */
 int cutie_hip_build_flags(void);
 
 #ifdef __cplusplus
